@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- env-steps/s of the batched quantum-dot tuning env on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config headline|config2|config1|mixed]
+    python bench.py --gpus N --steps K --warmup W [--config headline|config2|config1|mixed] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (metric, value, unit, ms_per_step, ...).
+--full adds what takes runs of its own: per-kernel times and the roofline / VALU figures, and (one GPU) the CPU baseline
+of the plain-C oracle with the parity check of env 0.  --dump-outputs DIR writes what the last timed step returned
+(dump_outputs below), so that two builds can be compared output for output on identical seeded inputs.
 
 One "step" = one VecQuantumDeviceEnv.step over the whole batch: action rescale + reward, N-1 CSD channels
 (exact k-best candidates -> tunnel-coupled ground state -> sensor), percentile normalisation, global +
@@ -81,6 +86,45 @@ def profile_figures(N, R):
     return ent
 
 
+def kernel_figures(ek, Nk, R):
+    """--full: (roofline, valu) of the heaviest bucket `ek` (Nk dots).  Every hot kernel by itself: HIP events inside the
+    library, on the launch stream, one launch chunk (`chunk` envs) per launch, on the state the timed steps left behind
+    (the random-action regime)."""
+    kms = ek.time_kernels(iters=2)
+    chunk = ek.chunk_envs()
+    dom = max(kms, key=kms.get); dom_ms = kms[dom]
+    achieved = b_alg(Nk, R) * chunk / (dom_ms * 1e-3) / 1e9
+    prof = profile_figures(Nk, R)
+    pk = ((prof or {}).get("kernels") or {}).get(dom) or {}
+    traffic = pk.get("hbm_bytes_per_env_step")
+    if traffic is not None:
+        traffic = traffic * chunk
+    roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "kernel": f"{dom}<{Nk}>", "kernel_ms": dom_ms, "envs_per_launch": chunk,
+                "algorithmic_bytes_per_env_step": b_alg(Nk, R),
+                "kernels_ms": {f"{k}<{Nk}>" if k != "qd_k_gs_solve" else "qd_k_gs_solve<all size classes>": v for k, v in kms.items()},
+                "traffic_source": (None if traffic is None else
+                                   {"file": "profiles/counters.json", "profile": prof.get("profile"),
+                                    "git_rev": prof.get("git_rev"), "kernel_src_sha": prof.get("kernel_src_sha")}),
+                "note": "the faithful path is float64 VALU/LDS bound, not HBM bound (SURVEY 7-H1); "
+                        "the HBM fraction is reported as the contract asks, the VALU figures below say how busy "
+                        "the pipeline that binds is; see DESIGN.md"}
+    # The roofline that binds: float64 vector issue.  From the rocprofv3 PMC passes under profiles/ (quoted only when
+    # they were taken on THIS kernel source): per hot kernel the vector-ALU issue utilisation (SQ_ACTIVE_INST_VALU x 4
+    # cycles / (duration of the same profiled dispatch x 2.4 GHz x 1024 SIMDs)), the enabled-lane fraction
+    # (SQ_THREAD_CYCLES_VALU / (64 x SQ_ACTIVE_INST_VALU)) and the achieved lane-instruction rate against the peak of
+    # 256 CUs x 4 SIMDs x 16 lanes/clk x 2.4 GHz = 39.3e12 lane-instructions/s (= 78.6 TFLOP/s if every one were an FMA).
+    valu = ({"peak_lane_instr_per_s": FP64_VECTOR_PEAK_TFLOPS / 2 * 1e12, "fp64_vector_peak_tflops": FP64_VECTOR_PEAK_TFLOPS,
+             "kernels": {k: {f: v.get(f) for f in ("valu_issue_utilisation", "enabled_lane_fraction", "lane_instr_per_s",
+                                                    "frac_of_peak_lane_instr", "insts_valu_per_pixel", "profiled_ms")}
+                         for k, v in prof["kernels"].items()},
+             "source": {"file": "profiles/counters.json", "profile": prof.get("profile"), "workload": prof.get("workload")}}
+            if prof else {"peak_lane_instr_per_s": FP64_VECTOR_PEAK_TFLOPS / 2 * 1e12, "kernels": None,
+                          "note": "no PMC profile of this kernel source under profiles/ (scripts/collect_profiles.sh)"})
+    return roofline, valu
+
+
 def cpu_baseline_and_parity(N, R, seed, seconds_budget=15.0):
     """The oracle leg.  (1) cpu_baseline: the plain-C oracle (literal reference algorithm: 4^N scan + dense 32x32
     eigensolve, OpenMP) timed on the host cores over whole CSD channels of env 0 of the workload (same device,
@@ -140,6 +184,43 @@ def cpu_baseline_and_parity(N, R, seed, seconds_budget=15.0):
     return base, parity
 
 
+DUMP_BYTES = 60 * 10 ** 6          # --dump-outputs stays under 64 MB, .npy headers included
+DUMP_SEED = 2024
+
+
+def dump_sample(B, bytes_per_env, budget):
+    """Env ids whose outputs --dump-outputs writes: all B if they fit the byte budget, else a fixed seeded sample (sorted),
+    the same in every run and every build."""
+    import numpy as np
+    k = min(B, max(1, budget // bytes_per_env))
+    if k == B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(B, k, replace=False))
+
+
+def dump_outputs(path, results):
+    """--dump-outputs: what the last timed step returned to its caller -- per dot count N the observation dict (global
+    image, per-agent plunger / barrier images, observed voltages), rewards, terminated and truncated -- as DIR/<name>.npy in
+    float32 (rewards float64; the boolean flags as 0/1 float32).  Every array holds the same envs (dump_sample: the whole
+    batch if it fits DUMP_BYTES, else a seeded sample); a mixed batch prefixes the names with '<N>dot_'."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for N, (obs, rew, term, trunc) in sorted(results.items()):
+        arrays = dict(obs, rewards=rew, terminated=term.to(torch.float32), truncated=trunc.to(torch.float32))
+        B = rew.shape[0]
+        per_env = sum(t[0].numel() * t.element_size() for t in arrays.values())
+        idx = torch.as_tensor(dump_sample(B, per_env, DUMP_BYTES // len(results)), device=rew.device)
+        prefix = f"{N}dot_" if len(results) > 1 else ""
+        for name, t in arrays.items():
+            a = t.index_select(0, idx).cpu().numpy()
+            assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+            np.save(os.path.join(path, prefix + name + ".npy"), a)
+            total += a.nbytes
+    assert total <= DUMP_BYTES, total
+
+
 # ----------------------------------------------------------------------------------------------
 def launch_ranks(args, argv):
     """--gpus N without torchrun: start N rank processes from a parent that never touches the GPU.  Every rank prints its
@@ -193,8 +274,13 @@ def build_parser():
     ap.add_argument("--dots", type=int, default=None)
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU")
     ap.add_argument("--resolution", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel times with the roofline / VALU figures and, on one GPU, the CPU baseline and the "
+                         "oracle parity check of env 0 (each takes runs of its own after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity check")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: time budget of the CPU baseline")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for the barrier / max-time reduction (gloo: rehearsal of N>1 on one GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: all ranks use cuda:0")
@@ -209,7 +295,10 @@ def build_parser():
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             sys.exit(launch_ranks(args, argv))
@@ -266,11 +355,11 @@ def run_rank(args, rank, world, local):
         env.stagger_episodes()
 
     def one_step():
+        """{N: (obs, rewards, terminated, truncated)} of the step"""
         if mixed:
-            env.step({n: (torch.rand((e.B, 2 * n - 1), generator=gen) * 2 - 1).to(dev) for n, e in parts.items()},
-                     auto_reset=True)
-        else:
-            env.step((torch.rand((B, 2 * N - 1), generator=gen) * 2 - 1).to(dev), auto_reset=True)
+            return env.step({n: (torch.rand((e.B, 2 * n - 1), generator=gen) * 2 - 1).to(dev) for n, e in parts.items()},
+                            auto_reset=True)
+        return {N: env.step((torch.rand((B, 2 * N - 1), generator=gen) * 2 - 1).to(dev), auto_reset=True)}
 
     for _ in range(args.warmup):
         one_step()
@@ -281,7 +370,7 @@ def run_rank(args, rank, world, local):
     t0 = time.perf_counter()
     n_resets = 0
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
         n_resets += sum(int((e._steps_host == 0).sum()) for e in parts.values())
     torch.cuda.synchronize(dev)
     if dist:
@@ -294,20 +383,10 @@ def run_rank(args, rank, world, local):
     dt = shard.max_over_ranks(dt, device=dev if args.backend == "nccl" else None)   # identity when not distributed
 
     if rank == 0:
+        if args.dump_outputs:          # before --full's kernel timings, which launch again on the env's buffers
+            dump_outputs(args.dump_outputs, last)
         total_env_steps = B * world * args.steps
         value = total_env_steps / dt
-        # every hot kernel of the heaviest bucket by itself: HIP events inside the library, on the launch stream, one launch
-        # chunk (`chunk` envs) per launch, on the state the timed steps left behind (the random-action regime)
-        Nk = max(parts); ek = parts[Nk]
-        kms = ek.time_kernels(iters=2)
-        chunk = ek.chunk_envs()
-        dom = max(kms, key=kms.get); dom_ms = kms[dom]
-        achieved = b_alg(Nk, R) * chunk / (dom_ms * 1e-3) / 1e9
-        prof = profile_figures(Nk, R)
-        pk = ((prof or {}).get("kernels") or {}).get(dom) or {}
-        traffic = pk.get("hbm_bytes_per_env_step")
-        if traffic is not None:
-            traffic = traffic * chunk
         if mixed:
             workload = (f"mixed N in {{2,4,6,8}} ragged batch, {B} envs per GPU ({B // 4} per dot count), {R}x{R} CSD, "
                         "latched-state model on, buckets on separate HIP streams")
@@ -329,35 +408,15 @@ def run_rank(args, rank, world, local):
                        "resolution": R, "resets_in_timed_region": n_resets,
                        "target": "BASELINE.json asks >= 1e6 env-steps/s; the faithful float64 algorithm is far below it "
                                  "(see DESIGN.md 9), this line reports what is measured"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": f"{dom}<{Nk}>", "kernel_ms": dom_ms, "envs_per_launch": chunk,
-                         "algorithmic_bytes_per_env_step": b_alg(Nk, R),
-                         "kernels_ms": {f"{k}<{Nk}>" if k != "qd_k_gs_solve" else "qd_k_gs_solve<all size classes>": v for k, v in kms.items()},
-                         "traffic_source": (None if traffic is None else
-                                            {"file": "profiles/counters.json", "profile": prof.get("profile"),
-                                             "git_rev": prof.get("git_rev"), "kernel_src_sha": prof.get("kernel_src_sha")}),
-                         "note": "the faithful path is float64 VALU/LDS bound, not HBM bound (SURVEY 7-H1); "
-                                 "the HBM fraction is reported as the contract asks, the VALU figures below say how busy "
-                                 "the pipeline that binds is; see DESIGN.md"},
-            # The roofline that binds: float64 vector issue.  From the rocprofv3 PMC passes under profiles/ (quoted only when
-            # they were taken on THIS kernel source): per hot kernel the vector-ALU issue utilisation (SQ_ACTIVE_INST_VALU x 4
-            # cycles / (duration of the same profiled dispatch x 2.4 GHz x 1024 SIMDs)), the enabled-lane fraction
-            # (SQ_THREAD_CYCLES_VALU / (64 x SQ_ACTIVE_INST_VALU)) and the achieved lane-instruction rate against the peak of
-            # 256 CUs x 4 SIMDs x 16 lanes/clk x 2.4 GHz = 39.3e12 lane-instructions/s (= 78.6 TFLOP/s if every one were an FMA).
-            "valu": ({"peak_lane_instr_per_s": FP64_VECTOR_PEAK_TFLOPS / 2 * 1e12, "fp64_vector_peak_tflops": FP64_VECTOR_PEAK_TFLOPS,
-                      "kernels": {k: {f: v.get(f) for f in ("valu_issue_utilisation", "enabled_lane_fraction", "lane_instr_per_s",
-                                                             "frac_of_peak_lane_instr", "insts_valu_per_pixel", "profiled_ms")}
-                                  for k, v in prof["kernels"].items()},
-                      "source": {"file": "profiles/counters.json", "profile": prof.get("profile"), "workload": prof.get("workload")}}
-                     if prof else {"peak_lane_instr_per_s": FP64_VECTOR_PEAK_TFLOPS / 2 * 1e12, "kernels": None,
-                                   "note": "no PMC profile of this kernel source under profiles/ (scripts/collect_profiles.sh)"}),
             "kernel_src_sha": kernel_source_hash(), "git_rev": git_rev(),
         }
-        if not args.no_cpu_baseline and world == 1:          # reported at N = 1 only
-            base, parity = cpu_baseline_and_parity(Nk, R, seed, args.cpu_seconds)
-            out["cpu_baseline"] = base
-            out["parity"] = parity
+        if args.full:
+            Nk = max(parts)
+            out["roofline"], out["valu"] = kernel_figures(parts[Nk], Nk, R)
+            if not args.no_cpu_baseline and world == 1:          # reported at N = 1 only
+                base, parity = cpu_baseline_and_parity(Nk, R, seed, args.cpu_seconds)
+                out["cpu_baseline"] = base
+                out["parity"] = parity
         print(json.dumps(out), flush=True)
     env.close()
     if dist:

@@ -5,13 +5,13 @@
 # rocprofv3 --kernel-trace --stats of the headline bench command, and the PMC passes on the kernel micro-benchmark.
 tag=${1:-r03}; out=gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
-python bench.py --steps 10 --warmup 3 > $out/bench_headline.json 2> $out/bench_headline.err || echo "headline failed"
-python bench.py --steps 10 --warmup 3 --noise --no-cpu-baseline > $out/bench_headline_noise_on.json 2> /dev/null || echo "noise failed"
-python bench.py --config config2 --steps 30 --warmup 5 --cpu-seconds 5 > $out/bench_config2_4dot_256env.json 2> /dev/null || echo "config2 failed"
-python bench.py --config config1 --steps 200 --warmup 20 --cpu-seconds 3 > $out/bench_config1_2dot_1env.json 2> /dev/null || echo "config1 failed"
-python bench.py --config mixed --envs 1024 --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_config5_mixed_1024env.json 2> /dev/null || echo "mixed failed"
-python bench.py --gpus 2 --share-gpu --backend gloo --envs 1024 --steps 6 --warmup 2 > $out/bench_2ranks_rehearsal_one_gpu.json 2> /dev/null || echo "2-rank failed"
-rocprofv3 --kernel-trace --stats -d $out/kstats --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $out/kstats.log 2>&1 || echo "kstats failed"
+python bench.py --full --steps 10 --warmup 3 > $out/bench_headline.json 2> $out/bench_headline.err || echo "headline failed"
+python bench.py --full --steps 10 --warmup 3 --noise --no-cpu-baseline > $out/bench_headline_noise_on.json 2> /dev/null || echo "noise failed"
+python bench.py --full --config config2 --steps 30 --warmup 5 --cpu-seconds 5 > $out/bench_config2_4dot_256env.json 2> /dev/null || echo "config2 failed"
+python bench.py --full --config config1 --steps 200 --warmup 20 --cpu-seconds 3 > $out/bench_config1_2dot_1env.json 2> /dev/null || echo "config1 failed"
+python bench.py --full --config mixed --envs 1024 --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_config5_mixed_1024env.json 2> /dev/null || echo "mixed failed"
+python bench.py --full --gpus 2 --share-gpu --backend gloo --envs 1024 --steps 6 --warmup 2 > $out/bench_2ranks_rehearsal_one_gpu.json 2> /dev/null || echo "2-rank failed"
+rocprofv3 --kernel-trace --stats -d $out/kstats --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $out/kstats.log 2>&1 || echo "kstats failed"
 cp $out/kstats/*/*kernel_stats.csv $out/kernel_stats_bench_headline.csv 2>/dev/null
 # PMC passes on ONE launch chunk of the bench (CHUNK envs, 8-dot 64x64) in the bench's regime: envs reset, then stepped with
 # uniform random actions for e % 12 + 1 steps (kbench mode wild12); the last dispatch of every kernel is the timed launch
