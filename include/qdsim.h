@@ -80,7 +80,10 @@ typedef struct qd_config {
     int32_t gate_curve_type;      /* QD_CURVE_* (reward.gate_curve_type, env.py:430-441) */
     int32_t update_method;        /* QD_UPDATE_KALMAN / QD_UPDATE_DIRECT (KalmanUpdater.py / DirectUpdater.py) */
     int32_t cnn_outputs;          /* 3: [NN, NNN_right, NNN_left]; 2: legacy nearest_neighbour [RL, LR] (env.py:592-618) */
-    int32_t reserved0;
+    int32_t num_charge_states;    /* K, latched_model.num_charge_states (qarray_config.yaml:129): kept charge states per
+                                     pixel, 1..32; 0 = 32 (the field was reserved0: zeroed callers keep the default).  The
+                                     K lowest by (E, index), padded with |0..0> when fewer are valid; H is K x K.
+                                     qd_create returns QD_ERR_ARG outside 0..32                                         */
     double delta_max;             /* simulator.delta_max                           */
     double gate_curve_exponent;   /* reward.gate_curve_exponent                    */
     double plunger_radius;        /* reward.plunger_radius        (sparse)         */
@@ -159,18 +162,20 @@ int qd_step(qd_handle* h, const float* actions_dev, const float* values_dev,
  *   raw_host   [B][C][P] float64 unnormalised sensor signal of the last observe
  *   plohi_host [B][2]    the 0.5 / 99.5 percentiles used
  *   occ_host   [B][C][P][N] float64 expectation occupations   (QD_FLAG_VALIDATE)
- *   states_host [B][C][P][32][N] int32 kept charge states      (QD_FLAG_VALIDATE) */
+ *   states_host [B][C][P][32][N] int32 kept charge states      (QD_FLAG_VALIDATE): slots 0..K-1 the K kept states in
+ *                                  the reference order, |0..0> padding included; slots K..31 are -1 */
 int qd_get_state(qd_handle* h, double* state_host, int32_t* steps_host);
 int qd_set_state(qd_handle* h, const double* state_host, const int32_t* steps_host);
 int qd_get_raw(qd_handle* h, double* raw_host, double* plohi_host);
 int qd_get_occupations(qd_handle* h, double* occ_host);
 int qd_get_candidates(qd_handle* h, int32_t* states_host);
-/* eig_host [B][C][P][2] float64 (QD_FLAG_VALIDATE): per pixel the ground energy of the 32-state
- * Hamiltonian (what jnp.linalg.eigh returns first, ground_state.py:150) and the relative residual
+/* eig_host [B][C][P][2] float64 (QD_FLAG_VALIDATE): per pixel the ground energy of the K-state
+ * Hamiltonian (K = num_charge_states) (what jnp.linalg.eigh returns first, ground_state.py:150) and the relative residual
  * ||H x - lambda x||_2 / ||H||_inf of the eigenpair the occupations were formed from. */
 int qd_get_eigen(qd_handle* h, double* eig_host);
 /* Counters of the tile-shared candidate search since qd_create (QD_FLAG_VALIDATE): tiles searched, tiles handed
- * whole to the per-pixel search, single pixels redone, sum of superset sizes, pixels redone for < 32 valid states;
+ * whole to the per-pixel search, single pixels redone, sum of superset sizes, pixels redone for < KC valid states
+ * (KC = 8, 16 or 32: the smallest of them >= K);
  * [8 + r]: tiles handed over by reason r (1 ranges, 2 seeds, 3 frontier overflow, 4 too few leaves, 5 superset size). */
 int qd_get_search_stats(qd_handle* h, uint64_t* out16);
 /* Counters of the ground-state kernel's eigen-solver phase since qd_create (QD_FLAG_VALIDATE): tasks (hop components of

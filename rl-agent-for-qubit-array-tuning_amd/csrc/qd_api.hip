@@ -35,6 +35,7 @@ struct qd_handle {
     unsigned long long* tel; int tel_words;
     unsigned long long* tstats;             // tile-search [0..15] and eigen-solver [16..31] counters (validate mode)
     int tile_search;                        // 0: per-pixel search only; 1: tile-shared candidate search + exact redo pass
+    int kept, kc;                           // K = num_charge_states (1..32) and the kept-set size the candidate stage runs (8, 16, 32)
     unsigned char* slabs;                   // scratch of the ground-state kernels: one slab per batch of QD_GS_PPB pixels in flight
     unsigned* gtiles;                       // [QD_GS_NBIN] tiles per size class of the launch in flight, then the tile lists
     int gs_chunk;                           // envs per ground-state launch (<= chunk)
@@ -103,6 +104,15 @@ struct QdEventPair {
         default: return qd_fail(h, QD_ERR_ARG, "n_dot must be in 2..8");          \
     }
 
+// kept-set size of the candidate stage (KK = h->kc)
+#define QD_DISPATCH_KC(KC_, ...)                                                  \
+    switch (KC_) {                                                                \
+        case 8: { constexpr int KK = 8; __VA_ARGS__; } break;                            \
+        case 16: { constexpr int KK = 16; __VA_ARGS__; } break;                          \
+        case 32: { constexpr int KK = 32; __VA_ARGS__; } break;                          \
+        default: return qd_fail(h, QD_ERR_ARG, "kept-set size must be 8, 16 or 32");     \
+    }
+
 extern "C" int qd_param_block_doubles(int n) { return (n < 2 || n > QD_MAXN) ? -1 : qd_layout(n).size; }
 extern "C" int qd_state_block_doubles(int n) { return (n < 2 || n > QD_MAXN) ? -1 : qd_layout(n).s_size; }
 extern "C" int qd_layout_query(int n, int32_t* out) {
@@ -135,12 +145,16 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
     if (cfg->cnn_outputs != 2 && cfg->cnn_outputs != 3) return QD_ERR_ARG;
     if (cfg->gate_curve_type < 0 || cfg->gate_curve_type > 3 || cfg->update_method < 0 || cfg->update_method > 1) return QD_ERR_ARG;
     if (cfg->flags & QD_FLAG_RETIRED_TILE_FUSED) return QD_ERR_ARG;      // the fused tile kernel of round 2 is gone
+    if (cfg->num_charge_states < 0 || cfg->num_charge_states > QD_K) return QD_ERR_ARG;
     qd_handle* h = new (std::nothrow) qd_handle();
     if (!h) return QD_ERR_NOMEM;
     memset(h, 0, sizeof(*h));
     h->cfg = *cfg; h->device = device;
     h->N = cfg->n_dot; h->R = cfg->resolution; h->B = cfg->batch;
     h->C = h->N - 1; h->P = h->R * h->R; h->L = qd_layout(h->N);
+    // K kept states; the candidate stage runs the smallest kept-set size >= K and hands over its first K
+    h->kept = cfg->num_charge_states ? cfg->num_charge_states : QD_K;
+    h->kc = h->kept <= 8 ? 8 : (h->kept <= 16 ? 16 : 32);
     *out = h;
     QD_ON_DEVICE(h);
     const bool val = (cfg->flags & QD_FLAG_VALIDATE) != 0;
@@ -421,7 +435,7 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
         // (small launches: 16 waves per batch instead of 4, see the kernel)
 #define QD_LAUNCH_STRUCTURE(VAL_, WPB_)                                                                                          \
         QD_DISPATCH_N(h->N, qd_k_gs_structure<NN, VAL_, WPB_><<<dim3(batches), dim3(64 * WPB_), 0, s>>>(env_ids, base + off, rec0 + off, g, h->R, \
-                      h->params, h->recs, h->state, h->cfg.noise_flags, h->slabs, h->gtiles, tilelist, h->gs_batches))
+                      h->params, h->recs, h->state, h->cfg.noise_flags, h->slabs, h->gtiles, tilelist, h->gs_batches, h->kept))
         const bool small = batches < (unsigned)h->cus;
         if (h->eig) { if (small) { QD_LAUNCH_STRUCTURE(true, 16); } else { QD_LAUNCH_STRUCTURE(true, 4); } }
         else        { if (small) { QD_LAUNCH_STRUCTURE(false, 16); } else { QD_LAUNCH_STRUCTURE(false, 4); } }
@@ -432,8 +446,10 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
         // A hop component lies in one total-charge sector of the kept states: at most 4 states for 2 dots (16 candidates), 12 for
         // 3 dots; the launches of size classes that cannot occur are skipped.  From 4 dots on the memory solver of the rare
         // 13..32-state blocks (one long latency chain: 0.4 ms for 8 envs, 0.9 ms for 180) and the wide register solvers go on
-        // two side streams, whatever the batch.
-        const int max_bin = h->N == 2 ? qd_gs_bin(4) : (h->N == 3 ? qd_gs_bin(12) : QD_GS_NBIN - 1);
+        // two side streams, whatever the batch.  Nor can a component hold more than the K kept states (K = 1: no task at all).
+        int max_bin = h->N == 2 ? qd_gs_bin(4) : (h->N == 3 ? qd_gs_bin(12) : QD_GS_NBIN - 1);
+        if (h->kept < 2) max_bin = -1;
+        else if (qd_gs_bin(h->kept) < max_bin) max_bin = qd_gs_bin(h->kept);
         const bool forked = max_bin >= 9;            // (8-dot, 4 envs: 1 760 -> 2 520 env-steps/s, 8 envs 3 390 -> 3 590; 2 and 3 dots have no memory-solver launch to hide)
         hipStream_t s9 = forked ? h->side : s, s48 = forked ? h->side2 : s;
         if (forked) {
@@ -449,7 +465,9 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
         if (max_bin >= 5) QD_HIP(qd_launch_solve<5>(h, s48));
         if (max_bin >= 4) QD_HIP(qd_launch_solve<4>(h, s48));
         if (forked) QD_HIP(hipEventRecord(h->ev_join2, h->side2));
-        QD_HIP(qd_launch_solve<0>(h, s)); QD_HIP(qd_launch_solve<1>(h, s)); QD_HIP(qd_launch_solve<2>(h, s));
+        if (max_bin >= 0) QD_HIP(qd_launch_solve<0>(h, s));
+        if (max_bin >= 1) QD_HIP(qd_launch_solve<1>(h, s));
+        if (max_bin >= 2) QD_HIP(qd_launch_solve<2>(h, s));
         if (max_bin >= 3) QD_HIP(qd_launch_solve<3>(h, s));
         if (forked) {
             QD_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
@@ -458,11 +476,11 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
         }
         if (stages & 4) {
         if (h->eig) {
-            QD_DISPATCH_N(h->N, qd_k_gs_select<NN, true><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids, base + off, rec0 + off, g, h->R,
-                          h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, h->eig, h->slabs));
+            QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc, qd_k_gs_select<NN, true, KK><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids,
+                          base + off, rec0 + off, g, h->R, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, h->eig, h->slabs)));
         } else {
-            QD_DISPATCH_N(h->N, qd_k_gs_select<NN, false><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids, base + off, rec0 + off, g, h->R,
-                          h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, nullptr, h->slabs));
+            QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc, qd_k_gs_select<NN, false, KK><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids,
+                          base + off, rec0 + off, g, h->R, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, nullptr, h->slabs)));
         }
         QD_HIP(hipGetLastError());
         }
@@ -484,25 +502,26 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
 //   tile_search 1: tile search + exact redo pass, then the ground-state kernels;  0: per-pixel search, then the ground-state kernels.
 static int qd_launch_csd(qd_handle* h, const int32_t* env_ids, int base, int cnt, hipStream_t s, int what /*1 search, 2 ground, 3 both*/,
                          int parts = 0 /*timing hooks only: 1 tile search alone, 2 redo pass alone; 4/8/16 structure / solve / select alone*/) {
-    const size_t shm = (size_t)QD_K * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
-    const int sorted = (h->cfg.flags & QD_FLAG_VALIDATE) ? 1 : 0;
+    const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
+    // validate mode keeps the reference order; K < KC needs it too, the ground-state stage takes the first K
+    const int sorted = ((h->cfg.flags & QD_FLAG_VALIDATE) || h->kept != h->kc) ? 1 : 0;
     dim3 g1(qd_cand_blocks(h->R), h->C, cnt);
     const int tiles = ((h->R + 7) / 8) * ((h->R + 7) / 8);
     dim3 gt(tiles, h->C, cnt);
     if (parts & 28) return qd_launch_ground(h, env_ids, base, cnt, s, (parts >> 2) & 7);
     if (what & 1) {
         if (h->tile_search == 1 && parts != 2) {
-            QD_DISPATCH_TILE(h->N, qd_k_tile<NN><<<gt, dim3(64), 0, s>>>(env_ids, base, h->R, h->params, h->state, h->recs,
-                             sorted, h->cfg.noise_flags, h->tstats));
+            QD_DISPATCH_TILE(h->N, QD_DISPATCH_KC(h->kc, qd_k_tile<NN, KK><<<gt, dim3(64), 0, s>>>(env_ids, base, h->R, h->params, h->state,
+                             h->recs, sorted, h->cfg.noise_flags, h->tstats)));
             QD_HIP(hipGetLastError());
         }
         if (parts != 1) {
             if (h->tile_search) {
-                QD_DISPATCH_N(h->N, qd_k_candidates<NN, true><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R, h->params, h->state, h->recs,
-                                                                                                    sorted, h->cfg.noise_flags));
+                QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc, qd_k_candidates<NN, true, KK><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R,
+                                                                                  h->params, h->state, h->recs, sorted, h->cfg.noise_flags)));
             } else {
-                QD_DISPATCH_N(h->N, qd_k_candidates<NN, false><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R, h->params, h->state, h->recs,
-                                                                                                     sorted, h->cfg.noise_flags));
+                QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc, qd_k_candidates<NN, false, KK><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R,
+                                                                                   h->params, h->state, h->recs, sorted, h->cfg.noise_flags)));
             }
             QD_HIP(hipGetLastError());
         }
@@ -649,12 +668,16 @@ extern "C" int qd_get_candidates(qd_handle* h, int32_t* states) {
         const size_t cnt = nrec - r0 < slice ? nrec - r0 : slice;
         hipError_t e_ = hipMemcpy(host, h->recs + r0, cnt * sizeof(QdPixelRec), hipMemcpyDeviceToHost);
         if (e_ != hipSuccess) { free(host); return qd_fail(h, QD_ERR_HIP, "hipMemcpy(recs)", e_); }
-        for (size_t r = 0; r < cnt; ++r)
+        // slots 0..K-1: the kept states (|0..0> padding from nvalid on); slots K..31: -1
+        for (size_t r = 0; r < cnt; ++r) {
+            const int nv = host[r].nvalid < h->kept ? host[r].nvalid : h->kept;
             for (int m = 0; m < QD_K; ++m)
                 for (int i = 0; i < N; ++i) {
-                    const int dig = (host[r].idx[m] >> (2 * (N - 1 - i))) & 3;
-                    states[((r0 + r) * QD_K + m) * N + i] = m < host[r].nvalid ? host[r].fl[i] + DELTA[dig] : 0;
+                    int v = -1;
+                    if (m < h->kept) v = m < nv ? host[r].fl[i] + DELTA[(host[r].idx[m] >> (2 * (N - 1 - i))) & 3] : 0;
+                    states[((r0 + r) * QD_K + m) * N + i] = v;
                 }
+        }
     }
     free(host);
     return QD_OK;

@@ -18,7 +18,7 @@
 #endif
 
 #define QD_MAXN 8            // dots
-#define QD_K 32              // kept charge states   (qarray_config.yaml:129)
+#define QD_K 32              // kept charge states, at most (qarray_config.yaml:129; a handle keeps num_charge_states <= 32)
 #define QD_NPEAK 5           // sensor peaks         (TunnelCoupledChargeSensed.py:77)
 
 // Per-env PARAMETER block (float64, constant during an episode), offsets in doubles.

@@ -1,6 +1,8 @@
-// qd_groundstate.h -- ground state of H = diag(F) + H_t over the 32 kept charge states of a pixel (SURVEY rows
-// a11-a13; reference: hamiltonian_build.py:12-45, 75-137, 460-483 and ground_state.py:149-162, where a dense 32x32
-// eigh is called per pixel and only column 0 is used).
+// qd_groundstate.h -- ground state of H = diag(F) + H_t over the K kept charge states of a pixel (K = num_charge_states,
+// 1..32, default 32; reference: hamiltonian_build.py:12-45, 75-137, 460-483 and
+// ground_state.py:149-162, where a dense K x K eigh is called per pixel and only column 0 is used).  The candidate
+// stage hands over a list of KC >= K states (KC = 8, 16, 32), in (E, idx) order whenever K < KC; the first K slots are
+// the kept states and nothing here reads a slot >= K.
 //
 // Three kernels per launch chunk (qd_kernels.h), the image cut into batches of QD_GS_PPB pixels with one slab of
 // scratch per batch:
@@ -128,11 +130,12 @@ __device__ __forceinline__ int qd_wave_max_int(int v) {
 
 // ---------------------------------------------------------------------------------------------------------------
 // Phase A.  rec: this half's pixel record (states, their free energies from the candidate search, tunnel couplings);
-// ps: the pixel's slot in the batch; live: false for the clamped duplicate beyond the image (nothing is emitted).
+// ps: the pixel's slot in the batch; live: false for the clamped duplicate beyond the image (nothing is emitted);
+// kept: K, the states of the Hamiltonian (lanes m >= K take no part: their link is QD_LINK_NONE).
 // ---------------------------------------------------------------------------------------------------------------
 template <int N, bool VALIDATE>
 __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict__ rec, bool live, int ps, QdWaveLds<N>& W,
-                                                    QdBlockLds& S, const QdSlab& sl) {
+                                                    QdBlockLds& S, const QdSlab& sl, int kept) {
     const int lane = threadIdx.x & 63;
     const int m = lane & 31;
     const int hb = lane & 32;
@@ -146,7 +149,8 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
     if (m >= 16 && m < 16 + N) W.pfl[hh][m - 16] = (short)rec->fl[m - 16];
     __builtin_amdgcn_wave_barrier();
     const double* pvv = W.pv[hh];
-    const int nvalid = rec->nvalid;
+    const bool inK = m < kept;
+    const int nvalid = min(rec->nvalid, kept);
     const bool valid = m < nvalid;
     const unsigned code = valid ? (unsigned)rec->idx[m] : 0u;
     // digit of dot i (base 4, dot 0 most significant) -> nibble N-1-i of ecode: spread the 2-bit digits to 4-bit spacing
@@ -155,10 +159,10 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
     ecode = (ecode | (ecode << 4)) & 0x0F0F0F0Fu;
     ecode = (ecode | (ecode << 2)) & 0x33333333u;
     // F_m: the candidate search already evaluated the canonical energy of every kept state, and of the |0..0> padding
-    // when fewer than 32 candidates are valid (N <= 3).  The diagonal enters RELATIVE to the pixel's lowest free energy:
+    // when fewer than K candidates are valid.  The diagonal enters RELATIVE to the pixel's lowest free energy:
     // H - c I has the same eigenvectors, and the common offset (|F| ~ 1e3..1e5 far from the ground truth, against
     // spreads of O(1)) would cost ~eps |F| in every subtraction.
-    const double Fabs = rec->E[m];
+    const double Fabs = inK ? rec->E[m] : INFINITY;                // (a state beyond K: no part in H, never active)
     const double fshift = qd_half_min(Fabs);
     const double F = Fabs - fshift;
 
@@ -194,7 +198,7 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
             nbrmask |= back << qj;
         }
     }
-    // states beyond the valid count (|0..0> padding) neither hop nor are hopped to
+    // states beyond the valid count (|0..0> padding, and everything from slot K on) neither hop nor are hopped to
     nbrmask = (valid && live) ? (nbrmask & (nvalid >= 32 ? 0xFFFFFFFFu : ((1u << nvalid) - 1u))) : 0u;
 #if defined(QD_ABLATE) && QD_ABLATE == 4
     nbrmask = 0;                                          // diagnostic: no hopping at all
@@ -291,7 +295,7 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
         sl.link[ps * 32 + m] = solve ? gi : (active ? QD_LINK_SINGLE : QD_LINK_NONE);
         sl.rank[ps * 32 + m] = (unsigned char)r;
         if (VALIDATE) {
-            const double hn = -qd_half_min(-(fabs(Fabs) + radius));       // ||H||_inf over the 32 states (unshifted)
+            const double hn = -qd_half_min(inK ? -(fabs(Fabs) + radius) : INFINITY);   // ||H||_inf over the K states (unshifted)
             if (m == 0) { sl.aux[ps] = hn; sl.aux[QD_GS_PPB + ps] = fshift; }
         }
     }
@@ -358,12 +362,13 @@ __device__ __forceinline__ int qd_eig_task_mem(double* rec, double& lam) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Phase C: one pixel per lane.  Returns the occupations, the ground energy (absolute) and, with VALIDATE, the
+// Phase C: one pixel per lane, over the first KC slots (the structure phase linked the slots K..KC-1 to nothing).
+// Returns the occupations, the ground energy (absolute) and, with VALIDATE, the
 // relative residual ||H x - lam x||_2 / ||H||_inf of the winning component's eigenpair.  Written as three rounds of
 // INDEPENDENT loads (links and energies; eigenvalues; the winner's vector) -- a lane's chain of 64 dependent loads was
 // what the first version of this phase spent its time on.
 // ---------------------------------------------------------------------------------------------------------------
-template <int N, bool VALIDATE>
+template <int N, bool VALIDATE, int KC>
 __device__ __forceinline__ void qd_ground_select(const QdPixelRec* __restrict__ rec, int ps, const QdSlab& sl,
                                                  double* occ, double& lam_out, double& resid_out) {
     const unsigned* __restrict__ link = sl.link + ps * 32;
@@ -371,32 +376,32 @@ __device__ __forceinline__ void qd_ground_select(const QdPixelRec* __restrict__ 
     const double* __restrict__ pool = sl.pool;
     const double* __restrict__ lamd = sl.lam;
     const int nvalid = rec->nvalid;
-    unsigned lk[QD_K];
-    double lam[QD_K];
+    unsigned lk[KC];
+    double lam[KC];
     {
         const uint4* l4 = reinterpret_cast<const uint4*>(link);
 #pragma unroll
-        for (int q = 0; q < QD_K / 4; ++q) { const uint4 v = l4[q]; lk[4 * q] = v.x; lk[4 * q + 1] = v.y; lk[4 * q + 2] = v.z; lk[4 * q + 3] = v.w; }
+        for (int q = 0; q < KC / 4; ++q) { const uint4 v = l4[q]; lk[4 * q] = v.x; lk[4 * q + 1] = v.y; lk[4 * q + 2] = v.z; lk[4 * q + 3] = v.w; }
     }
     // eigenvalues are relative to the pixel's lowest free energy; an isolated state that survived the Gershgorin test
     // is a state of exactly that energy (its bound F - 0 must not exceed min F): lambda = 0
 #pragma unroll
-    for (int m = 0; m < QD_K; ++m) {
+    for (int m = 0; m < KC; ++m) {
         const bool task = lk[m] < QD_LINK_SINGLE;
         const double lt = lamd[task ? lk[m] : 0u];         // (always a valid address; the value is used for tasks only)
         lam[m] = task ? lt : (lk[m] == QD_LINK_SINGLE ? 0.0 : INFINITY);
     }
     // the lowest component; tie between components (exactly equal energies): the state with the lowest candidate
     // index wins -- the reference order puts it first -- independent of the buffer order
-    unsigned idx2[QD_K / 2];
+    unsigned idx2[KC / 2];
     {
         const uint4* i4 = reinterpret_cast<const uint4*>(rec->idx);
 #pragma unroll
-        for (int q = 0; q < QD_K / 8; ++q) { const uint4 v = i4[q]; idx2[4 * q] = v.x; idx2[4 * q + 1] = v.y; idx2[4 * q + 2] = v.z; idx2[4 * q + 3] = v.w; }
+        for (int q = 0; q < KC / 8; ++q) { const uint4 v = i4[q]; idx2[4 * q] = v.x; idx2[4 * q + 1] = v.y; idx2[4 * q + 2] = v.z; idx2[4 * q + 3] = v.w; }
     }
     double best = INFINITY; unsigned bestkey = 0xFFFFFFFFu, wl = QD_LINK_NONE; int bm = 0;
 #pragma unroll
-    for (int m = 0; m < QD_K; ++m) {
+    for (int m = 0; m < KC; ++m) {
         const unsigned code = (idx2[m >> 1] >> (16 * (m & 1))) & 0xFFFFu;
         const unsigned key = (m < nvalid) ? code : 0xFFFFFFFEu;
         const bool better = (lam[m] < best) | ((lam[m] == best) & (key < bestkey));
@@ -405,15 +410,19 @@ __device__ __forceinline__ void qd_ground_select(const QdPixelRec* __restrict__ 
     const bool wtask = wl < QD_LINK_SINGLE;
     const unsigned woff = wtask ? sl.lists[wl] : 0u;          // the winner's record
     // the winner's vector: one (predicated) load per member state
-    unsigned rk8[QD_K / 4];
+    unsigned rk8[KC / 4];
     {
-        const uint4* r4 = reinterpret_cast<const uint4*>(rank);
+        if constexpr (KC >= 16) {
+            const uint4* r4 = reinterpret_cast<const uint4*>(rank);
 #pragma unroll
-        for (int q = 0; q < QD_K / 16; ++q) { const uint4 v = r4[q]; rk8[4 * q] = v.x; rk8[4 * q + 1] = v.y; rk8[4 * q + 2] = v.z; rk8[4 * q + 3] = v.w; }
+            for (int q = 0; q < KC / 16; ++q) { const uint4 v = r4[q]; rk8[4 * q] = v.x; rk8[4 * q + 1] = v.y; rk8[4 * q + 2] = v.z; rk8[4 * q + 3] = v.w; }
+        } else {
+            const uint2 v = *reinterpret_cast<const uint2*>(rank); rk8[0] = v.x; rk8[1] = v.y;
+        }
     }
-    double xs[QD_K];
+    double xs[KC];
 #pragma unroll
-    for (int m = 0; m < QD_K; ++m) {
+    for (int m = 0; m < KC; ++m) {
         const bool member = wtask ? (lk[m] == wl) : (m == bm);
         const unsigned rk = (rk8[m >> 2] >> (8 * (m & 3))) & 0xFFu;
         double x = 0.0;
@@ -424,7 +433,7 @@ __device__ __forceinline__ void qd_ground_select(const QdPixelRec* __restrict__ 
 #pragma unroll
     for (int i = 0; i < N; ++i) { occ[i] = 0.0; fl[i] = rec->fl[i]; }
 #pragma unroll
-    for (int m = 0; m < QD_K; ++m) {
+    for (int m = 0; m < KC; ++m) {
         const unsigned code = (idx2[m >> 1] >> (16 * (m & 1))) & 0xFFFFu;
         const double p = (m < nvalid) ? xs[m] * xs[m] : 0.0;          // (the padding lanes are |0..0>)
 #pragma unroll

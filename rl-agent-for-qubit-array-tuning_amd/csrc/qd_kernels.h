@@ -170,8 +170,10 @@ __global__ void qd_k_telegraph(const int* __restrict__ env_ids, int n_env, int C
 #define QD_CAND_WAVES 2         // <= 256 VGPRs: 2 waves per SIMD, which is also what the 20 KB of LDS per wave allows
 #endif
 
-// REDO: second pass behind the tile search (only the pixels it flagged; their front end comes with the record)
-template <int N, bool REDO>
+// REDO: second pass behind the tile search (only the pixels it flagged; their front end comes with the record).
+// KC: size of the kept set (8, 16, 32; the record's slots >= KC are not written).  A handle with K < KC states asks for
+// sort_output and the ground-state stage takes the first K.
+template <int N, bool REDO, int KC>
 __global__ void __launch_bounds__(QD_CAND_BLOCK, QD_CAND_WAVES)
 qd_k_candidates(const int* __restrict__ env_ids, int env_base, int R, const double* __restrict__ params,
                 const double* __restrict__ state, QdPixelRec* __restrict__ recs, int sort_output, int noise_flags) {
@@ -197,8 +199,8 @@ qd_k_candidates(const int* __restrict__ env_ids, int env_base, int R, const doub
     // lets 4 blocks share a CU (measured: 9.4 -> 4.3 ms per 76-env launch together with QD_CAND_WAVES=2)
     const double* spar = params + (size_t)e * L.size;
     const double* sst = state + (size_t)e * L.s_size;
-    double* se = (double*)smem_raw;                           // [32][BLOCK]
-    uint16_t* sid = (uint16_t*)(se + QD_K * QD_CAND_BLOCK);   // [32][BLOCK]
+    double* se = (double*)smem_raw;                           // [KC][BLOCK]
+    uint16_t* sid = (uint16_t*)(se + KC * QD_CAND_BLOCK);     // [KC][BLOCK]
     if (!inside) return;
     if (qd_radial_replaced(spar, sst, L, ch, noise_flags)) return;   // image will be pure noise: nothing to solve
     QdPixelRec* rec = recs + ((size_t)slot * (N - 1) + ch) * P + p;
@@ -223,14 +225,14 @@ qd_k_candidates(const int* __restrict__ env_ids, int env_base, int R, const doub
         qd_pixel_continuous<N>(spar, v_ext, vd, ncont, &isa);
     }
     int32_t fl[N];
-    const int nv = qd_candidates<N>(spar, vd, ncont, se + threadIdx.x, QD_CAND_BLOCK,
-                                    sid + threadIdx.x, QD_CAND_BLOCK, fl, sort_output != 0);
+    const int nv = qd_candidates<N, KC>(spar, vd, ncont, se + threadIdx.x, QD_CAND_BLOCK,
+                                        sid + threadIdx.x, QD_CAND_BLOCK, fl, sort_output != 0);
 #pragma unroll
-    for (int m = 0; m < QD_K; ++m) rec->idx[m] = m < nv ? sid[m * QD_CAND_BLOCK + threadIdx.x] : 0;
-    // fewer than 32 valid candidates (N <= 3): the list is padded with |0..0> states (a9 quirk), whose
+    for (int m = 0; m < KC; ++m) rec->idx[m] = m < nv ? sid[m * QD_CAND_BLOCK + threadIdx.x] : 0;
+    // fewer than KC valid candidates (N <= 3): the list is padded with |0..0> states (a9 quirk), whose
     // free energy the ground-state kernel needs too
     double F0 = 0.0;
-    if (nv < QD_K) {
+    if (nv < KC) {
         double dd[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) dd[i] = 0.0 - vd[i];
@@ -244,7 +246,7 @@ qd_k_candidates(const int* __restrict__ env_ids, int env_base, int R, const doub
         }
     }
 #pragma unroll
-    for (int m = 0; m < QD_K; ++m) rec->E[m] = (m < nv ? se[m * QD_CAND_BLOCK + threadIdx.x] : F0) * isa;
+    for (int m = 0; m < KC; ++m) rec->E[m] = (m < nv ? se[m * QD_CAND_BLOCK + threadIdx.x] : F0) * isa;
 #pragma unroll
     for (int i = 0; i < N; ++i) rec->fl[i] = fl[i];
     rec->nvalid = nv;
@@ -253,7 +255,7 @@ qd_k_candidates(const int* __restrict__ env_ids, int env_base, int R, const doub
 // ---------------------------------------------------------------------------
 // a11-a13 + a15 in three kernels (qd_groundstate.h).  The images of a launch chunk are cut into batches of QD_GS_PPB
 // pixels of one (env, channel); batch b owns slab b.
-//   qd_k_gs_structure  grid = batches, 256 threads: hop structure, one pixel per half-wave -> dense tasks in the slab,
+//   qd_k_gs_structure  grid = batches, 256 threads: hop structure over the first K states, one pixel per half-wave -> dense tasks in the slab,
 //                      the batch's 64-task tiles appended to the launch-wide tile list of each size class
 //   qd_k_gs_solve<K>   one launch per size class K (own register budget / occupancy), persistent waves striding over
 //                      the class's tile list: one task per lane
@@ -279,7 +281,8 @@ template <int N, bool VALIDATE, int WPB>
 __global__ void __launch_bounds__(64 * WPB, WPB == 4 ? QD_GS_WAVES : 4)
 qd_k_gs_structure(const int* __restrict__ env_ids, int env_base, int rec_slot0, QdGsGeom g, int R, const double* __restrict__ params,
                   const QdPixelRec* __restrict__ recs, const double* __restrict__ state, int noise_flags,
-                  unsigned char* __restrict__ slabs, unsigned* __restrict__ gtiles, unsigned* __restrict__ tilelist, size_t batches_cap) {
+                  unsigned char* __restrict__ slabs, unsigned* __restrict__ gtiles, unsigned* __restrict__ tilelist, size_t batches_cap,
+                  int kept) {
     const QdLayout L = qd_layout(N);
     __shared__ QdWaveLds<N> sW[WPB];
     __shared__ QdBlockLds sB;
@@ -306,7 +309,7 @@ qd_k_gs_structure(const int* __restrict__ env_ids, int env_base, int rec_slot0, 
         const int p = p0 + ps;
         // both halves of a wave run in lock step: clamp instead of exiting
         const int pc = p < g.P ? p : g.P - 1;
-        qd_ground_structure<N, VALIDATE>(rbase + pc, p < g.P, ps, W, sB, sl);
+        qd_ground_structure<N, VALIDATE>(rbase + pc, p < g.P, ps, W, sB, sl, kept);
     }
     __syncthreads();
     if (threadIdx.x < QD_GS_NBIN) {
@@ -385,7 +388,7 @@ qd_k_gs_solve(unsigned char* __restrict__ slabs, const unsigned* __restrict__ gt
 #ifndef QD_SEL_WAVES
 #define QD_SEL_WAVES 3
 #endif
-template <int N, bool VALIDATE>
+template <int N, bool VALIDATE, int KC>
 __global__ void __launch_bounds__(QD_GS_BLOCK, QD_SEL_WAVES)
 qd_k_gs_select(const int* __restrict__ env_ids, int env_base, int rec_slot0, QdGsGeom g, int R, const double* __restrict__ params,
                const QdPixelRec* __restrict__ recs, double* __restrict__ zraw, double* __restrict__ occ_out,
@@ -404,7 +407,7 @@ qd_k_gs_select(const int* __restrict__ env_ids, int env_base, int rec_slot0, QdG
     if (p >= g.P) return;
     const QdPixelRec* rec = recs + ((size_t)(rec_slot0 + slot) * g.C + ch) * g.P + p;
     double occ[N], lam, resid;
-    qd_ground_select<N, VALIDATE>(rec, ps, sl, occ, lam, resid);
+    qd_ground_select<N, VALIDATE, KC>(rec, ps, sl, occ, lam, resid);
     const size_t gp = ((size_t)e * g.C + ch) * g.P + p;
     // hand the sensor stage (qd_k_sensor) the pixel's constant c0 = 2 b + a (2 (Ns - v''_s) + 1):
     // F_{k+1} - F_k = c0 + 2 a (k + eta)   (closed form of the reference's energy differences),

@@ -170,7 +170,7 @@ QD_HD double qd_peak_width(const double* par, const double* st, const QdLayout& 
 // ---------------------------------------------------------------------------
 // a9  exact k-best candidate search.
 // Minimise E(c) = (c-v')^T A (c-v') over c = floor(n_cont) + delta,
-// delta in {-1,0,1,2}^N, c >= 0, keeping the 32 smallest by (E, index) where
+// delta in {-1,0,1,2}^N, c >= 0, keeping the KC smallest by (E, index) where
 // index = sum_i (delta_i+1) << 2(N-1-i).  Equivalent to the reference's scan of
 // all 4^N candidates with stable sorts (proved against the oracle in tests), but
 // done as a depth-first branch and bound:
@@ -187,8 +187,12 @@ QD_HD double qd_peak_width(const double* par, const double* st, const QdLayout& 
 // list is bit-identical to the brute-force scan.
 // The top-k buffer is caller-provided strided storage (LDS on the GPU).
 // ---------------------------------------------------------------------------
-template <int N>
+// KC (8, 16 or 32) is the size of the kept set: the handle runs the smallest KC >= num_charge_states, and the
+// first K entries of the (E, idx)-sorted KC list are the K lowest.
+template <int N, int KC = QD_K>
 struct QdSearch {
+    static_assert(KC == 8 || KC == 16 || KC == 32, "kept sets come in groups of 8");
+    static constexpr int NG = KC / 8;
     const double* A; int lda;        // cdd_inv (row-major, lda = G)
     const double* U;                 // N*N row-major upper factor
     const double* uinv;              // 1/U[i][i]
@@ -199,15 +203,15 @@ struct QdSearch {
     double* e; int es;               // energies, stride
     uint16_t* id; int is;            // indices, stride
     int count;
-    double gE[4]; unsigned gI[4]; int gS[4];    // per-group maxima of the kept buffer
-    double maxE; unsigned maxI; int maxS, maxG;  // overall maximum (the 32nd best)
+    double gE[NG]; unsigned gI[NG]; int gS[NG];  // per-group maxima of the kept buffer
+    double maxE; unsigned maxI; int maxS, maxG;  // overall maximum (the KC-th best)
     double lim;                      // prune when (partial + tail) > lim   (relative to Em)
     unsigned idx;
     unsigned long long nodes, leaves, inserts, shifts;   // statistics (host harness only)
 };
 
 // The kept set lives in caller-provided strided storage (LDS on the GPU) as an UNSORTED buffer
-// split into 4 groups of 8 slots; the lexicographic (E, idx) maximum of each group is cached in
+// split into KC / 8 groups of 8 slots; the lexicographic (E, idx) maximum of each group is cached in
 // registers.  Replacing the overall maximum costs one write + an 8-slot rescan (independent
 // reads) instead of a chain of dependent compare-and-shift steps.  qd_search_sort() orders the
 // final list when the caller wants the reference order.
@@ -217,8 +221,8 @@ QD_HD bool qd_lex_less(double ea, unsigned ia, double eb, unsigned ib) {
     return (bool)((int)(ea < eb) | ((int)(ea == eb) & (int)(ia < ib)));
 }
 
-template <int N>
-QD_HD void qd_search_rescan_group(QdSearch<N>& S, int g) {
+template <int N, int KC>
+QD_HD void qd_search_rescan_group(QdSearch<N, KC>& S, int g) {
     double me = -INFINITY; unsigned mi = 0; int ms = g * 8;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
@@ -227,32 +231,32 @@ QD_HD void qd_search_rescan_group(QdSearch<N>& S, int g) {
         if (t == 0 || qd_lex_less<N>(me, mi, e, i)) { me = e; mi = i; ms = sl; }
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) if (j == g) { S.gE[j] = me; S.gI[j] = mi; S.gS[j] = ms; }
+    for (int j = 0; j < QdSearch<N, KC>::NG; ++j) if (j == g) { S.gE[j] = me; S.gI[j] = mi; S.gS[j] = ms; }
 }
 
-template <int N>
-QD_HD void qd_search_set_bound(QdSearch<N>& S) {
-    // overall maximum = lexicographic max of the 4 group maxima
+template <int N, int KC>
+QD_HD void qd_search_set_bound(QdSearch<N, KC>& S) {
+    // overall maximum = lexicographic max of the group maxima
     int g = 0; double bound = S.gE[0]; unsigned bi = S.gI[0]; int bs = S.gS[0];
 #pragma unroll
-    for (int j = 1; j < 4; ++j)
+    for (int j = 1; j < QdSearch<N, KC>::NG; ++j)
         if (qd_lex_less<N>(bound, bi, S.gE[j], S.gI[j])) { bound = S.gE[j]; bi = S.gI[j]; bs = S.gS[j]; g = j; }
     S.maxE = bound; S.maxI = bi; S.maxS = bs; S.maxG = g;
     S.lim = (bound - S.Em) + ((fabs(bound) + fabs(S.Em)) * 1e-11 + 1e-300);
 }
 
-template <int N>
-QD_HD void qd_search_insert(QdSearch<N>& S, double E, unsigned idx) {
+template <int N, int KC>
+QD_HD void qd_search_insert(QdSearch<N, KC>& S, double E, unsigned idx) {
     if (!(E < INFINITY)) return;                          // inf / NaN: treated as invalid
 #ifndef __HIP_DEVICE_COMPILE__
     S.inserts++;
 #endif
-    if (S.count < QD_K) {
+    if (S.count < KC) {
         S.e[S.count * S.es] = E; S.id[S.count * S.is] = (uint16_t)idx;
         S.count++;
-        if (S.count == QD_K) {
+        if (S.count == KC) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) qd_search_rescan_group(S, g);
+            for (int g = 0; g < QdSearch<N, KC>::NG; ++g) qd_search_rescan_group(S, g);
             qd_search_set_bound(S);
         }
         return;
@@ -264,8 +268,8 @@ QD_HD void qd_search_insert(QdSearch<N>& S, double E, unsigned idx) {
 }
 
 // in-place insertion sort of the kept entries by (E, idx)
-template <int N>
-QD_HD void qd_search_sort(QdSearch<N>& S) {
+template <int N, int KC>
+QD_HD void qd_search_sort(QdSearch<N, KC>& S) {
     for (int i = 1; i < S.count; ++i) {
         const double E = S.e[i * S.es]; const unsigned idx = S.id[i * S.is];
         int pos = i;
@@ -286,9 +290,9 @@ struct QdSplit {
     static constexpr int A = (B - 3 >= 0) ? B - 3 : -1;
 };
 
-template <int N, int L>
+template <int N, int L, int KC>
 struct QdLevel {
-    static QD_HD void run(QdSearch<N>& S, double partial) {
+    static QD_HD void run(QdSearch<N, KC>& S, double partial) {
 #ifndef __HIP_DEVICE_COMPILE__
         S.nodes++;
 #endif
@@ -341,7 +345,7 @@ struct QdLevel {
                     S.pre2[i] = acc;
                 }
             }
-            QdLevel<N, L + 1>::run(S, pn);
+            QdLevel<N, L + 1, KC>::run(S, pn);
             const bool can_lo = lo >= kmin, can_hi = hi <= 3;
             if (!((int)can_lo | (int)can_hi)) return;
             const bool take_lo = (bool)((int)can_lo & ((int)!can_hi | (int)((kstar - (double)lo) <= ((double)hi - kstar))));
@@ -352,9 +356,9 @@ struct QdLevel {
     }
 };
 
-template <int N>
-struct QdLevel<N, N> {
-    static QD_HD void run(QdSearch<N>& S, double) {
+template <int N, int KC>
+struct QdLevel<N, N, KC> {
+    static QD_HD void run(QdSearch<N, KC>& S, double) {
 #ifndef __HIP_DEVICE_COMPILE__
         S.leaves++;
 #endif
@@ -381,14 +385,14 @@ struct QdLevel<N, N> {
     }
 };
 
-// Returns the number of valid candidates found (<= 32).  With sort_output the list is in the
+// Returns the number of valid candidates found (<= KC).  With sort_output the list is in the
 // reference order (increasing (E, idx)); otherwise it is the same SET in search order.
-template <int N>
+template <int N, int KC = QD_K>
 QD_HD int qd_candidates(const double* par, const double* vpp, const double* ncont,
                         double* e, int es, uint16_t* id, int is, int32_t* fl_out, bool sort_output,
                         unsigned long long* stats = nullptr) {
     const QdLayout L = qd_layout(N);
-    QdSearch<N> S;
+    QdSearch<N, KC> S;
     S.A = par + L.cdd_inv; S.lda = N + 1; S.U = par + L.ufac; S.uinv = par + L.uinv;
     bool shifted = false;
 #pragma unroll
@@ -425,7 +429,7 @@ QD_HD int qd_candidates(const double* par, const double* vpp, const double* ncon
     S.count = 0; S.lim = INFINITY; S.idx = 0;
     S.nodes = S.leaves = S.inserts = S.shifts = 0;
 #if !(defined(QD_CAND_ABLATE) && QD_CAND_ABLATE == 2)
-    QdLevel<N, 0>::run(S, 0.0);                            // (ablate 2: diagnostic, front end only)
+    QdLevel<N, 0, KC>::run(S, 0.0);                            // (ablate 2: diagnostic, front end only)
 #endif
     if (sort_output) qd_search_sort(S);
 #ifndef __HIP_DEVICE_COMPILE__

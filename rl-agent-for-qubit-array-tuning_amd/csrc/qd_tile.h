@@ -4,17 +4,17 @@
 // pixels of a CSD differ only by a small shift d_p of v' = cgd[:N] @ v_ext, and
 //     E_p(c) - E_p(c0) = [E_ref(c) - E_ref(c0)] - 2 d_p^T A (c - c0),        d_p = v'_p - v'_ref,
 // so with d_p = x dx + y dy (+ a rounding-level residual) the energies of a candidate over the whole tile are a
-// PLANE over (x, y).  A candidate can be among the 32 lowest of SOME pixel of the tile only if its minimum over
-// the tile m(c) does not exceed T = the 32nd smallest of the maxima M(c) taken over candidates valid in every
-// pixel.  The wave therefore searches ONCE per tile:
+// PLANE over (x, y).  A candidate can be among the KC lowest of SOME pixel of the tile only if its minimum over
+// the tile m(c) does not exceed T = the KC-th smallest of the maxima M(c) taken over candidates valid in every
+// pixel (KC = 8, 16 or 32: the kept set of the handle, template parameter).  The wave therefore searches ONCE per tile:
 //   1. per lane (= pixel): sweep voltages, couplings, continuous ground state, floor (as before)
 //   2. seeds: the product set of the cheapest per-dot options around the greedy lattice point, one per lane,
 //      gives an upper bound T'' >= T
 //   3. level-synchronous branch and bound over dots 0..N-1, 64 children at a time, keeps every partial state
 //      whose lower bound of m(c) is <= T''  ->  list S' (typically 50-130 states instead of 64 x ~100 leaves)
 //   4. T by bisection on the count of M(c) <= t, superset S = {m(c) <= T} (typically 40-90 states)
-//   5. per lane: energies of S by two FMAs each, own validity box, top-32 buffer in LDS
-// Every bound carries explicit margins (affine residual, arithmetic); a lane whose 32nd / 33rd energies are closer
+//   5. per lane: energies of S by two FMAs each, own validity box, top-KC buffer in LDS
+// Every bound carries explicit margins (affine residual, arithmetic); a lane whose KC-th / (KC+1)-th energies are closer
 // than the margin, and any tile that overflows a capacity, is flagged (nvalid = -1) and redone by the exact
 // per-pixel search (qd_k_candidates), so the kept SETS are bit-identical to the brute-force scan in every case.
 #pragma once
@@ -44,7 +44,7 @@ struct QdTileLds {
     int optval[QD_MAXN][4];
     union {
         struct { double pn[2][QD_T_FCAP]; uint32_t code[2][QD_T_FCAP]; } f;      // frontier ping-pong
-        struct { double e[QD_K][64]; uint16_t id[QD_K][64]; } k;                   // per-lane kept sets
+        struct { double e[QD_K][64]; uint16_t id[QD_K][64]; } k;                   // per-lane kept sets (first KC rows used)
     } u;
     double sD[QD_T_SCAP], sa[QD_T_SCAP], sb[QD_T_SCAP];
     uint32_t scode[QD_T_SCAP];
@@ -127,11 +127,11 @@ __device__ __forceinline__ void qd_tile_hand_over(QdPixelRec* rec, const double*
 
 // ---------------------------------------------------------------------------------------------
 // grid = (tiles, C, n_env), block = 64 (one wavefront = one 8x8 pixel tile)
-// stats (optional, 16 counters): tiles, tiles redone whole, lanes redone, sum of |S|, lanes redone for < 32 valid
+// stats (optional, 16 counters): tiles, tiles redone whole, lanes redone, sum of |S|, lanes redone for < KC valid
 // states in S; [8 + reason]: tiles redone by reason (1 ranges, 2 seeds, 3 frontier overflow, 4 too few leaves, 5 |S|)
 // ---------------------------------------------------------------------------------------------
-// Writes one QdPixelRec per pixel for the ground-state kernels (qd_k_gs_*).
-template <int N>
+// Writes one QdPixelRec per pixel for the ground-state kernels (qd_k_gs_*): the KC lowest states (slots >= KC untouched).
+template <int N, int KC>
 __global__ void __launch_bounds__(64)
 qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __restrict__ params,
           const double* __restrict__ state, QdPixelRec* __restrict__ recs, int sort_output, int noise_flags,
@@ -237,7 +237,9 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
         allvalid_count *= (unsigned long long)(ahi_[i] >= alo_[i] ? ahi_[i] - alo_[i] + 1 : 0);
         if (lane == 0) { T.lo[i] = lo_[i]; T.nd[i] = nd_[i]; }
     }
-    if (allvalid_count < (unsigned long long)QD_K) { fail = true; why = 1; }
+    static_assert(KC == 8 || KC == 16 || KC == 32, "kept sets come in groups of 8");
+    constexpr int NG = KC / 8;
+    if (allvalid_count < (unsigned long long)KC) { fail = true; why = 1; }
     __builtin_amdgcn_wave_barrier();
 
 #if defined(QD_TILE_STOP) && QD_TILE_STOP == 2
@@ -360,15 +362,15 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
         // of the CANONICAL absolute energies that define the reference order (~N^2 ulps of |E|)
         margin = 2.0 * rho * (double)maxdc + 1e-11 * escale + 1e-12 * qd_wmax_d(fabs(Ecg));
         const double Mh = (lane < prod) ? (pn - pn_ref) + qd_plane_max(pa, pb, x0, x1, y0, y1) + margin : INFINITY;
-        if (prod < QD_K) { fail = true; why = 2; }
+        if (prod < KC) { fail = true; why = 2; }
         else {
-            // 32nd smallest of the seeds' maxima
+            // KC-th smallest of the seeds' maxima
             int below = 0;
             for (int j = 0; j < 64; ++j) {
                 const double o = qd_rl(Mh, j);
                 below += (o < Mh || (o == Mh && j < lane)) ? 1 : 0;
             }
-            const unsigned long long sel = __ballot(below == QD_K - 1 && lane < prod);
+            const unsigned long long sel = __ballot(below == KC - 1 && lane < prod);
             Tpp = sel ? qd_rl(Mh, __builtin_ctzll(sel)) : INFINITY;
             if (!(Tpp < INFINITY)) { fail = true; why = 2; }
         }
@@ -438,7 +440,7 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
 #endif
     // ---- 5. T (bisection on the count of maxima) and the superset S --------------------------------
     int nS = 0, nSfront = 0;
-    if (!fail && nfront < QD_K) { fail = true; why = 4; }
+    if (!fail && nfront < KC) { fail = true; why = 4; }
     if (!fail) {
         constexpr int CH = QD_T_FCAP / 64;
         double Mh[CH];
@@ -466,13 +468,13 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
                 mlo = fmin(mlo, Mh[c]);
             }
         }
-        double tlo = qd_wmin_d(mlo), thi = Tpp;                             // count(M <= thi) >= 32 holds by construction
+        double tlo = qd_wmin_d(mlo), thi = Tpp;                             // count(M <= thi) >= KC holds by construction
         for (int it = 0; it < 14; ++it) {
             const double mid = 0.5 * (tlo + thi);
             int cnt = 0;
 #pragma unroll
             for (int c = 0; c < CH; ++c) cnt += __builtin_popcountll(__ballot(Mh[c] <= mid));
-            if (cnt >= QD_K) thi = mid; else tlo = mid;
+            if (cnt >= KC) thi = mid; else tlo = mid;
         }
         const double Tt = thi;
         // S = {m <= T}: the states whose maximum is within T (kept in most pixels) fill S from the front, the others
@@ -507,7 +509,7 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
         }
         nS = nfrontS + nbackS;
         nSfront = nfrontS;
-        if (nS > QD_T_SCAP || nS < QD_K) { fail = true; why = 5; }
+        if (nS > QD_T_SCAP || nS < KC) { fail = true; why = 5; }
         __builtin_amdgcn_wave_barrier();
     }
     if (stats && lane == 0) {
@@ -524,14 +526,14 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
     if (inside) rec->E[0] = (double)nS + T.sD[lane];                 // diagnostic build: time split of the kernel (scripts/ab_build.sh)
     return;
 #endif
-    // ---- 6. per lane: energies of S, own validity box, 32 lowest ------------------------------------
+    // ---- 6. per lane: energies of S, own validity box, KC lowest ------------------------------------
     uint32_t blo = 0, bhi = 0;
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         blo |= (uint32_t)(max(fl[i] - 1, 0) - lo_[i]) << (4 * (N - 1 - i));
         bhi |= (uint32_t)(fl[i] + 2 - lo_[i]) << (4 * (N - 1 - i));
     }
-    double gE[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}; int gS[4] = {0, 8, 16, 24};
+    double gE[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}; int gS[4] = {0, 8, 16, 24};     // (first NG groups used)
     double maxE = -INFINITY; int maxS = 0, maxG = 0, count = 0;
     double eout = INFINITY;                                                  // lowest energy NOT kept
     for (int si = 0; si < nS; ++si) {
@@ -541,12 +543,12 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
                            ((((bhi | 0x88888888u) - code) & 0x88888888u) == 0x88888888u);
         const double en = fma(xs, T.sa[s], fma(ys, T.sb[s], T.sD[s]));
         if (!valid) continue;
-        if (count < QD_K) {
+        if (count < KC) {
             T.u.k.e[count][lane] = en; T.u.k.id[count][lane] = (uint16_t)s;
             count++;
-            if (count == QD_K) {
+            if (count == KC) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
+                for (int g = 0; g < NG; ++g) {
                     double me = -INFINITY; int ms = g * 8;
 #pragma unroll
                     for (int t = 0; t < 8; ++t) { const double v = T.u.k.e[g * 8 + t][lane]; if (v > me) { me = v; ms = g * 8 + t; } }
@@ -554,7 +556,7 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
                 }
                 maxE = gE[0]; maxS = gS[0]; maxG = 0;
 #pragma unroll
-                for (int g = 1; g < 4; ++g) if (gE[g] > maxE) { maxE = gE[g]; maxS = gS[g]; maxG = g; }
+                for (int g = 1; g < NG; ++g) if (gE[g] > maxE) { maxE = gE[g]; maxS = gS[g]; maxG = g; }
             }
         } else if (en < maxE) {
             eout = fmin(eout, maxE);                                        // the evicted state
@@ -564,20 +566,20 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
 #pragma unroll
                 for (int t = 0; t < 8; ++t) { const double v = T.u.k.e[maxG * 8 + t][lane]; if (v > me) { me = v; ms = maxG * 8 + t; } }
 #pragma unroll
-                for (int g = 0; g < 4; ++g) if (g == maxG) { gE[g] = me; gS[g] = ms; }
+                for (int g = 0; g < NG; ++g) if (g == maxG) { gE[g] = me; gS[g] = ms; }
             }
             maxE = gE[0]; maxS = gS[0]; maxG = 0;
 #pragma unroll
-            for (int g = 1; g < 4; ++g) if (gE[g] > maxE) { maxE = gE[g]; maxS = gS[g]; maxG = g; }
+            for (int g = 1; g < NG; ++g) if (gE[g] > maxE) { maxE = gE[g]; maxS = gS[g]; maxG = g; }
         } else {
             eout = fmin(eout, en);
         }
     }
     // a lane whose boundary is closer than what the arithmetic can tell apart is redone exactly
     const double amb = 2.0 * margin;
-    const bool redo = (count < QD_K) || !(eout - maxE > amb);
+    const bool redo = (count < KC) || !(eout - maxE > amb);
     if (stats) {
-        const unsigned long long rm = __ballot(redo && inside), rc = __ballot(count < QD_K && inside);
+        const unsigned long long rm = __ballot(redo && inside), rc = __ballot(count < KC && inside);
         if (lane == 0 && rm) { atomicAdd(&stats[2], (unsigned long long)__builtin_popcountll(rm)); atomicAdd(&stats[4], (unsigned long long)__builtin_popcountll(rc)); }
     }
     if (!inside) return;
@@ -595,7 +597,7 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
     for (int i = 0; i < N; ++i) off |= (uint32_t)(lo_[i] - fl[i] + 1 + 4) << (4 * (N - 1 - i));
     if (sort_output) {
         // validate mode: canonical energies, reference order (E, idx)
-        for (int k = 0; k < QD_K; ++k) {
+        for (int k = 0; k < KC; ++k) {
             const uint32_t code = T.scode[T.u.k.id[k][lane]];
             double dd[N];
 #pragma unroll
@@ -611,7 +613,7 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
             }
             T.u.k.e[k][lane] = E;
         }
-        for (int i = 1; i < QD_K; ++i) {                                      // insertion sort by (E, code)
+        for (int i = 1; i < KC; ++i) {                                        // insertion sort by (E, code)
             const double E = T.u.k.e[i][lane]; const uint16_t id = T.u.k.id[i][lane];
             const uint32_t cd = T.scode[id];
             int pos = i;
@@ -625,7 +627,7 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
             T.u.k.e[pos][lane] = E; T.u.k.id[pos][lane] = id;
         }
     }
-    for (int k = 0; k < QD_K; ++k) {
+    for (int k = 0; k < KC; ++k) {
         const uint32_t code = T.scode[T.u.k.id[k][lane]];
         const uint32_t dg = (code + off) - 0x44444444u;                       // nibbles: c - fl + 1 in 0..3 (no carries: each sum < 16)
         // 2-bit digits at 4-bit spacing -> packed base-4 index (dot 0 most significant): three mask-shift steps
@@ -639,7 +641,7 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
     }
 #pragma unroll
     for (int i = 0; i < N; ++i) rec->fl[i] = fl[i];
-    rec->nvalid = QD_K;
+    rec->nvalid = KC;
     }
 }
 

@@ -39,7 +39,7 @@ class QdConfig(ctypes.Structure):
         ("kalman_variance_threshold", ctypes.c_double), ("kalman_process_noise", ctypes.c_double),
         ("rng_seed", ctypes.c_uint64), ("env_id_offset", ctypes.c_int64),
         ("use_deltas", ctypes.c_int32), ("sparse_reward", ctypes.c_int32), ("gate_curve_type", ctypes.c_int32),
-        ("update_method", ctypes.c_int32), ("cnn_outputs", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+        ("update_method", ctypes.c_int32), ("cnn_outputs", ctypes.c_int32), ("num_charge_states", ctypes.c_int32),
         ("delta_max", ctypes.c_double), ("gate_curve_exponent", ctypes.c_double),
         ("plunger_radius", ctypes.c_double), ("outer_plunger_radius", ctypes.c_double),
         ("outer_plunger_reward_max", ctypes.c_double), ("barrier_radius", ctypes.c_double),

@@ -42,6 +42,7 @@ class GenerationConfig:
     resolution: int | None = None
     env_config_path: str | None = None
     qarray_config_path: str | None = None
+    num_charge_states: int | None = None  # None: the qarray config's latched_model.num_charge_states
     noise: bool = True                    # sensor + radial noise as the reference's _get_obs applies them
     extra: dict = field(default_factory=dict)
 
@@ -75,6 +76,7 @@ class SymmetricCapacitanceGenerator:
         self.env = VecQuantumDeviceEnv(B, num_dots=cfg.num_dots, config_path=cfg.env_config_path,
                                        qarray_config_path=cfg.qarray_config_path, resolution=cfg.resolution,
                                        device=device, seed=cfg.seed_base, noise=True if cfg.noise else None,
+                                       num_charge_states=cfg.num_charge_states,
                                        capacitance_model=lambda img: (None, None))
         self.barrier_offset = float(self.env.config["simulator"]["full_barrier_range_width"]["max"]) / 2
         for d in ("images", "cgd_matrices", "ground_truth", "metadata"):

@@ -24,7 +24,7 @@ class QuantumDeviceEnv:
 
     def __init__(self, training=True, config_path="env_config.yaml", num_dots=None, use_barriers=None,
                  capacitance_model_checkpoint=None, capacitance_model=None, backend=None, seed=None,
-                 qarray_config_path=None):
+                 qarray_config_path=None, num_charge_states=None):
         self.config = load_yaml(config_path if config_path != "env_config.yaml" else None, "env_config.yaml")
         sim = self.config["simulator"]
         self.training = training
@@ -66,7 +66,7 @@ class QuantumDeviceEnv:
             from .vec_env import VecQuantumDeviceEnv
             backend = VecQuantumDeviceEnv(1, num_dots=N, config_path=config_path if config_path != "env_config.yaml" else None,
                                           qarray_config_path=qarray_config_path, resolution=R,
-                                          capacitance_model=capacitance_model,
+                                          capacitance_model=capacitance_model, num_charge_states=num_charge_states,
                                           seed=seed)            # None: fresh entropy per env, as the reference's unseeded RNGs
         self._b = backend
         self.current_step = 0

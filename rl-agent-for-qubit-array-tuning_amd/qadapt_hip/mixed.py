@@ -20,7 +20,7 @@ class MixedVecQuantumDeviceEnv:
                  device=None, streams=True, **kw):
         """counts: {n_dots: n_envs} of the WHOLE job; this object owns rank `rank`'s share of every bucket.
         capacitance_model_factory(n_dots) -> callable or None.  Other keywords go to VecQuantumDeviceEnv
-        (e.g. noise=["latch"] for the latched model of config 5)."""
+        (e.g. noise=["latch"] for the latched model of config 5, num_charge_states=16: one K for every bucket)."""
         R = resolution if resolution is not None else 64
         self.assignment = shard.shard_mixed(counts, rank, world, R)
         self.buckets, self.streams = {}, {}

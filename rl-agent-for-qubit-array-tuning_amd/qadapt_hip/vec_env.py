@@ -43,25 +43,61 @@ class SyntheticCapacitanceModel:
         return values.to(images.device), log_vars.to(images.device)
 
 
+def make_qd_config(config, qconfig, num_dots, resolution, batch, *, env_chunk=0, flags=0, noise_flags=0, seed=0,
+                   env_id_offset=0):
+    """The qd_config (include/qdsim.h) of a handle for the env config `config` and the qarray config `qconfig` (both as
+    loaded by load_yaml); builds no handle and needs no GPU.  The kept-state count K comes from
+    `qconfig.simulator.latched_model.num_charge_states` (check_solver_options)."""
+    sim, rew, cm = config["simulator"], config["reward"], config["capacitance_model"]
+    nearest = bool(cm.get("nearest_neighbour"))
+    return _lib.QdConfig(struct_size=ctypes.sizeof(_lib.QdConfig), n_dot=int(num_dots), resolution=int(resolution),
+                         batch=int(batch), max_steps=int(sim["max_steps"]), env_chunk=int(env_chunk), flags=int(flags),
+                         noise_flags=int(noise_flags),
+                         gate_ramp_start=float(rew["gate_ramp_start"]),
+                         gate_quadratic_start=float(rew["gate_quadratic_start"]),
+                         barrier_ramp_start=float(rew["barrier_ramp_start"]),
+                         kalman_prior_mean=0.3, kalman_prior_variance=0.5, kalman_prior_mean_nnn=0.15,
+                         kalman_variance_threshold=float(cm.get("variance_threshold", 0.05)),
+                         kalman_process_noise=float(cm.get("process_noise", 0.0)),
+                         rng_seed=int(seed) & 0xFFFFFFFFFFFFFFFF, env_id_offset=int(env_id_offset),
+                         use_deltas=1 if sim.get("use_deltas") else 0,
+                         sparse_reward=1 if rew.get("sparse_reward") else 0,
+                         gate_curve_type=_lib.QD_CURVES[rew.get("gate_curve_type", "constant")],
+                         update_method=_lib.QD_UPDATE_DIRECT if cm["update_method"] == "direct" else _lib.QD_UPDATE_KALMAN,
+                         cnn_outputs=2 if nearest else 3, num_charge_states=check_solver_options(qconfig),
+                         delta_max=float(sim.get("delta_max", 0.0)),
+                         gate_curve_exponent=float(rew.get("gate_curve_exponent", 2.0)),
+                         plunger_radius=float(rew.get("plunger_radius", 0.0)),
+                         outer_plunger_radius=float(rew.get("outer_plunger_radius", 0.0)),
+                         outer_plunger_reward_max=float(rew.get("outer_plunger_reward_max", 0.0)),
+                         barrier_radius=float(rew.get("barrier_radius", 0.0)))
+
+
 class VecQuantumDeviceEnv:
     def __init__(self, num_envs, num_dots=None, config_path=None, qarray_config_path=None,
                  resolution=None, device=None, seed=None, env_id_offset=0, capacitance_model=None,
                  validate=False, env_chunk=0, reset_kalman_on_reset=False, noise=None,
-                 vary_peak_width=False, peak_width_alpha=0.01, voltage_capacitance_model=None, pixel_search=False):
+                 vary_peak_width=False, peak_width_alpha=0.01, voltage_capacitance_model=None, pixel_search=False,
+                 num_charge_states=None):
         """pixel_search: a9 by the per-pixel search only (A/B switch; the default runs one search per 8x8 tile).
         seed: base seed of the per-env device streams (PCG64(seed + global env id)) and the Philox key of
         the stochastic stages; None draws fresh OS entropy, as the reference's unseeded generators do
         (qarray_base_class.py:773-774, env.py:161).
         vary_peak_width / peak_width_alpha: QarrayBaseClass ctor arguments (qarray_base_class.py:42-43).
         voltage_capacitance_model: overrides `simulator.voltage_capacitance_model.type` of the qarray
-        config (None keeps the file's value; "linear" or "none")."""
+        config (None keeps the file's value; "linear" or "none").
+        num_charge_states: overrides `simulator.latched_model.num_charge_states` of the qarray config (None keeps the
+        file's value): K, the charge states kept per pixel (1..32; the K x K Hamiltonian is solved exactly).  One K per
+        handle."""
         if seed is None:
             seed = int(np.random.SeedSequence().entropy) & 0x7FFFFFFFFFFF      # 47 bits: seed + env id stays exact
         self.seed = int(seed)
         self.env_id_offset = int(env_id_offset)
         self.config = load_yaml(config_path, "env_config.yaml")
         self.qconfig = load_yaml(qarray_config_path, "qarray_config.yaml")
-        check_solver_options(self.qconfig)
+        if num_charge_states is not None:
+            self.qconfig["simulator"].setdefault("latched_model", {})["num_charge_states"] = num_charge_states
+        self.num_charge_states = check_solver_options(self.qconfig)
         if voltage_capacitance_model is not None:
             self.qconfig["simulator"]["voltage_capacitance_model"]["type"] = \
                 None if voltage_capacitance_model in ("none", "null") else voltage_capacitance_model
@@ -112,28 +148,9 @@ class VecQuantumDeviceEnv:
         self._rngs = [np.random.Generator(np.random.PCG64(self.seed + self.env_id_offset + e)) for e in range(B)]
         # ---- library handle ---------------------------------------------------
         self._lib = _lib.lib()
-        cm = self.config["capacitance_model"]
-        cfg = _lib.QdConfig(struct_size=ctypes.sizeof(_lib.QdConfig), n_dot=N, resolution=R, batch=B,
-                            max_steps=self.max_steps, env_chunk=int(env_chunk),
-                            flags=(_lib.QD_FLAG_VALIDATE if validate else 0) | (_lib.QD_FLAG_PIXEL_SEARCH if pixel_search else 0),
-                            noise_flags=self._noise_flags(noise),
-                            gate_ramp_start=float(rew["gate_ramp_start"]),
-                            gate_quadratic_start=float(rew["gate_quadratic_start"]),
-                            barrier_ramp_start=float(rew["barrier_ramp_start"]),
-                            kalman_prior_mean=0.3, kalman_prior_variance=0.5, kalman_prior_mean_nnn=0.15,
-                            kalman_variance_threshold=float(cm.get("variance_threshold", 0.05)),
-                            kalman_process_noise=float(cm.get("process_noise", 0.0)),
-                            rng_seed=self.seed & 0xFFFFFFFFFFFFFFFF, env_id_offset=self.env_id_offset,
-                            use_deltas=1 if sim.get("use_deltas") else 0,
-                            sparse_reward=1 if rew.get("sparse_reward") else 0,
-                            gate_curve_type=_lib.QD_CURVES[rew.get("gate_curve_type", "constant")],
-                            update_method=_lib.QD_UPDATE_DIRECT if self.update_method == "direct" else _lib.QD_UPDATE_KALMAN,
-                            cnn_outputs=self.cnn_outputs, delta_max=float(sim.get("delta_max", 0.0)),
-                            gate_curve_exponent=float(rew.get("gate_curve_exponent", 2.0)),
-                            plunger_radius=float(rew.get("plunger_radius", 0.0)),
-                            outer_plunger_radius=float(rew.get("outer_plunger_radius", 0.0)),
-                            outer_plunger_reward_max=float(rew.get("outer_plunger_reward_max", 0.0)),
-                            barrier_radius=float(rew.get("barrier_radius", 0.0)))
+        cfg = make_qd_config(self.config, self.qconfig, N, R, B, env_chunk=env_chunk,
+                             flags=(_lib.QD_FLAG_VALIDATE if validate else 0) | (_lib.QD_FLAG_PIXEL_SEARCH if pixel_search else 0),
+                             noise_flags=self._noise_flags(noise), seed=self.seed, env_id_offset=self.env_id_offset)
         self._h = ctypes.c_void_p()
         rc = self._lib.qd_create(ctypes.byref(cfg), self.device.index, ctypes.byref(self._h))
         if rc != 0:                          # a partially built handle carries the error text and must be released
@@ -386,8 +403,8 @@ class VecQuantumDeviceEnv:
         return occ
 
     def eigen(self):
-        """(B,C,P,2): ground energy of each pixel's 32-state Hamiltonian and the relative residual of the
-        eigenpair the occupations came from (validate mode)."""
+        """(B,C,P,2): ground energy of each pixel's K-state Hamiltonian (K = num_charge_states) and the relative
+        residual of the eigenpair the occupations came from (validate mode)."""
         eg = np.zeros((self.B, self.C, self.R * self.R, 2))
         _lib.check(self._h, self._lib.qd_get_eigen(self._h, eg.ctypes.data), "qd_get_eigen")
         return eg
@@ -413,6 +430,8 @@ class VecQuantumDeviceEnv:
                 "tasks_by_size": {("9+" if k == 7 else str(k + 2)): int(out[4 + k]) for k in range(8)}}
 
     def candidates(self):
+        """(B,C,P,32,N) int32 kept charge states (validate mode): slots 0..K-1 the K = num_charge_states states in the
+        reference order (|0..0> padding included), slots K..31 are -1."""
         st = np.zeros((self.B, self.C, self.R * self.R, 32, self.N), np.int32)
         _lib.check(self._h, self._lib.qd_get_candidates(self._h, st.ctypes.data), "qd_get_candidates")
         return st
