@@ -157,6 +157,24 @@ int qd_update_capacitance(qd_handle* h, const int32_t* env_ids_dev, int n, const
 int qd_step(qd_handle* h, const float* actions_dev, const float* values_dev,
             const float* log_vars_dev, double* rewards_dev, uint8_t* truncated_dev, void* stream);
 
+/* Episode-end snapshot (what the reference's step() returns for a truncating env before its reset() replaces the
+ * device, multi_agent_wrapper.py:485-584, env.py:240-315): slot i of every destination receives env env_ids_dev[i]'s
+ *   global_dst   [n][R][R][C]      \
+ *   plunger_dst  [n][N][R][R][2]    | float32, the bound outputs (layouts as at qd_bind_outputs)
+ *   barrier_dst  [n][C][R][R][1]    |
+ *   voltages_dst [n][2N-1]         /
+ *   state_dst    [n][qd_state_block_doubles]  float64
+ *   params_dst   [n][qd_param_block_doubles]  float64
+ *   steps_dst    [n]               int32 step counter
+ * all compact, caller-owned device memory.  Any destination may be NULL, and so may an output that was never bound:
+ * that part is skipped.  n == 0 does nothing; n > B, or env_ids_dev == NULL with n > 0, is QD_ERR_ARG; ids outside
+ * [0, B) are skipped (their slots are left untouched).  One kernel launch, stream-ordered on `stream`; the host is
+ * never synchronised.  Called between qd_update_capacitance and qd_load_episodes it keeps the final observation and
+ * state of the envs an automatic reset is about to replace. */
+int qd_snapshot(qd_handle* h, const int32_t* env_ids_dev, int n,
+                float* global_dst, float* plunger_dst, float* barrier_dst, float* voltages_dst,
+                double* state_dst, double* params_dst, int32_t* steps_dst, void* stream);
+
 /* Validation / checkpoint access (blocking copies to HOST memory).
  *   state_host [B][qd_state_block_doubles], steps_host [B] int32
  *   raw_host   [B][C][P] float64 unnormalised sensor signal of the last observe

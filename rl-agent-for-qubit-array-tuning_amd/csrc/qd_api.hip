@@ -620,6 +620,34 @@ extern "C" int qd_step(qd_handle* h, const float* actions, const float* values, 
     return qd_update_capacitance(h, nullptr, 0, values, log_vars, 1, stream);
 }
 
+extern "C" int qd_snapshot(qd_handle* h, const int32_t* env_ids, int n, float* global_dst, float* plunger_dst,
+                           float* barrier_dst, float* voltages_dst, double* state_dst, double* params_dst,
+                           int32_t* steps_dst, void* stream) {
+    if (!h || n < 0) return qd_fail(h, QD_ERR_ARG, "qd_snapshot: bad argument");
+    if (n == 0) return QD_OK;
+    if (n > h->B) return qd_fail(h, QD_ERR_ARG, "qd_snapshot: n > batch");
+    if (!env_ids) return qd_fail(h, QD_ERR_ARG, "qd_snapshot: env_ids_dev is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    QD_ON_DEVICE(h);
+    const long long P = h->P, N = h->N, C = h->C;
+    const struct { const void* src; void* dst; long long bytes; } want[QD_SNAP_SEGS] = {
+        {h->gimg, global_dst, (long long)sizeof(float) * P * C},
+        {h->pimg, plunger_dst, (long long)sizeof(float) * N * P * 2},
+        {h->bimg, barrier_dst, (long long)sizeof(float) * C * P},
+        {h->volt, voltages_dst, (long long)sizeof(float) * (2 * N - 1)},
+        {h->state, state_dst, (long long)sizeof(double) * h->L.s_size},
+        {h->params, params_dst, (long long)sizeof(double) * h->L.size},
+        {h->steps, steps_dst, (long long)sizeof(int32_t)}};
+    QdSnapArgs a{};
+    int k = 0;
+    for (const auto& w : want)                            // unbound outputs and NULL destinations are skipped
+        if (w.src && w.dst) a.seg[k++] = QdSnapSeg{(const unsigned char*)w.src, (unsigned char*)w.dst, w.bytes};
+    if (k == 0) return QD_OK;
+    qd_k_snapshot<<<dim3(n, k), dim3(QD_SNAP_BLOCK), 0, s>>>(env_ids, h->B, a);
+    QD_HIP(hipGetLastError());
+    return QD_OK;
+}
+
 extern "C" int qd_get_state(qd_handle* h, double* state, int32_t* steps) {
     if (!h) return QD_ERR_ARG;
     QD_ON_DEVICE(h);

@@ -6,6 +6,7 @@
 //   qd_k_percentile  a17 (exact 0.5 / 99.5 percentiles, radix select)
 //   qd_k_write_obs   a17, a22 normalise + global / per-agent images + voltages
 //   qd_k_update      a19, a20, a21     Kalman, VGM (SVD pseudo-inverse), ground truth
+//   qd_k_snapshot    episode-end gather of outputs / state / params / step counters (qd_snapshot)
 //
 // Data layout in HBM (all per handle):
 //   params [B][L.size] f64, state [B][L.s_size] f64, steps [B] i32
@@ -975,6 +976,48 @@ qd_k_update(const int* __restrict__ env_ids, int n_env, const double* __restrict
         for (int b = 0; b < C; ++b) st[L.s_barrier_gt + b] = (double)(float)par[L.vbopt + b];
         st[L.s_sensor_gt] = sX[N];
     }
+}
+
+// ---------------------------------------------------------------------------
+// qd_snapshot: gather the per-env segments (bound outputs, state / parameter blocks, step counter) of a list of envs
+// into compact caller buffers, before an in-step reset overwrites them.  One block per (slot, segment); a segment is
+// copied 16 B per lane when its source and destination are both 16-B aligned (then only an odd R^2 leaves a tail of
+// 4-B words), 4 B per lane otherwise.  Consecutive lanes take consecutive 16-B pieces: 1 KiB per wave instruction.
+// ---------------------------------------------------------------------------
+#define QD_SNAP_SEGS 7
+#define QD_SNAP_BLOCK 256
+struct QdSnapSeg {
+    const unsigned char* src;                // segment of env 0 in the handle's buffer
+    unsigned char* dst;                      // slot 0 in the caller's buffer
+    long long bytes;                         // per env, a multiple of 4 (below 8 GiB)
+};
+struct QdSnapArgs { QdSnapSeg seg[QD_SNAP_SEGS]; };
+
+__global__ void __launch_bounds__(QD_SNAP_BLOCK)
+qd_k_snapshot(const int* __restrict__ env_ids, int B, QdSnapArgs a) {
+    const int slot = blockIdx.x;
+    const int e = env_ids[slot];
+    if (e < 0 || e >= B) return;
+    const QdSnapSeg sg = a.seg[blockIdx.y];
+    const unsigned char* src = sg.src + (size_t)e * sg.bytes;
+    unsigned char* dst = sg.dst + (size_t)slot * sg.bytes;
+    long long done = 0;
+    if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+        const int n16 = (int)(sg.bytes >> 4);
+        const uint4* s4 = reinterpret_cast<const uint4*>(src);
+        uint4* d4 = reinterpret_cast<uint4*>(dst);
+        int k = threadIdx.x;
+        for (; k + 3 * QD_SNAP_BLOCK < n16; k += 4 * QD_SNAP_BLOCK) {      // four loads in flight per lane
+            const uint4 v0 = s4[k], v1 = s4[k + QD_SNAP_BLOCK], v2 = s4[k + 2 * QD_SNAP_BLOCK], v3 = s4[k + 3 * QD_SNAP_BLOCK];
+            d4[k] = v0; d4[k + QD_SNAP_BLOCK] = v1; d4[k + 2 * QD_SNAP_BLOCK] = v2; d4[k + 3 * QD_SNAP_BLOCK] = v3;
+        }
+        for (; k < n16; k += QD_SNAP_BLOCK) d4[k] = s4[k];
+        done = (long long)n16 << 4;
+    }
+    const unsigned* s1 = reinterpret_cast<const unsigned*>(src + done);
+    unsigned* d1 = reinterpret_cast<unsigned*>(dst + done);
+    const int n4 = (int)((sg.bytes - done) >> 2);
+    for (int k = threadIdx.x; k < n4; k += QD_SNAP_BLOCK) d1[k] = s1[k];
 }
 
 #endif  // __HIPCC__

@@ -19,7 +19,7 @@ QD_NOISE_LATCH = 4
 EXPORTS = [
     "qd_param_block_doubles", "qd_state_block_doubles", "qd_layout_query", "qd_create", "qd_destroy",
     "qd_last_error", "qd_bind_outputs", "qd_load_episodes", "qd_apply_actions", "qd_observe",
-    "qd_update_capacitance", "qd_step", "qd_get_state", "qd_set_state", "qd_get_raw",
+    "qd_update_capacitance", "qd_step", "qd_snapshot", "qd_get_state", "qd_set_state", "qd_get_raw",
     "qd_get_occupations", "qd_get_candidates", "qd_get_eigen", "qd_get_search_stats", "qd_get_solver_stats", "qd_get_rng_state", "qd_set_rng_state",
     "qd_time_ground_kernel", "qd_time_candidates_kernel", "qd_time_kernels", "qd_timed_kernel_name", "qd_chunk_envs",
 ]
@@ -93,6 +93,7 @@ def lib():
     L.qd_update_capacitance.argtypes = [vp, vp, ctypes.c_int, fp, fp, ctypes.c_int, vp]
     L.qd_update_capacitance.restype = ctypes.c_int
     L.qd_step.argtypes = [vp, fp, fp, fp, dp, vp, vp]; L.qd_step.restype = ctypes.c_int
+    L.qd_snapshot.argtypes = [vp, vp, ctypes.c_int, fp, fp, fp, fp, dp, dp, vp, vp]; L.qd_snapshot.restype = ctypes.c_int
     L.qd_get_state.argtypes = [vp, dp, vp]; L.qd_get_state.restype = ctypes.c_int
     L.qd_set_state.argtypes = [vp, dp, vp]; L.qd_set_state.restype = ctypes.c_int
     L.qd_get_raw.argtypes = [vp, dp, dp]; L.qd_get_raw.restype = ctypes.c_int

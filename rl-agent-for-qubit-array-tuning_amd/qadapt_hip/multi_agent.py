@@ -20,11 +20,21 @@ The reference steps ONE env per RLlib runner through `MultiAgentEnvWrapper`
   MultiAgentEnvWrapper    the reference constructor signature; a batch of one, or -- through the reference's own
                           `base_env_class` hook -- any single gym-style base env.
 
+Episode ends under auto-reset: `final_observation="info"` or `"step"` keeps the last step of a truncating env (its
+outputs and state are captured on the device before the in-step reset replaces it, VecQuantumDeviceEnv.step
+keep_final); `distance_data_dir` / `is_collecting_data` write the reference's per-agent distance histories and cgd
+matrices (multi_agent_wrapper.py:118-133, 459-483, 527-570, 587-660).  See BatchedMultiAgentEnv.
+
 Subclasses ray.rllib's MultiAgentEnv when ray is importable (it is absent in the build container).
-The GIF / distance-history side logging of the reference (:587-895) is tooling, not simulation, and is not built;
-those constructor arguments are accepted and ignored.
+The GIF side logging of the reference (:587-895) is tooling, not simulation, and is not built; `gif_config` is
+accepted and ignored.
 """
 from __future__ import annotations
+
+import glob
+import json
+import os
+import random
 
 import numpy as np
 
@@ -168,18 +178,74 @@ class _HostMirror:
         return {n: h.numpy().copy() for n, h in s.items()}
 
 
+class _FinalMirror:
+    """Pinned host buffers of a step's snapshot (VecQuantumDeviceEnv.final), apart from the 2-deep ring of _HostMirror:
+    stage() queues the device -> host copies of the n captured rows, take() (after the stream has been synchronised)
+    hands out FRESH numpy arrays, whatever zero_copy says -- learners keep final observations past the next step."""
+
+    NAMES = ("plunger_images", "barrier_images", "voltages", "global_image", "state", "params", "steps")
+
+    def __init__(self, with_global):
+        import torch
+        self.torch = torch
+        self.names = [n for n in self.NAMES if with_global or n != "global_image"]
+        self.bufs = {}
+        self.n = 0
+        self.env_ids = None
+
+    def stage(self, final):
+        torch = self.torch
+        self.n = n = int(len(final["env_ids"]))
+        self.env_ids = np.asarray(final["env_ids"])
+        for name in self.names:
+            t = final[name]
+            buf = self.bufs.get(name)
+            if buf is None or buf.shape[0] < n or buf.shape[1:] != t.shape[1:]:
+                buf = self.bufs[name] = torch.empty((max(n, 2 * (buf.shape[0] if buf is not None else 0)),) + tuple(t.shape[1:]),
+                                                    dtype=t.dtype, pin_memory=t.is_cuda)
+            buf[:n].copy_(t, non_blocking=True)
+
+    def take(self):
+        return {name: self.bufs[name][:self.n].numpy().copy() for name in self.names}
+
+
 class BatchedMultiAgentEnv:
     """B logical multi-agent envs over ONE batched backend (one launch set per step).
 
     backend: a VecQuantumDeviceEnv (built here from the keyword arguments when None), or any object with its
-    surface (num_envs, N, R, reset(), step(actions, auto_reset=...), device_state(), the output tensors) -- the
-    CPU-tier tests pass a fake."""
+    surface (num_envs, N, R, reset(), step(actions, auto_reset=..., keep_final=...), final, device_state(),
+    device_state_of(), cgd_full_of(), the output tensors) -- the CPU-tier tests pass a fake."""
+
+    FINAL_OBSERVATION_MODES = (None, "info", "step")
 
     def __init__(self, num_envs=None, return_voltage=True, return_global_state=False, env_config_path=None,
-                 capacitance_model=None, backend=None, auto_reset=True, zero_copy=False, **vec_kwargs):
+                 capacitance_model=None, backend=None, auto_reset=True, zero_copy=False, final_observation=None,
+                 distance_data_dir=None, is_collecting_data=False, **vec_kwargs):
         """auto_reset (default True): an env that truncates gets a new random device and a fresh first observation inside
         the same batched step, the way a vectorised runner expects; with False a truncated env stays truncated until
-        its view's reset() (or reset()) is called.  zero_copy: see _HostMirror."""
+        its view's reset() (or reset()) is called.  zero_copy: see _HostMirror.
+
+        final_observation: what a truncating env's step hands out.
+          None    (default) today's behaviour: under auto_reset the new episode's first observation and device state.
+          "info"  gymnasium's same-step auto-reset convention: observations and infos as with None; every agent's info
+                  of a truncated env also holds "final_observation" (that agent's observation of the old episode's last
+                  step) and "final_info" ({"ground_truth", "current_voltage"} of the old device).
+          "step"  the reference wrapper's convention (multi_agent_wrapper.py:485-584): a truncated env's step returns the
+                  old episode's last observation and infos; its view's reset() then returns the new episode's first
+                  observation, already rendered by the step (no launch, no device round trip).
+        Final-step arrays are fresh host arrays in every mode, zero_copy or not.
+
+        distance_data_dir / is_collecting_data: the reference wrapper's logs, call for call.  Per env, a history of
+        current_voltage - ground_truth (float64, one entry per agent and step) starts at the env's first reset (the
+        vector reset(), or its view's reset()).  At a truncating step the history is saved BEFORE that step's distance
+        is appended, then cleared, then the step's distance (of the old device) is appended; with is_collecting_data the
+        old device's cgd_full is also saved as JSON (<dir>/cgd/).  A reset saves what remains unless is_collecting_data
+        is set, then clears it.  Files: <dir>/<agent_id>/<count:04d>_<rand:06d>.npy, count = max(existing) + 1 per
+        folder; episodes that end at the same batched step are written in ascending env index.  The vector step()
+        makes no per-env reset() call under auto_reset, so there only the truncation save happens and the history
+        runs on into the next episode; views (and MultiAgentEnvWrapper) save at reset() as the reference does."""
+        if final_observation not in self.FINAL_OBSERVATION_MODES:
+            raise ValueError(f"final_observation must be one of {self.FINAL_OBSERVATION_MODES}, got {final_observation!r}")
         if backend is None:
             from .vec_env import VecQuantumDeviceEnv
             backend = VecQuantumDeviceEnv(num_envs, config_path=env_config_path, capacitance_model=capacitance_model,
@@ -198,9 +264,61 @@ class BatchedMultiAgentEnv:
         self.views = [MultiAgentEnvView(self, i) for i in range(self.B)]
         self.launches = 0                       # batched steps issued (tests: one per step, whatever B is)
         self._latest = None                     # (host arrays, device state) of the most recent reset / step
+        self.final_observation = final_observation
+        self.distance_data_dir = distance_data_dir
+        self.is_collecting_data = bool(is_collecting_data)
+        self._keep_final = final_observation is not None or distance_data_dir is not None
+        self._final_mirror = _FinalMirror(return_global_state) if self._keep_final else None
+        self._history = [None] * self.B         # per env: agent -> list of distances (None before the first reset)
+        self._counts = {}
+        if distance_data_dir is not None:       # multi_agent_wrapper.py:118-133; one glob per folder, then counted here
+            for folder in self.roster.ids + ["cgd"]:
+                path = os.path.join(distance_data_dir, folder)
+                os.makedirs(path, exist_ok=True)
+                ext = "*.json" if folder == "cgd" else "*.npy"
+                found = [int(os.path.basename(f).split("_")[0]) for f in glob.glob(os.path.join(path, ext))]
+                self._counts[folder] = max(found) + 1 if found else 1
+
+    # -- distance / cgd logs ---------------------------------------------------------------------------------
+    def _next_file(self, folder, ext):
+        count = self._counts[folder]
+        self._counts[folder] = count + 1
+        return os.path.join(self.distance_data_dir, folder, f"{count:04d}_{random.randint(0, 999999):06d}{ext}")
+
+    def _save_history(self, history):                                   # multi_agent_wrapper.py:587-620
+        for a in self.roster.ids:
+            np.save(self._next_file(a, ".npy"), np.array(history[a], dtype=np.float64))
+
+    def _save_cgd(self, cgd):                                           # multi_agent_wrapper.py:622-660
+        with open(self._next_file("cgd", ".json"), "w") as f:
+            json.dump(np.asarray(cgd).tolist(), f)
+
+    def _log_reset(self, b):                                            # multi_agent_wrapper.py:468-472
+        if self.distance_data_dir is None:
+            return
+        if self._history[b] is not None and not self.is_collecting_data:
+            self._save_history(self._history[b])
+        self._history[b] = {a: [] for a in self.roster.ids}
+
+    def _log_step(self, b, truncated, info, cgd):                       # multi_agent_wrapper.py:527-570
+        if self.distance_data_dir is None or self._history[b] is None:
+            return
+        if truncated:
+            self._save_history(self._history[b])
+            if self.is_collecting_data and cgd is not None:
+                self._save_cgd(cgd)
+            self._history[b] = {a: [] for a in self.roster.ids}
+        for a in self.roster.ids:
+            self._history[b][a].append(info[a]["current_voltage"] - info[a]["ground_truth"])
 
     # -- vector API ----------------------------------------------------------------------------------------
     def reset(self, *, seed=None, options=None):
+        out = self._reset_batch(seed)
+        for b in range(self.B):
+            self._log_reset(b)
+        return out
+
+    def _reset_batch(self, seed=None):
         self.vec.reset(seed=seed)
         host = self._mirror.pull()
         ds = self.vec.device_state()
@@ -216,7 +334,7 @@ class BatchedMultiAgentEnv:
         """First observation of env b's running episode as of the latest launch (after an automatic reset this is
         the new episode's first observation): what a view's reset() returns without touching the device."""
         if self._latest is None:
-            self.reset()
+            self._reset_batch()
         host, ds = self._latest
         return self._obs_of(host, b), self._reset_info(ds, b)
 
@@ -224,7 +342,7 @@ class BatchedMultiAgentEnv:
         """Reset env b ALONE (new random device, step counter 0, fresh first observation), as the reference wrapper's
         reset() does for its one env (multi_agent_wrapper.py:459-483 -> env.py:135-237)."""
         if self._latest is None:
-            self.reset(seed=seed)
+            self._reset_batch(seed=seed)
             return self.current(b)
         self.vec.reset(env_ids=[b], seed=seed)
         host = self._mirror.pull()
@@ -249,11 +367,24 @@ class BatchedMultiAgentEnv:
         return self._launch()
 
     def _launch(self):
-        self.vec.step(self._actions, auto_reset=self.auto_reset)
+        if self._keep_final:
+            self.vec.step(self._actions, auto_reset=self.auto_reset, keep_final=True)
+            final = getattr(self.vec, "final", None)
+            if final is not None:
+                self._final_mirror.stage(final)            # queued before the mirror's pull, which waits for the stream
+        else:
+            self.vec.step(self._actions, auto_reset=self.auto_reset)
+            final = None
         self.launches += 1
         host = self._mirror.pull()
         ds = self.vec.device_state()
         self._latest = (host, ds)
+        fin_host = fin_ds = None
+        fin_slot = {}
+        if final is not None:
+            fin_host = self._final_mirror.take()
+            fin_ds = self.vec.device_state_of(fin_host["state"], fin_host["params"], fin_host["steps"])
+            fin_slot = {int(e): k for k, e in enumerate(self._final_mirror.env_ids)}
         ro = self.roster
         obs, rews, terms, truncs, infos = [], [], [], [], []
         for b in range(self.B):
@@ -261,17 +392,40 @@ class BatchedMultiAgentEnv:
             rews.append(ro.rewards(host["rewards"][b]))
             tr = bool(host["truncated"][b])
             terms.append(ro.flags(False)); truncs.append(ro.flags(tr))
-            try:
-                info = {}
-                for i, a in enumerate(ro.plungers):
-                    info[a] = {"ground_truth": ds["gate_ground_truth"][b][i], "current_voltage": ds["current_gate_voltages"][b][i]}
-                for j, a in enumerate(ro.barriers):
-                    info[a] = {"ground_truth": ds["barrier_ground_truth"][b][j], "current_voltage": ds["current_barrier_voltages"][b][j]}
-            except Exception as e:                                    # multi_agent_wrapper.py:572-573
-                raise RuntimeError(f"Error creating multi-agent info: {e}")
+            info = self._agent_infos(ds, b)
+            if tr and self._keep_final:
+                k = fin_slot.get(b)
+                if k is not None:                          # captured before the in-step reset
+                    f_obs, f_info, cgd = self._obs_of(fin_host, k), self._agent_infos(fin_ds, k), \
+                        self.vec.cgd_full_of(fin_host["params"][k:k + 1])[0]
+                else:                                      # nothing was reset under this step: its outputs are the final ones
+                    f_obs = self._obs_of({n: v[b:b + 1].copy() for n, v in host.items()}, 0)
+                    f_info = self._agent_infos(ds, b)
+                    cgd = self.vec.cgd_full(b) if hasattr(self.vec, "cgd_full") else None
+                self._log_step(b, True, f_info, cgd)
+                if self.final_observation == "info":
+                    for a in ro.ids:
+                        info[a]["final_observation"] = f_obs[a]
+                        info[a]["final_info"] = f_info[a]
+                elif self.final_observation == "step":
+                    obs[b], info = f_obs, f_info
+            else:
+                self._log_step(b, tr, info, None)
             infos.append(info)
         self._staged[:] = False
         return obs, rews, terms, truncs, infos
+
+    def _agent_infos(self, ds, b):
+        ro = self.roster
+        try:
+            info = {}
+            for i, a in enumerate(ro.plungers):
+                info[a] = {"ground_truth": ds["gate_ground_truth"][b][i], "current_voltage": ds["current_gate_voltages"][b][i]}
+            for j, a in enumerate(ro.barriers):
+                info[a] = {"ground_truth": ds["barrier_ground_truth"][b][j], "current_voltage": ds["current_barrier_voltages"][b][j]}
+        except Exception as e:                                    # multi_agent_wrapper.py:572-573
+            raise RuntimeError(f"Error creating multi-agent info: {e}")
+        return info
 
     def _obs_of(self, host, b):
         return self.roster.observations(host["plunger_images"][b], host["barrier_images"][b], host["voltages"][b],
@@ -331,10 +485,14 @@ class MultiAgentEnvView(_RllibBase):
         they truncate (auto_reset, the default): then the env's first observation already exists and is returned
         without touching the device.  An env that truncated WITHOUT being replaced (auto_reset=False), or an explicit
         seed, gets a real reset of this env alone: new device, step counter 0, fresh observation -- the reference
-        wrapper's reset semantics (multi_agent_wrapper.py:459-483)."""
+        wrapper's reset semantics (multi_agent_wrapper.py:459-483).  With distance_data_dir, the env's remaining
+        distance history is saved (unless is_collecting_data) and a new one started, as the reference's reset() does."""
         if seed is not None or self.batch.needs_reset(self.index):
-            return self.batch.reset_env(self.index, seed=seed)
-        return self.batch.current(self.index)
+            out = self.batch.reset_env(self.index, seed=seed)
+        else:
+            out = self.batch.current(self.index)
+        self.batch._log_reset(self.index)
+        return out
 
     def stage(self, agent_actions):
         self.batch._stage(self.index, agent_actions)
@@ -387,7 +545,8 @@ class _SingleEnvBackend:
         self._info = info
         self._remember(obs)
 
-    def step(self, actions, auto_reset=False):
+    def step(self, actions, auto_reset=False, keep_final=False):
+        """Nothing is ever reset under the wrapper here, so the step's own outputs and info are the final ones."""
         N = self.N
         a = np.asarray(actions, np.float32).reshape(-1)
         obs, rewards, terminated, truncated, info = self.env.step(
@@ -402,6 +561,15 @@ class _SingleEnvBackend:
         ds = (self._info or {}).get("current_device_state") or {}
         return {k: np.asarray(v)[None] if np.ndim(v) else np.asarray([v]) for k, v in ds.items()}
 
+    def cgd_full(self, b=0):
+        """The base env's current cgd matrix, looked up as the reference's _save_cgd_matrix does
+        (multi_agent_wrapper.py:622-640); None when it has none."""
+        model = getattr(getattr(self.env, "array", None), "model", None)
+        for name in ("cgd_full", "cgd", "Cgd"):
+            if model is not None and getattr(model, name, None) is not None:
+                return np.array(getattr(model, name))
+        return None
+
     def close(self):
         if hasattr(self.env, "close"):
             self.env.close()
@@ -414,7 +582,12 @@ class MultiAgentEnvWrapper(MultiAgentEnvView):
     def __init__(self, training: bool = True, return_voltage: bool = False, return_global_state: bool = False,
                  gif_config: dict = None, distance_data_dir: str = None, env_config_path: str = None,
                  capacitance_model_checkpoint: str = None, is_collecting_data: bool = False,
-                 base_env_class=None, **base_env_kwargs):
+                 base_env_class=None, final_observation=None, **base_env_kwargs):
+        """final_observation: see BatchedMultiAgentEnv (None, the default, keeps today's behaviour).
+        distance_data_dir / is_collecting_data: the reference's distance-history and cgd logs (BatchedMultiAgentEnv)."""
+        if final_observation not in BatchedMultiAgentEnv.FINAL_OBSERVATION_MODES:
+            raise ValueError(f"final_observation must be one of {BatchedMultiAgentEnv.FINAL_OBSERVATION_MODES}, "
+                             f"got {final_observation!r}")
         if return_global_state and not return_voltage:
             raise ValueError("return_global_state=True requires return_voltage=True (the global "
                              "state extends the per-agent dict observation).")
@@ -433,7 +606,8 @@ class MultiAgentEnvWrapper(MultiAgentEnvView):
         else:
             backend = _SingleEnvBackend(self.base_env, dict(return_global_state=return_global_state))
         batch = BatchedMultiAgentEnv(return_voltage=return_voltage, return_global_state=return_global_state,
-                                     backend=backend)
+                                     backend=backend, final_observation=final_observation,
+                                     distance_data_dir=distance_data_dir, is_collecting_data=is_collecting_data)
         super().__init__(batch, 0)
         self.base_observation_space = self.base_env.observation_space
         self.base_action_space = self.base_env.action_space

@@ -43,6 +43,27 @@ class SyntheticCapacitanceModel:
         return values.to(images.device), log_vars.to(images.device)
 
 
+def device_state_from_rows(L, st, params, steps):
+    """The reference's info["current_device_state"] (env.py:214-222) for host rows of state blocks `st` (n, L.s_size),
+    parameter blocks `params` (n, L.size) and step counters `steps` (n,): ground truths float32, voltages float64."""
+    N, G = L.N, L.N + 1
+    return {"gate_ground_truth": st[:, L.s_gate_gt:L.s_gate_gt + N].astype(np.float32),
+            "barrier_ground_truth": st[:, L.s_barrier_gt:L.s_barrier_gt + N - 1].astype(np.float32),
+            "sensor_ground_truth": st[:, L.s_sensor_gt].copy(),
+            "current_gate_voltages": st[:, L.s_gate_v:L.s_gate_v + N].copy(),
+            "current_barrier_voltages": st[:, L.s_barrier_v:L.s_barrier_v + N - 1].copy(),
+            "virtual_gate_matrix": st[:, L.s_vgm:L.s_vgm + G * G].reshape(-1, G, G).copy(),
+            "virtual_gate_origin": params[:, L.origin:L.origin + G].copy(),
+            "kalman_means": st[:, L.s_kmean:L.s_kmean + N * N].reshape(-1, N, N).copy(),
+            "kalman_variances": st[:, L.s_kvar:L.s_kvar + N * N].reshape(-1, N, N).copy(),
+            "steps": steps}
+
+
+def cgd_full_from_params(L, params):
+    """(n, N+1, 2N) float64: the devices' cgd_full (the reference's array.model.cgd_full) from parameter block rows."""
+    return params[:, L.cgd:L.cgd + L.G * L.V].reshape(-1, L.G, L.V).copy()
+
+
 def make_qd_config(config, qconfig, num_dots, resolution, batch, *, env_chunk=0, flags=0, noise_flags=0, seed=0,
                    env_id_offset=0):
     """The qd_config (include/qdsim.h) of a handle for the env config `config` and the qarray config `qconfig` (both as
@@ -176,6 +197,7 @@ class VecQuantumDeviceEnv:
         self._steps_host = np.zeros(B, np.int64)      # host mirror of the device step counters (truncation is
         self._needs_reset = True                      # deterministic, so auto-reset needs no device read-back)
         self.obs_count = 0
+        self.final = None                             # step(keep_final=True): the truncating envs' last step (_snapshot)
 
     # ------------------------------------------------------------------ helpers
     def _noise_flags(self, noise):
@@ -285,10 +307,13 @@ class VecQuantumDeviceEnv:
         return self._obs()
 
     # ------------------------------------------------------------------ step
-    def step(self, actions, cnn_outputs=None, auto_reset=False):
+    def step(self, actions, cnn_outputs=None, auto_reset=False, keep_final=False):
         """actions: (B, 2N-1) float32 tensor (gates then barriers) or the reference's
         dict {"action_gate_voltages": (B,N), "action_barrier_voltages": (B,N-1)}.
-        Returns (obs, rewards (B,2N-1) float64, terminated (B) bool, truncated (B) bool)."""
+        Returns (obs, rewards (B,2N-1) float64, terminated (B) bool, truncated (B) bool).
+        keep_final: the envs whose episode ends at this step are captured (qd_snapshot, one launch on the same stream)
+        after their last step and before auto_reset replaces their devices; `self.final` then holds them (see
+        _snapshot), else None.  Rewards and truncation flags are not touched by the reset and stay in the return value."""
         if self._needs_reset:
             raise RuntimeError("step() called before reset()")
         if isinstance(actions, dict):
@@ -316,6 +341,11 @@ class VecQuantumDeviceEnv:
         truncated = self.truncated.bool()
         terminated = torch.zeros_like(truncated)
         obs = self._obs()
+        self.final = None
+        if keep_final:
+            done = np.nonzero(self._steps_host >= self.max_steps)[0]
+            if done.size:
+                self.final = self._snapshot(done.astype(np.int32))
         if auto_reset:
             # the step counter alone decides truncation (env.py:281-285), so the host knows which envs are
             # done without reading the device: sampling the new devices below overlaps the kernels launched above
@@ -324,6 +354,41 @@ class VecQuantumDeviceEnv:
                 truncated = truncated.clone()             # self.truncated is rewritten by the next step only, but be explicit
                 obs = self.reset(env_ids=done.astype(np.int32))
         return obs, self.rewards, terminated, truncated
+
+    def _snapshot(self, ids):
+        """qd_snapshot of the envs `ids` (host int32) into fresh compact device tensors, stream-ordered, no host wait:
+        {"global_image" (n,R,R,C), "plunger_images" (n,N,R,R,2), "barrier_images" (n,C,R,R,1), "voltages" (n,2N-1)
+        float32; "state" (n, L.s_size), "params" (n, L.size) float64; "steps" (n,) int32; "env_ids" (n,) host int64}.
+        Slot i is env env_ids[i].  final_device_state() / cgd_full_of() read the state and parameter rows."""
+        n, N, R, C, dev = int(ids.size), self.N, self.R, self.C, self.device
+        ids_dev = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).pin_memory().to(dev, non_blocking=True)
+        f = {"global_image": torch.empty((n, R, R, C), dtype=torch.float32, device=dev),
+             "plunger_images": torch.empty((n, N, R, R, 2), dtype=torch.float32, device=dev),
+             "barrier_images": torch.empty((n, C, R, R, 1), dtype=torch.float32, device=dev),
+             "voltages": torch.empty((n, 2 * N - 1), dtype=torch.float32, device=dev),
+             "state": torch.empty((n, self.L.s_size), dtype=torch.float64, device=dev),
+             "params": torch.empty((n, self.L.size), dtype=torch.float64, device=dev),
+             "steps": torch.empty((n,), dtype=torch.int32, device=dev)}
+        ptr = [ctypes.c_void_p(f[k].data_ptr()) for k in ("global_image", "plunger_images", "barrier_images", "voltages",
+                                                           "state", "params", "steps")]
+        _lib.check(self._h, self._lib.qd_snapshot(self._h, ctypes.c_void_p(ids_dev.data_ptr()), n, *ptr, self._stream()),
+                   "qd_snapshot")
+        f["env_ids"] = ids.astype(np.int64)
+        f["env_ids_dev"] = ids_dev
+        return f
+
+    def device_state_of(self, state, params, steps):
+        """device_state()'s dict for host rows of state / parameter blocks and step counters (e.g. a snapshot's)."""
+        return device_state_from_rows(self.L, state, params, steps)
+
+    def cgd_full_of(self, params):
+        return cgd_full_from_params(self.L, params)
+
+    def final_device_state(self, final=None):
+        """device_state() of the envs of a snapshot (default: self.final), slot by slot, as they were at their last
+        step (blocking host copy)."""
+        f = self.final if final is None else final
+        return self.device_state_of(f["state"].cpu().numpy(), f["params"].cpu().numpy(), f["steps"].cpu().numpy())
 
     # ------------------------------------------------------------------ state access
     def get_state(self):
@@ -380,17 +445,7 @@ class VecQuantumDeviceEnv:
     def device_state(self):
         """The reference's info["current_device_state"] for every env (env.py:214-222)."""
         st, steps = self.get_state()
-        L, N, G = self.L, self.N, self.N + 1
-        return {"gate_ground_truth": st[:, L.s_gate_gt:L.s_gate_gt + N].astype(np.float32),
-                "barrier_ground_truth": st[:, L.s_barrier_gt:L.s_barrier_gt + N - 1].astype(np.float32),
-                "sensor_ground_truth": st[:, L.s_sensor_gt].copy(),
-                "current_gate_voltages": st[:, L.s_gate_v:L.s_gate_v + N].copy(),
-                "current_barrier_voltages": st[:, L.s_barrier_v:L.s_barrier_v + N - 1].copy(),
-                "virtual_gate_matrix": st[:, L.s_vgm:L.s_vgm + G * G].reshape(-1, G, G).copy(),
-                "virtual_gate_origin": self._params_host[:, L.origin:L.origin + G].copy(),
-                "kalman_means": st[:, L.s_kmean:L.s_kmean + N * N].reshape(-1, N, N).copy(),
-                "kalman_variances": st[:, L.s_kvar:L.s_kvar + N * N].reshape(-1, N, N).copy(),
-                "steps": steps}
+        return device_state_from_rows(self.L, st, self._params_host, steps)
 
     def raw(self):
         raw = np.zeros((self.B, self.C, self.R * self.R)); pl = np.zeros((self.B, 2))
