@@ -83,7 +83,8 @@ typedef struct qd_config {
     int32_t num_charge_states;    /* K, latched_model.num_charge_states (qarray_config.yaml:129): kept charge states per
                                      pixel, 1..32; 0 = 32 (the field was reserved0: zeroed callers keep the default).  The
                                      K lowest by (E, index), padded with |0..0> when fewer are valid; H is K x K.
-                                     qd_create returns QD_ERR_ARG outside 0..32                                         */
+                                     QD_ALL_CHARGE_STATES(m) (negative): the untruncated space, see below.
+                                     qd_create returns QD_ERR_ARG above 32 and for an unsupported full space            */
     double delta_max;             /* simulator.delta_max                           */
     double gate_curve_exponent;   /* reward.gate_curve_exponent                    */
     double plunger_radius;        /* reward.plunger_radius        (sparse)         */
@@ -91,6 +92,15 @@ typedef struct qd_config {
     double outer_plunger_reward_max; /* reward.outer_plunger_reward_max (sparse)  */
     double barrier_radius;        /* reward.barrier_radius        (sparse)         */
 } qd_config;
+
+/* num_charge_states = QD_ALL_CHARGE_STATES(m), m >= 1: the reference's num_charge_states = None (ground_state.py:79-83)
+ * with max_charge_carriers = m.  Every pixel uses all M = (m + 1)^N states with 0..m carriers per dot (reference order:
+ * base m + 1, dot 0 the most significant digit) and the ground state of the whole M x M Hamiltonian; no continuous
+ * ground state and no candidate search run.  Supported while M <= 128 and no total-charge sector holds more than 32
+ * states (m = 4: N = 2 and 3; m = 2: up to N = 4); other (N, m) are QD_ERR_ARG.  In this mode qd_get_candidates returns
+ * QD_ERR_ARG (there is no per-pixel list), qd_get_occupations / qd_get_eigen work as usual, and qd_time_kernels reports
+ * 0 for the tile search and the redo pass. */
+#define QD_ALL_CHARGE_STATES(m) (-(m))
 
 #define QD_CURVE_CONSTANT 0
 #define QD_CURVE_POLYNOMIAL 1
@@ -188,7 +198,7 @@ int qd_get_raw(qd_handle* h, double* raw_host, double* plohi_host);
 int qd_get_occupations(qd_handle* h, double* occ_host);
 int qd_get_candidates(qd_handle* h, int32_t* states_host);
 /* eig_host [B][C][P][2] float64 (QD_FLAG_VALIDATE): per pixel the ground energy of the K-state
- * Hamiltonian (K = num_charge_states) (what jnp.linalg.eigh returns first, ground_state.py:150) and the relative residual
+ * Hamiltonian (K = num_charge_states; M x M in the full space) (what jnp.linalg.eigh returns first, ground_state.py:150) and the relative residual
  * ||H x - lambda x||_2 / ||H||_inf of the eigenpair the occupations were formed from. */
 int qd_get_eigen(qd_handle* h, double* eig_host);
 /* Counters of the tile-shared candidate search since qd_create (QD_FLAG_VALIDATE): tiles searched, tiles handed

@@ -8,6 +8,7 @@
 
 #include "qdsim.h"
 #include "qd_kernels.h"
+#include "qd_fullspace.h"
 
 // Scratch + streams of one launch chunk in flight.  Product mode keeps TWO: consecutive chunks alternate between them on
 // two internal streams, so the candidate search of one chunk (float64 VALU bound) runs beside the ground-state stage of
@@ -36,6 +37,9 @@ struct qd_handle {
     unsigned long long* tstats;             // tile-search [0..15] and eigen-solver [16..31] counters (validate mode)
     int tile_search;                        // 0: per-pixel search only; 1: tile-shared candidate search + exact redo pass
     int kept, kc;                           // K = num_charge_states (1..32) and the kept-set size the candidate stage runs (8, 16, 32)
+    int full_m;                             // > 0: the untruncated space with at most full_m carriers per dot (qd_fullspace.h)
+    QdFullTab* ftab;                        //   its sector tables (device)
+    int ppb;                                // pixels per ground-state batch (slab): QD_GS_PPB, or qd_full_ppb in the full space
     unsigned char* slabs;                   // scratch of the ground-state kernels: one slab per batch of QD_GS_PPB pixels in flight
     unsigned* gtiles;                       // [QD_GS_NBIN] tiles per size class of the launch in flight, then the tile lists
     int gs_chunk;                           // envs per ground-state launch (<= chunk)
@@ -145,7 +149,8 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
     if (cfg->cnn_outputs != 2 && cfg->cnn_outputs != 3) return QD_ERR_ARG;
     if (cfg->gate_curve_type < 0 || cfg->gate_curve_type > 3 || cfg->update_method < 0 || cfg->update_method > 1) return QD_ERR_ARG;
     if (cfg->flags & QD_FLAG_RETIRED_TILE_FUSED) return QD_ERR_ARG;      // the fused tile kernel of round 2 is gone
-    if (cfg->num_charge_states < 0 || cfg->num_charge_states > QD_K) return QD_ERR_ARG;
+    if (cfg->num_charge_states > QD_K) return QD_ERR_ARG;
+    if (cfg->num_charge_states < 0 && !qd_full_supported(cfg->n_dot, -cfg->num_charge_states)) return QD_ERR_ARG;
     qd_handle* h = new (std::nothrow) qd_handle();
     if (!h) return QD_ERR_NOMEM;
     memset(h, 0, sizeof(*h));
@@ -153,13 +158,22 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
     h->N = cfg->n_dot; h->R = cfg->resolution; h->B = cfg->batch;
     h->C = h->N - 1; h->P = h->R * h->R; h->L = qd_layout(h->N);
     // K kept states; the candidate stage runs the smallest kept-set size >= K and hands over its first K
-    h->kept = cfg->num_charge_states ? cfg->num_charge_states : QD_K;
+    h->kept = cfg->num_charge_states > 0 ? cfg->num_charge_states : QD_K;
     h->kc = h->kept <= 8 ? 8 : (h->kept <= 16 ? 16 : 32);
+    h->full_m = cfg->num_charge_states < 0 ? -cfg->num_charge_states : 0;
     *out = h;
     QD_ON_DEVICE(h);
     const bool val = (cfg->flags & QD_FLAG_VALIDATE) != 0;
+    QdFullTab ftab;
+    h->ppb = QD_GS_PPB;
+    if (h->full_m) {
+        qd_full_build(h->N, h->full_m, ftab);
+        h->ppb = qd_full_ppb(ftab, val);
+        QD_HIP(hipMalloc(&h->ftab, sizeof(QdFullTab)));
+        QD_HIP(hipMemcpy(h->ftab, &ftab, sizeof(QdFullTab), hipMemcpyHostToDevice));
+    }
     const size_t per_env_rec = (size_t)h->C * h->P * sizeof(QdPixelRec);
-    const size_t batches_per_env = (size_t)h->C * ((h->P + QD_GS_PPB - 1) / QD_GS_PPB);
+    const size_t batches_per_env = (size_t)h->C * ((h->P + h->ppb - 1) / h->ppb);
     const size_t per_env_slab = batches_per_env * (qd_gs_slab_bytes(val) + 4 * (qd_gs_tile_off(QD_GS_NBIN, 1)));
     // scratch in flight per launch, sized for 288 GB of HBM: candidate records (488 B / pixel) + the ground-state slabs
     // (worst case 5.7 KB / pixel: a pixel whose 32 states form ONE hop component needs a 528-double block) -- 64 GiB, i.e.
@@ -233,7 +247,7 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
         QD_HIP(hipMalloc(&h->occ, sizeof(double) * (size_t)h->B * h->C * h->P * h->N));
     // the tile-shared search pays off where neighbouring pixels are close in voltage (fine grids) and needs >= 32
     // candidates valid across a tile (N >= 4); otherwise every pixel is searched on its own
-    h->tile_search = (h->N >= 4 && h->R >= 32 && !(cfg->flags & QD_FLAG_PIXEL_SEARCH)) ? 1 : 0;
+    h->tile_search = (h->N >= 4 && h->R >= 32 && !(cfg->flags & QD_FLAG_PIXEL_SEARCH) && !h->full_m) ? 1 : 0;
     for (int k = 0; k < h->nlanes; ++k) {
         QD_HIP(hipMalloc(&h->lanes[k].slabs, h->gs_batches * qd_gs_slab_bytes(val)));
         QD_HIP(hipMalloc(&h->lanes[k].gtiles, sizeof(unsigned) * (16 + qd_gs_tile_off(QD_GS_NBIN, h->gs_batches))));
@@ -270,7 +284,7 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
 extern "C" int qd_destroy(qd_handle* h) {
     if (!h) return QD_ERR_ARG;
     QdDeviceGuard guard_(h->device);
-    void* bufs[] = {h->params, h->state, h->steps, h->zraw, h->plohi, h->occ, h->tel, h->eig, h->tstats};
+    void* bufs[] = {h->params, h->state, h->steps, h->zraw, h->plohi, h->occ, h->tel, h->eig, h->tstats, h->ftab};
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (int k = 0; k < QD_MAX_LANES; ++k) {
         void* lb[] = {h->lanes[k].recs, h->lanes[k].slabs, h->lanes[k].gtiles};
@@ -422,7 +436,7 @@ static hipError_t qd_launch_solve(qd_handle* h, hipStream_t s) {   // s: the str
 // a11-a13 + a15 for the envs at list positions [base, base + cnt): structure -> solve per size class -> select, in
 // launches of at most gs_chunk envs (the slabs in flight)
 static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int cnt, hipStream_t s, int stages = 7 /*1 structure, 2 solve, 4 select*/) {
-    const int nb = (h->P + QD_GS_PPB - 1) / QD_GS_PPB;
+    const int nb = (h->P + h->ppb - 1) / h->ppb;
     unsigned* tilelist = h->gtiles + 16;
     // records: product mode keeps one launch chunk (slot = position in the chunk), validate mode all envs (position in the list)
     const int rec0 = (h->cfg.flags & QD_FLAG_VALIDATE) ? base : 0;
@@ -437,7 +451,12 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
         QD_DISPATCH_N(h->N, qd_k_gs_structure<NN, VAL_, WPB_><<<dim3(batches), dim3(64 * WPB_), 0, s>>>(env_ids, base + off, rec0 + off, g, h->R, \
                       h->params, h->recs, h->state, h->cfg.noise_flags, h->slabs, h->gtiles, tilelist, h->gs_batches, h->kept))
         const bool small = batches < (unsigned)h->cus;
-        if (h->eig) { if (small) { QD_LAUNCH_STRUCTURE(true, 16); } else { QD_LAUNCH_STRUCTURE(true, 4); } }
+        if (h->full_m) {
+            if (h->eig) { QD_DISPATCH_N(h->N, qd_k_full_structure<NN, true><<<dim3(batches), dim3(256), 0, s>>>(env_ids, base + off, rec0 + off,
+                          g, h->ppb, h->R, h->params, h->state, h->cfg.noise_flags, h->ftab, h->recs, h->slabs, h->gtiles, tilelist, h->gs_batches)); }
+            else { QD_DISPATCH_N(h->N, qd_k_full_structure<NN, false><<<dim3(batches), dim3(256), 0, s>>>(env_ids, base + off, rec0 + off,
+                          g, h->ppb, h->R, h->params, h->state, h->cfg.noise_flags, h->ftab, h->recs, h->slabs, h->gtiles, tilelist, h->gs_batches)); }
+        } else if (h->eig) { if (small) { QD_LAUNCH_STRUCTURE(true, 16); } else { QD_LAUNCH_STRUCTURE(true, 4); } }
         else        { if (small) { QD_LAUNCH_STRUCTURE(false, 16); } else { QD_LAUNCH_STRUCTURE(false, 4); } }
 #undef QD_LAUNCH_STRUCTURE
         QD_HIP(hipGetLastError());
@@ -447,8 +466,13 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
         // 3 dots; the launches of size classes that cannot occur are skipped.  From 4 dots on the memory solver of the rare
         // 13..32-state blocks (one long latency chain: 0.4 ms for 8 envs, 0.9 ms for 180) and the wide register solvers go on
         // two side streams, whatever the batch.  Nor can a component hold more than the K kept states (K = 1: no task at all).
+        // In the full space a component is at most a sector.
         int max_bin = h->N == 2 ? qd_gs_bin(4) : (h->N == 3 ? qd_gs_bin(12) : QD_GS_NBIN - 1);
-        if (h->kept < 2) max_bin = -1;
+        if (h->full_m) {
+            int M = 0, maxsec = 0;
+            qd_full_sizes(h->N, h->full_m, M, maxsec);
+            max_bin = qd_gs_bin(maxsec);
+        } else if (h->kept < 2) max_bin = -1;
         else if (qd_gs_bin(h->kept) < max_bin) max_bin = qd_gs_bin(h->kept);
         const bool forked = max_bin >= 9;            // (8-dot, 4 envs: 1 760 -> 2 520 env-steps/s, 8 envs 3 390 -> 3 590; 2 and 3 dots have no memory-solver launch to hide)
         hipStream_t s9 = forked ? h->side : s, s48 = forked ? h->side2 : s;
@@ -475,7 +499,13 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
         }
         }
         if (stages & 4) {
-        if (h->eig) {
+        if (h->full_m) {
+            const unsigned blk = (unsigned)((h->ppb + 63) / 64 * 64);
+            if (h->eig) { QD_DISPATCH_N(h->N, qd_k_full_select<NN, true><<<dim3(batches), dim3(blk), 0, s>>>(env_ids, base + off, rec0 + off, g,
+                          h->ppb, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, h->eig, h->ftab, h->slabs)); }
+            else { QD_DISPATCH_N(h->N, qd_k_full_select<NN, false><<<dim3(batches), dim3(blk), 0, s>>>(env_ids, base + off, rec0 + off, g,
+                          h->ppb, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, nullptr, h->ftab, h->slabs)); }
+        } else if (h->eig) {
             QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc, qd_k_gs_select<NN, true, KK><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids,
                           base + off, rec0 + off, g, h->R, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, h->eig, h->slabs)));
         } else {
@@ -509,6 +539,7 @@ static int qd_launch_csd(qd_handle* h, const int32_t* env_ids, int base, int cnt
     const int tiles = ((h->R + 7) / 8) * ((h->R + 7) / 8);
     dim3 gt(tiles, h->C, cnt);
     if (parts & 28) return qd_launch_ground(h, env_ids, base, cnt, s, (parts >> 2) & 7);
+    if (h->full_m) return (what & 2) ? qd_launch_ground(h, env_ids, base, cnt, s) : QD_OK;   // no candidate stage
     if (what & 1) {
         if (h->tile_search == 1 && parts != 2) {
             QD_DISPATCH_TILE(h->N, QD_DISPATCH_KC(h->kc, qd_k_tile<NN, KK><<<gt, dim3(64), 0, s>>>(env_ids, base, h->R, h->params, h->state,
@@ -683,6 +714,7 @@ extern "C" int qd_get_occupations(qd_handle* h, double* occ) {
 extern "C" int qd_get_candidates(qd_handle* h, int32_t* states) {
     if (!h || !states) return QD_ERR_ARG;
     if (!(h->cfg.flags & QD_FLAG_VALIDATE)) return qd_fail(h, QD_ERR_STATE, "qd_get_candidates needs QD_FLAG_VALIDATE");
+    if (h->full_m) return qd_fail(h, QD_ERR_ARG, "qd_get_candidates: the full charge-state space keeps no candidate list");
     QD_ON_DEVICE(h);
     QD_HIP(hipDeviceSynchronize());
     // records come over in bounded slices (64 MiB of host staging at most)
@@ -798,6 +830,7 @@ extern "C" int qd_time_kernels(qd_handle* h, int iters, float* mean_ms_out, void
     // (the redo pass consumes the tile search's flags and the solvers overwrite their input blocks: the producing kernel is
     // re-run, untimed, in front of each of their launches)
     for (int k = 0; k < QD_TIMED_KERNELS; ++k) {
+        if (h->full_m && k < 2) { mean_ms_out[k] = 0.f; continue; }     // the full space runs no candidate search
         float total = 0.f;
         for (int i = 0; i < iters; ++i) {
             if (k == 1 && h->tile_search == 1) { int rc = qd_launch_csd(h, nullptr, 0, cnt, s, 1, 1); if (rc) return rc; }

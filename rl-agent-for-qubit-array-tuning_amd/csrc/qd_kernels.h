@@ -3,6 +3,7 @@
 //   qd_k_actions     a2, a3   one thread per env
 //   qd_k_candidates  a5, a8, a9, a10   one pixel per lane, exact k-best search
 //   qd_k_gs_*        a11-a13, a15      structure per half-wave -> dense tasks per lane -> selection per lane (qd_groundstate.h)
+//   (qd_k_full_structure / qd_k_full_select: the untruncated charge-state space, qd_fullspace.h)
 //   qd_k_percentile  a17 (exact 0.5 / 99.5 percentiles, radix select)
 //   qd_k_write_obs   a17, a22 normalise + global / per-agent images + voltages
 //   qd_k_update      a19, a20, a21     Kalman, VGM (SVD pseudo-inverse), ground truth
@@ -271,6 +272,27 @@ __device__ __forceinline__ void qd_gs_locate(const QdGsGeom& g, int batch, int& 
     ch = rem / g.nb; p0 = (rem - ch * g.nb) * QD_GS_PPB;
 }
 
+// end of a structure kernel (after the block's last task): the batch's task counts per size class into the slab and its
+// 64-task tiles appended to the launch-wide tile list of each class
+__device__ __forceinline__ void qd_gs_publish_tiles(const QdBlockLds& sB, const QdSlab& sl, int batch, unsigned* __restrict__ gtiles,
+                                                    unsigned* __restrict__ tilelist, size_t batches_cap) {
+    if (threadIdx.x < QD_GS_NBIN) {
+        const int bin = threadIdx.x;
+        const unsigned nt = sB.cnt[bin];
+        sl.cnt[bin] = nt;
+        const unsigned ntile = (nt + 63u) >> 6;
+        if (ntile) {
+            const unsigned start = atomicAdd(&gtiles[bin], ntile);
+            // tile descriptor: batch (20 bits) | tile index in the batch's list (6) | tasks in the tile - 1 (6)
+            unsigned* tl = tilelist + qd_gs_tile_off(bin, batches_cap) + start;
+            for (unsigned t = 0; t < ntile; ++t) {
+                const unsigned here = nt - t * 64u < 64u ? nt - t * 64u : 64u;
+                tl[t] = ((unsigned)batch << 12) | (t << 6) | (here - 1u);
+            }
+        }
+    }
+}
+
 #ifndef QD_GS_WAVES
 #define QD_GS_WAVES 7            // 72 VGPRs (28 B of scratch per lane) and 7 x 21 KB of LDS per CU (8 dots).  The kernel is latency
                                  // bound (ds_bpermute / LDS chains): measured per env-step 4 waves per SIMD 26.8 us, 5: 22.6, 6: 20.5, 7: 19.6,
@@ -313,21 +335,7 @@ qd_k_gs_structure(const int* __restrict__ env_ids, int env_base, int rec_slot0, 
         qd_ground_structure<N, VALIDATE>(rbase + pc, p < g.P, ps, W, sB, sl, kept);
     }
     __syncthreads();
-    if (threadIdx.x < QD_GS_NBIN) {
-        const int bin = threadIdx.x;
-        const unsigned nt = sB.cnt[bin];
-        sl.cnt[bin] = nt;
-        const unsigned ntile = (nt + 63u) >> 6;
-        if (ntile) {
-            const unsigned start = atomicAdd(&gtiles[bin], ntile);
-            // tile descriptor: batch (20 bits) | tile index in the batch's list (6) | tasks in the tile - 1 (6)
-            unsigned* tl = tilelist + qd_gs_tile_off(bin, batches_cap) + start;
-            for (unsigned t = 0; t < ntile; ++t) {
-                const unsigned here = nt - t * 64u < 64u ? nt - t * 64u : 64u;
-                tl[t] = ((unsigned)batch << 12) | (t << 6) | (here - 1u);
-            }
-        }
-    }
+    qd_gs_publish_tiles(sB, sl, batch, gtiles, tilelist, batches_cap);
 }
 
 // size class -> solver

@@ -98,6 +98,22 @@ QD_HD void qd_pixel_voltages(const double* par, const double* st, int ch, int R,
 // so results are bit-identical to the constant-capacitance path.
 //   vd[N]: in  v' = (cgd_full @ v_ext)[:N];  out  the scaled v'.
 // ---------------------------------------------------------------------------
+// the two scale factors of the linear voltage-dependent capacitance model (1, 1 with the model off), the same operations
+// as at the top of qd_pixel_continuous (which keeps its own copy: the K-state kernels stay instruction for instruction as they were)
+template <int N>
+QD_HD void qd_vc_scales(const double* par, const QdLayout& L, const double* v_ext, double& sa, double& sb) {
+    constexpr int V = 2 * N;
+    sa = 1.0; sb = 1.0;
+    if (par[L.scal + 4] != 0.0) {
+        double sum = 0.0;
+#pragma unroll
+        for (int j = 0; j < V; ++j) sum += fabs(v_ext[j]);
+        const double mabs = sum / (double)V;
+        sa = fma(par[L.scal + 5], mabs, 1.0);
+        sb = fma(par[L.scal + 6], mabs, 1.0);
+    }
+}
+
 template <int N>
 QD_HD void qd_pixel_continuous(const double* par, const double* v_ext, double* vd, double* ncont, double* isa) {
     constexpr int G = N + 1, V = 2 * N;

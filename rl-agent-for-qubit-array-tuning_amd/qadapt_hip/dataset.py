@@ -42,7 +42,7 @@ class GenerationConfig:
     resolution: int | None = None
     env_config_path: str | None = None
     qarray_config_path: str | None = None
-    num_charge_states: int | None = None  # None: the qarray config's latched_model.num_charge_states
+    num_charge_states: int | str | None = None  # None: the qarray config's latched_model.num_charge_states; "all": full space
     noise: bool = True                    # sensor + radial noise as the reference's _get_obs applies them
     extra: dict = field(default_factory=dict)
 

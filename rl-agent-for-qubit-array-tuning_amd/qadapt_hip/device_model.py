@@ -327,25 +327,56 @@ class DeviceSampler:
         return len(self.plan.lo)
 
 
-def check_solver_options(qconfig):
+def full_space_sizes(n_dot, max_charge_carriers):
+    """(M, largest sector) of the untruncated charge-state space: M = (m + 1)^N states with 0..m carriers per dot,
+    split by total charge into sectors that hopping does not connect (charge_states.py:5-34)."""
+    base = int(max_charge_carriers) + 1
+    counts = np.ones(1, np.int64)                         # states per total charge, dot by dot
+    for _ in range(int(n_dot)):
+        counts = np.convolve(counts, np.ones(base, np.int64))
+    return int(base ** int(n_dot)), int(counts.max())
+
+
+FULL_SPACE_MAX_STATES = 128          # M, at most
+FULL_SPACE_MAX_SECTOR = 32           # states of a total-charge sector, at most (the ground-state solvers' cap)
+
+
+def check_solver_options(qconfig, n_dot=None):
     """`simulator.latched_model` of qarray_config.yaml (qarray_config.yaml:127-130 in the reference) selects how the
-    reference solves each pixel.  This library implements the exact path: the K = `num_charge_states` lowest charge states
-    (1..32, default 32) and the EXACT ground state of their K x K Hamiltonian (the reference: dense `jnp.linalg.eigh`,
-    ground_state.py:149-162).  Two options would silently give other numbers than the reference and are refused instead:
+    reference solves each pixel.  This library implements the exact paths:
+      * `num_charge_states: K` (1..32): the K lowest charge states per pixel and the EXACT ground state of their K x K
+        Hamiltonian (the reference: dense `jnp.linalg.eigh`, ground_state.py:149-162);
+      * `num_charge_states: null`, spelled out: the reference model's own default, every charge state with 0..m carriers
+        per dot, m = `simulator.model.max_charge_carriers` (an integer >= 1), and the exact ground state of the whole
+        (m + 1)^N-state Hamiltonian (ground_state.py:79-83).  Supported while M = (m + 1)^N <= 128 and no total-charge
+        sector holds more than 32 states (m = 4: 2 and 3 dots);
+      * the key absent: K = 32 (the reference would raise KeyError there; this library keeps its documented default).
+    Refused, because they would silently give other numbers than the reference:
       * `use_sparse: true` -- the reference then approximates the ground state by 50 float32 Lanczos steps from the uniform
         superposition at ONE representative tunnel coupling (fully_sparse_jax_eigensolver.py:68-133, ground_state.py:117-147);
         that approximation is not built;
       * `num_charge_states` outside 1..32 (or not an integer) -- the kernels keep at most 32 states per pixel (QD_K).
     `charge_state_batch_size` only chunks the reference's scan and does not change its result (any value is fine).
-    Returns K (32 when the key is absent or null)."""
+    n_dot: checks the full space's size for that dot count (None: only the option itself).
+    Returns K, or None for the full space."""
     lm = ((qconfig or {}).get("simulator") or {}).get("latched_model") or {}
     if lm.get("use_sparse"):
         raise NotImplementedError("latched_model.use_sparse: true selects the reference's 50-step float32 Lanczos approximation "
                                   "(fully_sparse_jax_eigensolver.py:68-133); qadapt_hip only computes the exact ground state "
                                   "(the default, use_sparse: false)")
-    k = lm.get("num_charge_states", 32)
-    if k is None:
+    if "num_charge_states" not in lm:
         return 32
+    k = lm["num_charge_states"]
+    if k is None:
+        m = max_charge_carriers(qconfig)
+        if n_dot is not None:
+            M, sec = full_space_sizes(n_dot, m)
+            if M > FULL_SPACE_MAX_STATES or sec > FULL_SPACE_MAX_SECTOR:
+                raise NotImplementedError(
+                    f"latched_model.num_charge_states = null with max_charge_carriers = {m} and {n_dot} dots: M = {M} states, "
+                    f"largest sector {sec}; the full space is supported for M <= {FULL_SPACE_MAX_STATES} with sectors of "
+                    f"at most {FULL_SPACE_MAX_SECTOR} states")
+        return None
     try:
         ok = not isinstance(k, bool) and int(k) == k and 1 <= int(k) <= 32
     except (TypeError, ValueError):
@@ -353,3 +384,17 @@ def check_solver_options(qconfig):
     if not ok:
         raise NotImplementedError(f"latched_model.num_charge_states = {k!r}: the kernels keep 1 to 32 charge states")
     return int(k)
+
+
+def max_charge_carriers(qconfig):
+    """`simulator.model.max_charge_carriers` (qarray_config.yaml:64), the carriers per dot of the full space: an integer
+    >= 1, else ValueError."""
+    m = (((qconfig or {}).get("simulator") or {}).get("model") or {}).get("max_charge_carriers")
+    try:
+        ok = not isinstance(m, bool) and int(m) == m and int(m) >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"simulator.model.max_charge_carriers = {m!r}: the full charge-state space "
+                         "(latched_model.num_charge_states: null) needs an integer >= 1")
+    return int(m)

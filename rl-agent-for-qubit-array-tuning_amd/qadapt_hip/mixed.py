@@ -12,7 +12,8 @@ from __future__ import annotations
 import torch
 
 from . import shard
-from .vec_env import VecQuantumDeviceEnv
+from .device_model import check_solver_options, load_yaml
+from .vec_env import VecQuantumDeviceEnv, override_charge_states
 
 
 class MixedVecQuantumDeviceEnv:
@@ -20,8 +21,13 @@ class MixedVecQuantumDeviceEnv:
                  device=None, streams=True, **kw):
         """counts: {n_dots: n_envs} of the WHOLE job; this object owns rank `rank`'s share of every bucket.
         capacitance_model_factory(n_dots) -> callable or None.  Other keywords go to VecQuantumDeviceEnv
-        (e.g. noise=["latch"] for the latched model of config 5, num_charge_states=16: one K for every bucket)."""
+        (e.g. noise=["latch"] for the latched model of config 5, num_charge_states=16: one K for every bucket; "all" for the
+        full charge-state space, which every bucket's dot count must support: checked here, before any handle exists)."""
         R = resolution if resolution is not None else 64
+        qconfig = override_charge_states(load_yaml(kw.get("qarray_config_path"), "qarray_config.yaml"),
+                                         kw.get("num_charge_states"))
+        for N in sorted(counts):
+            check_solver_options(qconfig, n_dot=N)
         self.assignment = shard.shard_mixed(counts, rank, world, R)
         self.buckets, self.streams = {}, {}
         kw.pop("capacitance_model", None)

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .device_model import DeviceSampler, check_solver_options, load_yaml
+from .device_model import DeviceSampler, check_solver_options, load_yaml, max_charge_carriers
 from .layout import layout
 
 
@@ -64,13 +64,25 @@ def cgd_full_from_params(L, params):
     return params[:, L.cgd:L.cgd + L.G * L.V].reshape(-1, L.G, L.V).copy()
 
 
+def override_charge_states(qconfig, num_charge_states):
+    """The num_charge_states= constructor override applied to a loaded qarray config: None keeps the file's value, "all"
+    writes an explicit null (the full charge-state space), anything else is written as given (checked later)."""
+    if num_charge_states is not None:
+        qconfig["simulator"].setdefault("latched_model", {})["num_charge_states"] = \
+            None if num_charge_states == "all" else num_charge_states
+    return qconfig
+
+
 def make_qd_config(config, qconfig, num_dots, resolution, batch, *, env_chunk=0, flags=0, noise_flags=0, seed=0,
                    env_id_offset=0):
     """The qd_config (include/qdsim.h) of a handle for the env config `config` and the qarray config `qconfig` (both as
     loaded by load_yaml); builds no handle and needs no GPU.  The kept-state count K comes from
-    `qconfig.simulator.latched_model.num_charge_states` (check_solver_options)."""
+    `qconfig.simulator.latched_model.num_charge_states` (check_solver_options); an explicit null there selects the full
+    charge-state space, encoded as -max_charge_carriers (QD_ALL_CHARGE_STATES in qdsim.h)."""
     sim, rew, cm = config["simulator"], config["reward"], config["capacitance_model"]
     nearest = bool(cm.get("nearest_neighbour"))
+    k = check_solver_options(qconfig, n_dot=num_dots)
+    ncs = k if k is not None else -max_charge_carriers(qconfig)
     return _lib.QdConfig(struct_size=ctypes.sizeof(_lib.QdConfig), n_dot=int(num_dots), resolution=int(resolution),
                          batch=int(batch), max_steps=int(sim["max_steps"]), env_chunk=int(env_chunk), flags=int(flags),
                          noise_flags=int(noise_flags),
@@ -85,7 +97,7 @@ def make_qd_config(config, qconfig, num_dots, resolution, batch, *, env_chunk=0,
                          sparse_reward=1 if rew.get("sparse_reward") else 0,
                          gate_curve_type=_lib.QD_CURVES[rew.get("gate_curve_type", "constant")],
                          update_method=_lib.QD_UPDATE_DIRECT if cm["update_method"] == "direct" else _lib.QD_UPDATE_KALMAN,
-                         cnn_outputs=2 if nearest else 3, num_charge_states=check_solver_options(qconfig),
+                         cnn_outputs=2 if nearest else 3, num_charge_states=ncs,
                          delta_max=float(sim.get("delta_max", 0.0)),
                          gate_curve_exponent=float(rew.get("gate_curve_exponent", 2.0)),
                          plunger_radius=float(rew.get("plunger_radius", 0.0)),
@@ -108,23 +120,25 @@ class VecQuantumDeviceEnv:
         voltage_capacitance_model: overrides `simulator.voltage_capacitance_model.type` of the qarray
         config (None keeps the file's value; "linear" or "none").
         num_charge_states: overrides `simulator.latched_model.num_charge_states` of the qarray config (None keeps the
-        file's value): K, the charge states kept per pixel (1..32; the K x K Hamiltonian is solved exactly).  One K per
-        handle."""
+        file's value): K, the charge states kept per pixel (1..32; the K x K Hamiltonian is solved exactly), or "all":
+        every charge state with 0..max_charge_carriers carriers per dot (the YAML's explicit `num_charge_states: null`,
+        the reference model's default).  One mode per handle; `self.num_charge_states` is K, or None for the full space,
+        whose carrier cap is `self.max_charge_carriers` (None otherwise)."""
         if seed is None:
             seed = int(np.random.SeedSequence().entropy) & 0x7FFFFFFFFFFF      # 47 bits: seed + env id stays exact
         self.seed = int(seed)
         self.env_id_offset = int(env_id_offset)
         self.config = load_yaml(config_path, "env_config.yaml")
         self.qconfig = load_yaml(qarray_config_path, "qarray_config.yaml")
-        if num_charge_states is not None:
-            self.qconfig["simulator"].setdefault("latched_model", {})["num_charge_states"] = num_charge_states
-        self.num_charge_states = check_solver_options(self.qconfig)
+        override_charge_states(self.qconfig, num_charge_states)
         if voltage_capacitance_model is not None:
             self.qconfig["simulator"]["voltage_capacitance_model"]["type"] = \
                 None if voltage_capacitance_model in ("none", "null") else voltage_capacitance_model
         sim = self.config["simulator"]
         self.num_envs = int(num_envs)
         self.num_dots = int(num_dots if num_dots is not None else sim["num_dots"])
+        self.num_charge_states = check_solver_options(self.qconfig, n_dot=self.num_dots)
+        self.max_charge_carriers = max_charge_carriers(self.qconfig) if self.num_charge_states is None else None
         self.use_barriers = bool(sim["use_barriers"])
         if not self.use_barriers:
             raise NotImplementedError("env.py only supports barrier mode for now")      # env.py:61-62
@@ -458,8 +472,8 @@ class VecQuantumDeviceEnv:
         return occ
 
     def eigen(self):
-        """(B,C,P,2): ground energy of each pixel's K-state Hamiltonian (K = num_charge_states) and the relative
-        residual of the eigenpair the occupations came from (validate mode)."""
+        """(B,C,P,2): ground energy of each pixel's K-state Hamiltonian (K = num_charge_states; the whole M-state one in
+        the full space) and the relative residual of the eigenpair the occupations came from (validate mode)."""
         eg = np.zeros((self.B, self.C, self.R * self.R, 2))
         _lib.check(self._h, self._lib.qd_get_eigen(self._h, eg.ctypes.data), "qd_get_eigen")
         return eg
@@ -486,7 +500,7 @@ class VecQuantumDeviceEnv:
 
     def candidates(self):
         """(B,C,P,32,N) int32 kept charge states (validate mode): slots 0..K-1 the K = num_charge_states states in the
-        reference order (|0..0> padding included), slots K..31 are -1."""
+        reference order (|0..0> padding included), slots K..31 are -1.  The full space keeps no such list: QdError."""
         st = np.zeros((self.B, self.C, self.R * self.R, 32, self.N), np.int32)
         _lib.check(self._h, self._lib.qd_get_candidates(self._h, st.ctypes.data), "qd_get_candidates")
         return st
