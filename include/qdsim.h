@@ -96,8 +96,10 @@ typedef struct qd_config {
 /* num_charge_states = QD_ALL_CHARGE_STATES(m), m >= 1: the reference's num_charge_states = None (ground_state.py:79-83)
  * with max_charge_carriers = m.  Every pixel uses all M = (m + 1)^N states with 0..m carriers per dot (reference order:
  * base m + 1, dot 0 the most significant digit) and the ground state of the whole M x M Hamiltonian; no continuous
- * ground state and no candidate search run.  Supported while M <= 128 and no total-charge sector holds more than 32
- * states (m = 4: N = 2 and 3; m = 2: up to N = 4); other (N, m) are QD_ERR_ARG.  In this mode qd_get_candidates returns
+ * ground state and no candidate search run.  Supported while M <= 512, no total-charge sector holds more than 64
+ * states, m <= 15 and N m + 1 <= 32 (m = 4: N = 2 and 3; m = 3: up to N = 4; m = 2: up to N = 5; m = 1: up to N = 7);
+ * other (N, m) are QD_ERR_ARG.  Sectors of 33..64 states are solved one per wavefront (csrc/qd_eig_wave.h) and counted
+ * in qd_get_solver_stats' out16[14].  In this mode qd_get_candidates returns
  * QD_ERR_ARG (there is no per-pixel list), qd_get_occupations / qd_get_eigen work as usual, and qd_time_kernels reports
  * 0 for the tile search and the redo pass. */
 #define QD_ALL_CHARGE_STATES(m) (-(m))

@@ -16,6 +16,7 @@
 #define QD_MAX_LANES 4
 struct QdLane {
     QdPixelRec* recs; unsigned char* slabs; unsigned* gtiles;
+    unsigned char* wide;                               // the wide class's lists (full space with a sector above 32 states)
     hipStream_t run, side, side2;
     hipEvent_t ev_fork, ev_join, ev_join2, ev_done;
 };
@@ -39,6 +40,8 @@ struct qd_handle {
     int kept, kc;                           // K = num_charge_states (1..32) and the kept-set size the candidate stage runs (8, 16, 32)
     int full_m;                             // > 0: the untruncated space with at most full_m carriers per dot (qd_fullspace.h)
     QdFullTab* ftab;                        //   its sector tables (device)
+    int full_spl;                           //   states per lane of its structure kernel (2, 4, 8)
+    QdWide wide;                            //   the wide class (sectors of 33..64 states): capw > 0 when the handle has one
     int ppb;                                // pixels per ground-state batch (slab): QD_GS_PPB, or qd_full_ppb in the full space
     unsigned char* slabs;                   // scratch of the ground-state kernels: one slab per batch of QD_GS_PPB pixels in flight
     unsigned* gtiles;                       // [QD_GS_NBIN] tiles per size class of the launch in flight, then the tile lists
@@ -57,7 +60,7 @@ struct qd_handle {
 
 static void qd_use_lane(qd_handle* h, int k) {
     const QdLane& ln = h->lanes[k];
-    h->recs = ln.recs; h->slabs = ln.slabs; h->gtiles = ln.gtiles;
+    h->recs = ln.recs; h->slabs = ln.slabs; h->gtiles = ln.gtiles; h->wide.buf = ln.wide;
     h->side = ln.side; h->side2 = ln.side2; h->ev_fork = ln.ev_fork; h->ev_join = ln.ev_join; h->ev_join2 = ln.ev_join2;
 }
 
@@ -169,12 +172,15 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
     if (h->full_m) {
         qd_full_build(h->N, h->full_m, ftab);
         h->ppb = qd_full_ppb(ftab, val);
+        if (h->ppb < 1) return qd_fail(h, QD_ERR_ARG, "the full charge-state space of this shape does not fit a slab");
+        h->full_spl = qd_full_spl(ftab.M);
+        if (qd_full_wide(ftab.maxsec)) h->wide.capw = (unsigned)((h->ppb * qd_full_wide_tasks(ftab) + 1) & ~1);
         QD_HIP(hipMalloc(&h->ftab, sizeof(QdFullTab)));
         QD_HIP(hipMemcpy(h->ftab, &ftab, sizeof(QdFullTab), hipMemcpyHostToDevice));
     }
     const size_t per_env_rec = (size_t)h->C * h->P * sizeof(QdPixelRec);
     const size_t batches_per_env = (size_t)h->C * ((h->P + h->ppb - 1) / h->ppb);
-    const size_t per_env_slab = batches_per_env * (qd_gs_slab_bytes(val) + 4 * (qd_gs_tile_off(QD_GS_NBIN, 1)));
+    const size_t per_env_slab = batches_per_env * (qd_gs_slab_bytes(val) + 4 * (qd_gs_tile_off(QD_GS_NBIN, 1)) + qd_wide_bytes(h->wide.capw));
     // scratch in flight per launch, sized for 288 GB of HBM: candidate records (488 B / pixel) + the ground-state slabs
     // (worst case 5.7 KB / pixel: a pixel whose 32 states form ONE hop component needs a 528-double block) -- 64 GiB, i.e.
     // 388 envs of the 8-dot 64x64 headline per launch (measured, whole bench: 20 GiB 9 070, 40 GiB 9 670, 64 GiB 9 950 env-steps/s),
@@ -251,6 +257,7 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
     for (int k = 0; k < h->nlanes; ++k) {
         QD_HIP(hipMalloc(&h->lanes[k].slabs, h->gs_batches * qd_gs_slab_bytes(val)));
         QD_HIP(hipMalloc(&h->lanes[k].gtiles, sizeof(unsigned) * (16 + qd_gs_tile_off(QD_GS_NBIN, h->gs_batches))));
+        if (h->wide.capw) QD_HIP(hipMalloc(&h->lanes[k].wide, h->gs_batches * qd_wide_bytes(h->wide.capw)));
     }
     qd_use_lane(h, 0);
     if (cfg->flags & QD_FLAG_VALIDATE) {
@@ -287,7 +294,7 @@ extern "C" int qd_destroy(qd_handle* h) {
     void* bufs[] = {h->params, h->state, h->steps, h->zraw, h->plohi, h->occ, h->tel, h->eig, h->tstats, h->ftab};
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (int k = 0; k < QD_MAX_LANES; ++k) {
-        void* lb[] = {h->lanes[k].recs, h->lanes[k].slabs, h->lanes[k].gtiles};
+        void* lb[] = {h->lanes[k].recs, h->lanes[k].slabs, h->lanes[k].gtiles, h->lanes[k].wide};
         for (void* b : lb) if (b) (void)hipFree(b);
     }
     for (int k = 0; k < 2; ++k) {
@@ -452,10 +459,21 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
                       h->params, h->recs, h->state, h->cfg.noise_flags, h->slabs, h->gtiles, tilelist, h->gs_batches, h->kept))
         const bool small = batches < (unsigned)h->cus;
         if (h->full_m) {
-            if (h->eig) { QD_DISPATCH_N(h->N, qd_k_full_structure<NN, true><<<dim3(batches), dim3(256), 0, s>>>(env_ids, base + off, rec0 + off,
-                          g, h->ppb, h->R, h->params, h->state, h->cfg.noise_flags, h->ftab, h->recs, h->slabs, h->gtiles, tilelist, h->gs_batches)); }
-            else { QD_DISPATCH_N(h->N, qd_k_full_structure<NN, false><<<dim3(batches), dim3(256), 0, s>>>(env_ids, base + off, rec0 + off,
-                          g, h->ppb, h->R, h->params, h->state, h->cfg.noise_flags, h->ftab, h->recs, h->slabs, h->gtiles, tilelist, h->gs_batches)); }
+            // (shapes without a sector above 32 states have M <= 128: the kernel without the wide class, 2 states per lane)
+#define QD_LAUNCH_FULL(VAL_, SPL_, WIDE_)                                                                                         \
+            QD_DISPATCH_N(h->N, qd_k_full_structure<NN, VAL_, SPL_, WIDE_><<<dim3(batches), dim3(64 * QdFullWpb<SPL_>::v), 0, s>>>(env_ids,    \
+                          base + off, rec0 + off, g, h->ppb, h->R, h->params, h->state, h->cfg.noise_flags, h->ftab, h->recs, h->slabs,   \
+                          h->gtiles, tilelist, h->gs_batches, h->wide))
+#define QD_LAUNCH_FULL_V(VAL_)                                                                                                    \
+            do {                                                                                                                  \
+                if (!h->wide.capw && h->full_spl == 2) { QD_LAUNCH_FULL(VAL_, 2, false); }                                        \
+                else if (h->full_spl == 2) { QD_LAUNCH_FULL(VAL_, 2, true); }                                                     \
+                else if (h->full_spl == 4) { QD_LAUNCH_FULL(VAL_, 4, true); }                                                     \
+                else { QD_LAUNCH_FULL(VAL_, 8, true); }                                                                           \
+            } while (0)
+            if (h->eig) QD_LAUNCH_FULL_V(true); else QD_LAUNCH_FULL_V(false);
+#undef QD_LAUNCH_FULL_V
+#undef QD_LAUNCH_FULL
         } else if (h->eig) { if (small) { QD_LAUNCH_STRUCTURE(true, 16); } else { QD_LAUNCH_STRUCTURE(true, 4); } }
         else        { if (small) { QD_LAUNCH_STRUCTURE(false, 16); } else { QD_LAUNCH_STRUCTURE(false, 4); } }
 #undef QD_LAUNCH_STRUCTURE
@@ -471,7 +489,7 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
         if (h->full_m) {
             int M = 0, maxsec = 0;
             qd_full_sizes(h->N, h->full_m, M, maxsec);
-            max_bin = qd_gs_bin(maxsec);
+            max_bin = qd_gs_bin(maxsec < QD_K ? maxsec : QD_K);
         } else if (h->kept < 2) max_bin = -1;
         else if (qd_gs_bin(h->kept) < max_bin) max_bin = qd_gs_bin(h->kept);
         const bool forked = max_bin >= 9;            // (8-dot, 4 envs: 1 760 -> 2 520 env-steps/s, 8 envs 3 390 -> 3 590; 2 and 3 dots have no memory-solver launch to hide)
@@ -480,6 +498,13 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
             QD_HIP(hipEventRecord(h->ev_fork, s));
             QD_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
             QD_HIP(hipStreamWaitEvent(h->side2, h->ev_fork, 0));
+        }
+        if (h->wide.capw) {                            // the wide class first: its tasks are the longest
+            const size_t slots = (size_t)batches * h->wide.capw, full = (size_t)h->cus * 4;
+            const dim3 wgrid((unsigned)(slots < full ? slots : full));
+            if (h->eig) qd_k_full_solve_wide<true><<<wgrid, dim3(64), 0, s>>>(h->slabs, h->wide, batches, h->tstats);
+            else        qd_k_full_solve_wide<false><<<wgrid, dim3(64), 0, s>>>(h->slabs, h->wide, batches, nullptr);
+            QD_HIP(hipGetLastError());
         }
         if (max_bin >= 9) QD_HIP(qd_launch_solve<9>(h, s9));
         if (forked) QD_HIP(hipEventRecord(h->ev_join, h->side));
@@ -501,10 +526,12 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
         if (stages & 4) {
         if (h->full_m) {
             const unsigned blk = (unsigned)((h->ppb + 63) / 64 * 64);
-            if (h->eig) { QD_DISPATCH_N(h->N, qd_k_full_select<NN, true><<<dim3(batches), dim3(blk), 0, s>>>(env_ids, base + off, rec0 + off, g,
-                          h->ppb, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, h->eig, h->ftab, h->slabs)); }
-            else { QD_DISPATCH_N(h->N, qd_k_full_select<NN, false><<<dim3(batches), dim3(blk), 0, s>>>(env_ids, base + off, rec0 + off, g,
-                          h->ppb, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, nullptr, h->ftab, h->slabs)); }
+#define QD_LAUNCH_FSEL(VAL_, WIDE_, EIG_)                                                                                          \
+            QD_DISPATCH_N(h->N, qd_k_full_select<NN, VAL_, WIDE_><<<dim3(batches), dim3(blk), 0, s>>>(env_ids, base + off, rec0 + off, g,   \
+                          h->ppb, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, EIG_, h->ftab, h->slabs, h->wide))
+            if (h->eig) { if (h->wide.capw) { QD_LAUNCH_FSEL(true, true, h->eig); } else { QD_LAUNCH_FSEL(true, false, h->eig); } }
+            else { if (h->wide.capw) { QD_LAUNCH_FSEL(false, true, nullptr); } else { QD_LAUNCH_FSEL(false, false, nullptr); } }
+#undef QD_LAUNCH_FSEL
         } else if (h->eig) {
             QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc, qd_k_gs_select<NN, true, KK><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids,
                           base + off, rec0 + off, g, h->R, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, h->eig, h->slabs)));

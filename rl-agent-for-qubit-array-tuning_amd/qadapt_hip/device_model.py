@@ -337,8 +337,10 @@ def full_space_sizes(n_dot, max_charge_carriers):
     return int(base ** int(n_dot)), int(counts.max())
 
 
-FULL_SPACE_MAX_STATES = 128          # M, at most
-FULL_SPACE_MAX_SECTOR = 32           # states of a total-charge sector, at most (the ground-state solvers' cap)
+FULL_SPACE_MAX_STATES = 512          # M, at most
+FULL_SPACE_MAX_SECTOR = 64           # states of a total-charge sector, at most: one per lane of the wave-per-block solver
+FULL_SPACE_MAX_CARRIERS = 15         # m, at most (the state tables keep 4 bits per dot)
+FULL_SPACE_MAX_SECTORS = 32          # total-charge sectors, N m + 1, at most
 
 
 def check_solver_options(qconfig, n_dot=None):
@@ -348,8 +350,9 @@ def check_solver_options(qconfig, n_dot=None):
         Hamiltonian (the reference: dense `jnp.linalg.eigh`, ground_state.py:149-162);
       * `num_charge_states: null`, spelled out: the reference model's own default, every charge state with 0..m carriers
         per dot, m = `simulator.model.max_charge_carriers` (an integer >= 1), and the exact ground state of the whole
-        (m + 1)^N-state Hamiltonian (ground_state.py:79-83).  Supported while M = (m + 1)^N <= 128 and no total-charge
-        sector holds more than 32 states (m = 4: 2 and 3 dots);
+        (m + 1)^N-state Hamiltonian (ground_state.py:79-83).  Supported while M = (m + 1)^N <= 512, no total-charge
+        sector holds more than 64 states, m <= 15 and N m + 1 <= 32 (m = 4: 2 and 3 dots; m = 3: up to 4 dots; m = 2: up
+        to 5; m = 1: up to 7);
       * the key absent: K = 32 (the reference would raise KeyError there; this library keeps its documented default).
     Refused, because they would silently give other numbers than the reference:
       * `use_sparse: true` -- the reference then approximates the ground state by 50 float32 Lanczos steps from the uniform
@@ -371,11 +374,13 @@ def check_solver_options(qconfig, n_dot=None):
         m = max_charge_carriers(qconfig)
         if n_dot is not None:
             M, sec = full_space_sizes(n_dot, m)
-            if M > FULL_SPACE_MAX_STATES or sec > FULL_SPACE_MAX_SECTOR:
+            if (M > FULL_SPACE_MAX_STATES or sec > FULL_SPACE_MAX_SECTOR or m > FULL_SPACE_MAX_CARRIERS
+                    or n_dot * m + 1 > FULL_SPACE_MAX_SECTORS):
                 raise NotImplementedError(
                     f"latched_model.num_charge_states = null with max_charge_carriers = {m} and {n_dot} dots: M = {M} states, "
                     f"largest sector {sec}; the full space is supported for M <= {FULL_SPACE_MAX_STATES} with sectors of "
-                    f"at most {FULL_SPACE_MAX_SECTOR} states")
+                    f"at most {FULL_SPACE_MAX_SECTOR} states, at most {FULL_SPACE_MAX_CARRIERS} carriers per dot and "
+                    f"at most {FULL_SPACE_MAX_SECTORS} total-charge sectors")
         return None
     try:
         ok = not isinstance(k, bool) and int(k) == k and 1 <= int(k) <= 32
