@@ -187,6 +187,62 @@ int qd_snapshot(qd_handle* h, const int32_t* env_ids_dev, int n,
                 float* global_dst, float* plunger_dst, float* barrier_dst, float* voltages_dst,
                 double* state_dst, double* params_dst, int32_t* steps_dst, void* stream);
 
+/* Stateless probe scans: QarrayBaseClass._get_obs(gate_voltages, barrier_voltages, sensor_voltage) asked as a side
+ * question (qarray_base_class.py:171-229; its users outside step() are map_device_range.py, map_full_device_range.py,
+ * gui/image_generator.py:136 and the dataset generator).  Renders nq queries in one call; every pointer is caller-owned
+ * DEVICE memory, the call is stream-ordered on `stream` and never synchronises the host.
+ *   env_of_query_dev [nq]      int32, each in [0, B): query q uses that env's parameter block and its CURRENT virtual
+ *                              gate matrix and origin; everything else comes from the query
+ *   gate_v_dev       [nq][N]   virtual gate voltages, as _get_obs takes them
+ *   barrier_v_dev    [nq][N-1]
+ *   sensor_v_dev     [nq]      or NULL: 0.0, as sensor_voltage=None
+ *   window_dev       [nq]      half-widths of the scan window, or NULL: the env's own window
+ *   raw_dst          [nq][C][P]    float64 unnormalised signal, layout of qd_get_raw; may be NULL
+ *   image_dst        [nq][R][R][C] float32, normalised per query with its own 0.5 / 99.5 percentiles, as the
+ *                                  global_image of qd_observe; may be NULL
+ *   plohi_dst        [nq][2]       those percentiles; may be NULL
+ * Probes are DETERMINISTIC: every launch runs with noise flags 0 whatever the handle's noise_flags are (no sensor noise,
+ * no radial noise, no latching); stochastic probes are not built.  The hot kernels are the ones qd_observe runs, on
+ * probe copies of the parameter and state blocks, so a probe at an env's own voltages, sensor voltage and window equals
+ * the raw signal, percentiles and image of a noise-free qd_observe bit for bit.
+ * The call changes nothing that qd_step, qd_observe or any qd_get_* function can see: not the state blocks, step
+ * counters or Kalman state, not the bound outputs, raw signal or percentiles of the last observe, not the observation
+ * serial of qd_get_rng_state or the telegraph chains.  nq may exceed B and many queries may name one env; queries run in
+ * launch chunks of qd_chunk_envs.  Scratch (per query in flight: a parameter copy, a state block, C*P doubles of signal)
+ * is allocated by the first probe and freed by qd_destroy; handles that never probe allocate nothing.  That first
+ * call allocates with hipMalloc, which may wait for the device: "never synchronises" holds from the second probe on.
+ * nq == 0 does nothing.  QD_ERR_ARG, found without reading the device: nq < 0, env_of_query_dev, gate_v_dev or
+ * barrier_v_dev NULL.  An id outside [0, B) leaves its destination slots untouched, as at qd_snapshot.  A handle created
+ * with QD_FLAG_VALIDATE answers QD_ERR_STATE: its record, occupation and eigenvalue buffers hold B envs and belong to
+ * the last observe.  Works for num_charge_states 1..32 and in the full charge-state space. */
+int qd_probe(qd_handle* h, const int32_t* env_of_query_dev, int nq, const double* gate_v_dev,
+             const double* barrier_v_dev, const double* sensor_v_dev, const double* window_dev,
+             double* raw_dst, float* image_dst, double* plohi_dst, void* stream);
+
+/* Stitches one channel of nx*ny probe signals into one composite image on the device (map_device_range.py:134-170,
+ * map_full_device_range.py:168-194).  raw_dev [nx*ny][C][P] as qd_probe wrote it, query index i*ny + j for scan (i, j);
+ * composite_dst [ny*R][nx*R] float32; both DEVICE memory, stream-ordered, no host wait.
+ *   QD_MAP_GLOBAL    scan (i, j) at rows j*R.., columns i*R..; ONE 0.5 / 99.5 percentile pair (numpy 'linear') over the
+ *                    whole composite, exact (a radix select spread over the grid, same keys and interpolation as the
+ *                    per-env percentiles); (z - p_lo) / (p_hi - p_lo) clipped to [0, 1], all zero when p_hi <= p_lo.
+ *                    plohi_dst [2] or NULL.
+ *   QD_MAP_PER_SCAN  every scan normalised with its own percentiles; row blocks flipped (block ny-1-j holds scan j).
+ *                    plohi_dst [nx*ny][2] or NULL.
+ * QD_ERR_ARG: NULL raw_dev or composite_dst, nx or ny < 1, more than 65535 scans, nx*ny*P >= 2^32 (the select counts in
+ * 32 bits), channel outside [0, C), unknown mode.
+ * Scratch (nx*ny*P doubles) is allocated on first use, grown on demand and freed by qd_destroy.  A call that allocates
+ * or grows it (the first, and any with more scans than every call before) uses hipMalloc / hipFree and WAITS for the
+ * device; all other calls are stream-ordered without a host wait. */
+#define QD_MAP_GLOBAL 0
+#define QD_MAP_PER_SCAN 1
+int qd_probe_compose(qd_handle* h, const double* raw_dev, int nx, int ny, int channel, int mode,
+                     float* composite_dst, double* plohi_dst, void* stream);
+/* Timing hook of scripts/probe_rate.py: mean HIP-event duration over `iters` runs of the 0.5 / 99.5 percentiles of the n
+ * doubles at z_dev, by the grid-wide select of QD_MAP_GLOBAL (single_block 0) or by one block of the per-env percentile
+ * kernel (single_block 1); out_dev [2] receives the percentiles.  n < 2^32. */
+int qd_time_select(qd_handle* h, const double* z_dev, long long n, int single_block, int iters,
+                   double* out_dev, float* mean_ms, void* stream);
+
 /* Validation / checkpoint access (blocking copies to HOST memory).
  *   state_host [B][qd_state_block_doubles], steps_host [B] int32
  *   raw_host   [B][C][P] float64 unnormalised sensor signal of the last observe

@@ -9,6 +9,7 @@
 #include "qdsim.h"
 #include "qd_kernels.h"
 #include "qd_fullspace.h"
+#include "qd_probe.h"
 
 // Scratch + streams of one launch chunk in flight.  Product mode keeps TWO: consecutive chunks alternate between them on
 // two internal streams, so the candidate search of one chunk (float64 VALU bound) runs beside the ground-state stage of
@@ -55,6 +56,11 @@ struct qd_handle {
     hipEvent_t ev_fork, ev_join, ev_join2;  // rare 13..32-state blocks is one long latency chain, and the short register-solver
                                             // launches fill each other's tails
     unsigned long long obs_serial;
+    // probe scans (qd_probe): one launch chunk of parameter copies, state blocks, signals and percentiles, allocated by the
+    // first probe; the composite's compact channel, per-scan percentiles and select state (qd_probe_compose) likewise
+    double *pparams, *pstate, *pz, *pplohi;
+    double *cz, *cplohi; size_t cz_cap, cplohi_cap;
+    QdSelState* sel;
     char err[512];
 };
 
@@ -291,7 +297,8 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
 extern "C" int qd_destroy(qd_handle* h) {
     if (!h) return QD_ERR_ARG;
     QdDeviceGuard guard_(h->device);
-    void* bufs[] = {h->params, h->state, h->steps, h->zraw, h->plohi, h->occ, h->tel, h->eig, h->tstats, h->ftab};
+    void* bufs[] = {h->params, h->state, h->steps, h->zraw, h->plohi, h->occ, h->tel, h->eig, h->tstats, h->ftab,
+                    h->pparams, h->pstate, h->pz, h->pplohi, h->cz, h->cplohi, h->sel};
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (int k = 0; k < QD_MAX_LANES; ++k) {
         void* lb[] = {h->lanes[k].recs, h->lanes[k].slabs, h->lanes[k].gtiles, h->lanes[k].wide};
@@ -703,6 +710,191 @@ extern "C" int qd_snapshot(qd_handle* h, const int32_t* env_ids, int n, float* g
     if (k == 0) return QD_OK;
     qd_k_snapshot<<<dim3(n, k), dim3(QD_SNAP_BLOCK), 0, s>>>(env_ids, h->B, a);
     QD_HIP(hipGetLastError());
+    return QD_OK;
+}
+
+// The env buffers the launchers read from the handle, pointed at the probe's for the lifetime of this object: the hot
+// kernels run on the probe blocks with noise_flags 0 and nothing of the envs is written.
+// The boundary: under this scope only qd_launch_csd / qd_launch_ground / qd_launch_solve, qd_k_sensor (with qd_noise_cfg)
+// and qd_k_percentile run, and of the per-env handle fields they read exactly the six swapped here
+//   params, state, zraw, plohi, occ, cfg.noise_flags
+// (tel and obs_serial go into qd_noise_cfg but are dead with flags 0; eig / tstats are NULL: validate handles are refused;
+// recs, slabs, gtiles, wide are launch scratch of lane 0).  steps, tel, the bound outputs gimg / pimg / bimg / volt and
+// the staging ring are NOT swapped: a launcher that starts to read one of them must get a probe twin here first, or it
+// acts on env data during a probe (tests/test_gpu_probe.py, the bit-identity and the no-footprint test, would show it).
+struct QdProbeScope {
+    qd_handle* h; double *params, *state, *zraw, *plohi, *occ; int noise_flags;
+    explicit QdProbeScope(qd_handle* h_) : h(h_), params(h_->params), state(h_->state), zraw(h_->zraw), plohi(h_->plohi),
+                                           occ(h_->occ), noise_flags(h_->cfg.noise_flags) {
+        h->params = h->pparams; h->state = h->pstate; h->zraw = h->pz; h->plohi = h->pplohi; h->occ = nullptr;
+        h->cfg.noise_flags = 0;
+        qd_use_lane(h, 0);
+    }
+    ~QdProbeScope() {
+        h->params = params; h->state = state; h->zraw = zraw; h->plohi = plohi; h->occ = occ; h->cfg.noise_flags = noise_flags;
+    }
+};
+
+static int qd_probe_chunk(qd_handle* h, int cnt, hipStream_t s) {
+    QdProbeScope scope(h);
+    int rc = qd_launch_csd(h, nullptr, 0, cnt, s, 3);
+    if (rc) return rc;
+    dim3 g3((h->P + 255) / 256, h->C, cnt);
+    QD_DISPATCH_N(h->N, qd_k_sensor<NN><<<g3, dim3(256), 0, s>>>(nullptr, h->R, h->params, h->state, h->zraw, qd_noise_cfg(h)));
+    QD_HIP(hipGetLastError());
+    if ((long)h->C * h->P <= (long)QD_PCT_KPT * QD_PCT_BLOCK)
+        qd_k_percentile<true><<<dim3(cnt), dim3(QD_PCT_BLOCK), 0, s>>>(nullptr, (long)h->C * h->P, h->zraw, h->plohi);
+    else
+        qd_k_percentile<false><<<dim3(cnt), dim3(QD_PCT_BLOCK), 0, s>>>(nullptr, (long)h->C * h->P, h->zraw, h->plohi);
+    QD_HIP(hipGetLastError());
+    return QD_OK;
+}
+
+extern "C" int qd_probe(qd_handle* h, const int32_t* env_of_query, int nq, const double* gate_v, const double* barrier_v,
+                        const double* sensor_v, const double* window, double* raw_dst, float* image_dst, double* plohi_dst,
+                        void* stream) {
+    if (!h) return QD_ERR_ARG;
+    if (nq < 0) return qd_fail(h, QD_ERR_ARG, "qd_probe: nq < 0");
+    if (!env_of_query) return qd_fail(h, QD_ERR_ARG, "qd_probe: env_of_query_dev is NULL");
+    if (!gate_v || !barrier_v) return qd_fail(h, QD_ERR_ARG, "qd_probe: gate_v_dev or barrier_v_dev is NULL");
+    if (h->cfg.flags & QD_FLAG_VALIDATE)
+        return qd_fail(h, QD_ERR_STATE, "qd_probe: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
+                                        "B envs' last observe and renders no probes; use a handle without the flag");
+    if (nq == 0) return QD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    QD_ON_DEVICE(h);
+    const int pc = h->chunk;                                  // queries in flight = envs per launch chunk (lane 0's scratch)
+    if (!h->pparams) {
+        QD_HIP(hipMalloc(&h->pparams, sizeof(double) * (size_t)pc * h->L.size));
+        QD_HIP(hipMalloc(&h->pstate, sizeof(double) * (size_t)pc * h->L.s_size));
+        QD_HIP(hipMalloc(&h->pz, sizeof(double) * (size_t)pc * h->C * h->P));
+        QD_HIP(hipMalloc(&h->pplohi, sizeof(double) * 2 * (size_t)pc));
+    }
+    const QdProbeQuery Q{env_of_query, gate_v, barrier_v, sensor_v, window};
+    for (int base = 0; base < nq; base += pc) {
+        const int cnt = nq - base < pc ? nq - base : pc;
+        qd_k_probe_gather<<<dim3(cnt), dim3(QD_PROBE_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params, h->state, h->pparams, h->pstate);
+        QD_HIP(hipGetLastError());
+        int rc = qd_probe_chunk(h, cnt, s);
+        if (rc) return rc;
+        if (raw_dst || image_dst || plohi_dst) {
+            qd_k_probe_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(env_of_query, base, h->B, h->C, h->P, h->pz, h->pplohi,
+                                                                                 raw_dst, image_dst, plohi_dst);
+            QD_HIP(hipGetLastError());
+        }
+    }
+    return QD_OK;
+}
+
+// numpy 'linear' percentile ranks of n values, as qd_k_percentile takes them
+static void qd_pct_ranks(long n, double q, long& ip, long& in, double& g) {
+    const double virt = (double)(n - 1) * q, prev = floor(virt);
+    ip = (long)prev; if (ip < 0) ip = 0; if (ip > n - 1) ip = n - 1;
+    in = ip + 1; if (in > n - 1) in = n - 1;
+    g = virt - prev;
+}
+
+// exact 0.5 / 99.5 percentiles of z[0..n) into plohi[0..1] (and plohi_dst when given), grid-wide radix select
+static int qd_launch_select(qd_handle* h, const double* z, long n, double* plohi, double* plohi_dst, hipStream_t s) {
+    long ip[2], in[2]; double g[2];
+    qd_pct_ranks(n, 0.5 / 100.0, ip[0], in[0], g[0]);
+    qd_pct_ranks(n, 99.5 / 100.0, ip[1], in[1], g[1]);
+    // 8 values per thread and pass keep the per-block histogram flush (<= 512 atomics) a small part of the pass
+    long blocks = (n + (long)QD_SEL_BLOCK * 8 - 1) / ((long)QD_SEL_BLOCK * 8);
+    const long full = (long)h->cus * 8;
+    if (blocks > full) blocks = full;
+    if (blocks < 1) blocks = 1;
+    qd_k_sel_init<<<dim3(1), dim3(512), 0, s>>>(h->sel, ip[0], ip[1]);
+    for (int pass = 7; pass >= 0; --pass) {
+        qd_k_sel_hist<<<dim3((unsigned)blocks), dim3(QD_SEL_BLOCK), 0, s>>>(z, n, pass, h->sel);
+        qd_k_sel_pick<<<dim3(1), dim3(128), 0, s>>>(pass, h->sel);
+    }
+    qd_k_sel_rank<<<dim3((unsigned)blocks), dim3(QD_SEL_BLOCK), 0, s>>>(z, n, h->sel);
+    qd_k_sel_finish<<<dim3(1), dim3(64), 0, s>>>(h->sel, ip[0], ip[1], in[0], in[1], g[0], g[1], plohi, plohi_dst);
+    QD_HIP(hipGetLastError());
+    return QD_OK;
+}
+
+static int qd_compose_scratch(qd_handle* h, size_t nq) {
+    const size_t need = nq * (size_t)h->P;
+    if (need > h->cz_cap) {
+        if (h->cz) { QD_HIP(hipFree(h->cz)); h->cz = nullptr; h->cz_cap = 0; }
+        QD_HIP(hipMalloc(&h->cz, sizeof(double) * need));
+        h->cz_cap = need;
+    }
+    if (nq > h->cplohi_cap) {
+        if (h->cplohi) { QD_HIP(hipFree(h->cplohi)); h->cplohi = nullptr; h->cplohi_cap = 0; }
+        QD_HIP(hipMalloc(&h->cplohi, sizeof(double) * 2 * nq));
+        h->cplohi_cap = nq;
+    }
+    if (!h->sel) QD_HIP(hipMalloc(&h->sel, sizeof(QdSelState)));
+    return QD_OK;
+}
+
+extern "C" int qd_probe_compose(qd_handle* h, const double* raw, int nx, int ny, int channel, int mode, float* composite_dst,
+                                double* plohi_dst, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    if (!raw || !composite_dst || nx < 1 || ny < 1) return qd_fail(h, QD_ERR_ARG, "qd_probe_compose: bad argument");
+    if (channel < 0 || channel >= h->C) return qd_fail(h, QD_ERR_ARG, "qd_probe_compose: channel out of range");
+    if (mode != QD_MAP_GLOBAL && mode != QD_MAP_PER_SCAN) return qd_fail(h, QD_ERR_ARG, "qd_probe_compose: unknown mode");
+    if ((long long)nx * ny > 65535) return qd_fail(h, QD_ERR_ARG, "qd_probe_compose: more than 65535 scans");
+    // (the select's histogram bins are 32-bit counters)
+    if ((long long)nx * ny * h->P >= (1ll << 32)) return qd_fail(h, QD_ERR_ARG, "qd_probe_compose: nx*ny*P must stay below 2^32");
+    hipStream_t s = (hipStream_t)stream;
+    QD_ON_DEVICE(h);
+    const long nq = (long)nx * ny, n = nq * h->P;
+    // (a grown scratch is freed only after the stream work that used the old one: hipFree waits for the device)
+    int rc = qd_compose_scratch(h, (size_t)nq);
+    if (rc) return rc;
+    {
+        long blocks = (n + 1023) / 1024;
+        if (blocks > (long)h->cus * 8) blocks = (long)h->cus * 8;
+        qd_k_map_extract<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(raw, nq, h->C, h->P, channel, h->cz);
+        QD_HIP(hipGetLastError());
+    }
+    const int per_scan = mode == QD_MAP_PER_SCAN ? 1 : 0;
+    if (per_scan) {
+        if ((long)h->P <= (long)QD_PCT_KPT * QD_PCT_BLOCK)
+            qd_k_percentile<true><<<dim3((unsigned)nq), dim3(QD_PCT_BLOCK), 0, s>>>(nullptr, (long)h->P, h->cz, h->cplohi);
+        else
+            qd_k_percentile<false><<<dim3((unsigned)nq), dim3(QD_PCT_BLOCK), 0, s>>>(nullptr, (long)h->P, h->cz, h->cplohi);
+        QD_HIP(hipGetLastError());
+    } else {
+        rc = qd_launch_select(h, h->cz, n, h->cplohi, plohi_dst, s);
+        if (rc) return rc;
+    }
+    qd_k_map_place<<<dim3((h->P + 255) / 256, (unsigned)nq), dim3(256), 0, s>>>(h->cz, nx, ny, h->R, per_scan, per_scan, h->cplohi,
+                                                                               composite_dst, plohi_dst);
+    QD_HIP(hipGetLastError());
+    return QD_OK;
+}
+
+// timing hook of scripts/probe_rate.py: the 0.5 / 99.5 percentiles of n caller-owned device doubles by the grid-wide select
+// (single_block 0) or by one qd_k_percentile block (single_block 1); out_dev [2]
+extern "C" int qd_time_select(qd_handle* h, const double* z_dev, long long n, int single_block, int iters, double* out_dev,
+                              float* mean_ms, void* stream) {
+    if (!h || !z_dev || n < 1 || n >= (1ll << 32) || iters < 1 || !out_dev || !mean_ms)
+        return qd_fail(h, QD_ERR_ARG, "qd_time_select: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    QD_ON_DEVICE(h);
+    if (!h->sel) QD_HIP(hipMalloc(&h->sel, sizeof(QdSelState)));
+    QdEventPair ev;
+    if (!ev.ok) return qd_fail(h, QD_ERR_HIP, "hipEventCreate");
+    QD_HIP(hipEventRecord(ev.a, s));
+    for (int i = 0; i < iters; ++i) {
+        if (single_block) {
+            qd_k_percentile<false><<<dim3(1), dim3(QD_PCT_BLOCK), 0, s>>>(nullptr, (long)n, z_dev, out_dev);
+            QD_HIP(hipGetLastError());
+        } else {
+            int rc = qd_launch_select(h, z_dev, (long)n, out_dev, nullptr, s);
+            if (rc) return rc;
+        }
+    }
+    QD_HIP(hipEventRecord(ev.b, s));
+    QD_HIP(hipEventSynchronize(ev.b));
+    float ms = 0.f;
+    QD_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+    *mean_ms = ms / iters;
     return QD_OK;
 }
 

@@ -19,6 +19,53 @@ from . import spaces
 from .device_model import load_yaml
 
 
+class ArrayFacade:
+    """`env.array` of the reference (a QarrayBaseClass) as far as its users outside step() need it: `model.cgd_full`,
+    `barrier_alpha`, `gate_ground_truth`, the scan geometry (`obs_voltage_min`, `obs_voltage_max`, `obs_image_size`,
+    `num_dots`, `num_barrier_voltages`) and the stateless `_get_obs` (qarray_base_class.py:171-229), rendered by the
+    backend's probe on the current device without touching the episode.  The window is
+    (obs_voltage_max - obs_voltage_min) / 2 around each gate voltage; it follows the device (`window_delta`) at every
+    reset and may be overwritten, as the reference's scripts do, but must stay symmetric: the kernels hold one
+    half-width per scan."""
+
+    def __init__(self, backend, num_dots, resolution):
+        self._b = backend
+        self.model = types.SimpleNamespace(cgd_full=None)
+        self.barrier_alpha = None
+        self.gate_ground_truth = None
+        self.num_dots = int(num_dots)
+        self.num_barrier_voltages = int(num_dots) - 1
+        self.obs_image_size = int(resolution)
+        self.obs_channels = int(num_dots) - 1
+        self.obs_voltage_min, self.obs_voltage_max = -1.0, 1.0            # qarray_base_class.py:38-39
+
+    def _get_obs(self, gate_voltages, barrier_voltages=None, sensor_voltage=None):
+        assert (
+            len(gate_voltages) == self.num_dots
+        ), f"Incorrect gate voltage shape, expected {self.num_dots}, got {len(gate_voltages)}"
+        if barrier_voltages is not None:
+            assert (
+                len(barrier_voltages) == self.num_dots - 1
+            ), f"Incorrect barrier voltage shape, expected {self.num_dots - 1}, got {len(barrier_voltages)}"
+        # qarray_base_class.py:142
+        assert barrier_voltages is not None, "Barrier voltages must be provided for models with barriers"
+        vmin, vmax = float(self.obs_voltage_min), float(self.obs_voltage_max)
+        if not abs(vmin + vmax) <= 1e-12 * max(abs(vmin), abs(vmax), 1.0):
+            raise ValueError(f"asymmetric scan window: obs_voltage_min = {vmin}, obs_voltage_max = {vmax}; the HIP kernels "
+                             "hold one half-width per scan, so obs_voltage_min must equal -obs_voltage_max")
+        out = self._b.probe([0], np.asarray(gate_voltages, np.float64)[None, :],
+                            np.asarray(barrier_voltages, np.float64)[None, :],
+                            sensor_voltage=None if sensor_voltage is None else float(sensor_voltage),
+                            window=(vmax - vmin) / 2)
+        raw = out["raw"]
+        raw = raw.detach().cpu().numpy() if hasattr(raw, "detach") else np.asarray(raw)
+        image = np.ascontiguousarray(raw[0].transpose(1, 2, 0))           # (R, R, C) float64, unnormalised
+        expected = (self.obs_image_size, self.obs_image_size, self.obs_channels)
+        if image.shape != expected:
+            raise ValueError(f"Image observation shape {image.shape} does not match expected {expected}")
+        return {"image": image, "obs_gate_voltages": gate_voltages, "obs_barrier_voltages": barrier_voltages}
+
+
 class QuantumDeviceEnv:
     metadata = {"render_modes": []}
 
@@ -70,8 +117,7 @@ class QuantumDeviceEnv:
                                           seed=seed)            # None: fresh entropy per env, as the reference's unseeded RNGs
         self._b = backend
         self.current_step = 0
-        self.array = types.SimpleNamespace(model=types.SimpleNamespace(cgd_full=None), barrier_alpha=None,
-                                           gate_ground_truth=None)
+        self.array = ArrayFacade(backend, N, R)
         self.reset()
 
     # -- helpers ---------------------------------------------------------------
@@ -106,6 +152,10 @@ class QuantumDeviceEnv:
         self.current_step = 0
         obs = self._b.reset(seed=seed)
         self._refresh_device_state()
+        ep, L = getattr(self._b, "last_episode", None), getattr(self._b, "L", None)
+        if ep is not None and L is not None:                    # a new device brings its own window (window_delta)
+            w = float(ep.params[0, L.scal + 2])
+            self.array.obs_voltage_min, self.array.obs_voltage_max = -w, w
         return self._observation(obs), self._get_info()
 
     def step(self, action, skip_obs=False):

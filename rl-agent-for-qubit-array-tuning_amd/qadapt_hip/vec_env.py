@@ -269,6 +269,66 @@ class VecQuantumDeviceEnv:
         fv[env_ids] = values; fl[env_ids] = log_vars
         return fv, fl
 
+    # ------------------------------------------------------------------ probe scans
+    def _to_dev(self, x, dtype, shape):
+        """numpy / torch / scalar -> contiguous device tensor of `dtype`, broadcast to `shape`; host data goes through
+        pinned memory so that the upload does not wait for the stream."""
+        if isinstance(x, torch.Tensor):
+            t = x.to(device=self.device, dtype=dtype)
+        else:
+            a = np.ascontiguousarray(np.asarray(x), dtype={torch.float64: np.float64, torch.int32: np.int32}[dtype])
+            t = torch.from_numpy(a.reshape(-1)).pin_memory().to(self.device, non_blocking=True).reshape(a.shape)
+        return t.broadcast_to(shape).contiguous()
+
+    def probe(self, env_ids, gate_voltages, barrier_voltages, sensor_voltage=None, window=None, normalised=False):
+        """Stateless scans (qd_probe): the reference's `array._get_obs(gate_voltages, barrier_voltages, sensor_voltage)`
+        for nq queries in one call, each on the device of env `env_ids[q]` with that env's current virtual gate matrix.
+        Nothing of the episodes changes (state, step counters, Kalman filters, last observation, noise streams), nq may
+        exceed the batch and one env may serve many queries.  Probes are deterministic: no noise stage runs.
+          env_ids           (nq,) ints, or one id for all queries
+          gate_voltages     (nq, N) virtual gate voltages; barrier_voltages (nq, N-1)
+          sensor_voltage    None (0.0, as the reference's default), a scalar or (nq,)
+          window            None (each env's own half-width), a scalar or (nq,) half-widths
+        numpy or torch inputs.  Returns device tensors {"raw": (nq, C, R, R) float64 unnormalised}, plus, with
+        normalised=True, {"image": (nq, R, R, C) float32 normalised per query, "plohi": (nq, 2) its percentiles}."""
+        N, C, R = self.N, self.C, self.R
+        gv = gate_voltages if isinstance(gate_voltages, torch.Tensor) else np.asarray(gate_voltages, np.float64)
+        gv = gv.reshape(-1, N)
+        nq = int(gv.shape[0])
+        gv = self._to_dev(gv, torch.float64, (nq, N))
+        bv = barrier_voltages if isinstance(barrier_voltages, torch.Tensor) else np.asarray(barrier_voltages, np.float64)
+        bv = self._to_dev(bv.reshape(-1, C), torch.float64, (nq, C))
+        ids = env_ids if isinstance(env_ids, torch.Tensor) else np.asarray(env_ids, np.int32)
+        ids = self._to_dev(ids.reshape(-1), torch.int32, (nq,))
+        sv = None if sensor_voltage is None else self._to_dev(sensor_voltage, torch.float64, (nq,))
+        wd = None if window is None else self._to_dev(window, torch.float64, (nq,))
+        out = {"raw": torch.empty((nq, C, R, R), dtype=torch.float64, device=self.device)}
+        if normalised:
+            out["image"] = torch.empty((nq, R, R, C), dtype=torch.float32, device=self.device)
+            out["plohi"] = torch.empty((nq, 2), dtype=torch.float64, device=self.device)
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())    # noqa: E731
+        rc = self._lib.qd_probe(self._h, ptr(ids), nq, ptr(gv), ptr(bv), ptr(sv), ptr(wd), ptr(out["raw"]),
+                                ptr(out.get("image")), ptr(out.get("plohi")), self._stream())
+        _lib.check(self._h, rc, "qd_probe")
+        return out
+
+    def compose(self, raw, nx, ny, channel=0, mode="global"):
+        """One channel of nx*ny probe signals `raw` (nx*ny, C, R, R; scan (i, j) at index i*ny + j) stitched into one
+        (ny*R, nx*R) float32 device image (qd_probe_compose).  mode "global": one exact 0.5 / 99.5 percentile pair over
+        the whole composite, scan (i, j) at row block j; "per_scan": every scan normalised by itself, row blocks flipped.
+        Returns (composite, plohi): plohi (2,) or (nx*ny, 2) float64."""
+        per = {"global": _lib.QD_MAP_GLOBAL, "per_scan": _lib.QD_MAP_PER_SCAN}[mode]
+        nq, R = int(nx) * int(ny), self.R
+        raw = raw.to(device=self.device, dtype=torch.float64).contiguous()
+        if raw.numel() != nq * self.C * R * R:
+            raise ValueError(f"raw holds {raw.numel()} values, {nx} x {ny} scans need {nq * self.C * R * R}")
+        comp = torch.empty((int(ny) * R, int(nx) * R), dtype=torch.float32, device=self.device)
+        plohi = torch.empty((nq, 2) if per else (2,), dtype=torch.float64, device=self.device)
+        rc = self._lib.qd_probe_compose(self._h, raw.data_ptr(), int(nx), int(ny), int(channel), per, comp.data_ptr(),
+                                        plohi.data_ptr(), self._stream())
+        _lib.check(self._h, rc, "qd_probe_compose")
+        return comp, plohi
+
     # ------------------------------------------------------------------ reset
     def load_new_devices(self, env_ids=None, seed=None):
         """Sample new random devices for the listed envs and upload their parameter / initial
