@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 import helpers as H
-from test_full_charge_space import full_states, full_hamiltonian, pixel_inputs
-import wide_scenes as WS
+import eig_cases as EC
 
 _LIB = None
 
@@ -57,30 +56,22 @@ def check(A, tag):
     return gap
 
 
-@pytest.mark.parametrize("s", list(range(33, 65)))
+@pytest.mark.parametrize("s", EC.WIDE_SIZES)
 def test_random_symmetric_blocks_of_every_wide_size(s):
-    rng = np.random.default_rng(1000 + s)
-    for scale in (1e-22, 1e-6, 1.0, 1e9, 1e44):
-        for rep in range(3):
-            A = rng.normal(size=(s, s)) * scale
-            check(A + A.T, (s, scale, rep))
+    for tag, A in EC.wide_random_family(s):
+        check(A, tag)
 
 
-@pytest.mark.parametrize("s", [33, 44, 51, 64])
+@pytest.mark.parametrize("s", EC.WIDE_HOP_SIZES)
 def test_hop_type_blocks_over_coupling_scales(s):
     """non-negative diagonal of O(1), non-positive couplings from 1e-22 to 1e44 on a connected sparse graph"""
-    from test_eig_solver_cpu import hop_block
-    rng = np.random.default_rng(7 + s)
-    for tscale in (1e-22, 1e-8, 1e-3, 1.0, 30.0, 1e6, 1e14, 1e30, 1e44):
-        for rep in range(3):
-            check(hop_block(rng, s, tscale), (s, tscale, rep))
+    for tag, A in EC.wide_hop_family(s):
+        check(A, tag)
 
 
 def test_small_sizes_run_too():
-    rng = np.random.default_rng(3)
-    for s in (2, 3, 4, 7, 13, 32):
-        A = rng.normal(size=(s, s))
-        check(A + A.T, s)
+    for s, A in EC.wide_small_family():
+        check(A, s)
 
 
 def test_size_outside_one_wave_is_an_error():
@@ -96,50 +87,22 @@ def test_real_sector_blocks(N, m):
     """Every sector of more than 32 states, out of the scenes the GPU test runs (near / far / random actions: tunnel
     couplings up to ~1e45 occur) -- the blocks as the structure kernel hands them over, diagonal relative to the
     pixel's lowest free energy."""
-    states = full_states(N, m)
-    Q = states.sum(axis=1)
-    wide = [np.flatnonzero(Q == q) for q in np.unique(Q) if (Q == q).sum() > 32]
-    assert wide
-    params, st = WS.scene(N, m)
     tcmax, n, resolved = 0.0, 0, 0
-    for e in range(len(params)):
-        dev = H.dev_view(N, params[e]); sv = H.state_view(N, st[e])
-        for ch in range(N - 1):
-            F, tc, _, _ = pixel_inputs(dev, sv, ch, 4, states, vc=dev.vc)
-            F = F - F.min(axis=1, keepdims=True)
-            Hm = full_hamiltonian(F, tc, states)
-            tcmax = max(tcmax, float(np.abs(tc).max()))
-            for p in range(len(F)):
-                for sel in wide:
-                    resolved += check(Hm[p][np.ix_(sel, sel)], (N, m, e, ch, p, len(sel))) > H.GAP_MIN
-                    n += 1
+    for tag, A, tcmax in EC.wide_sector_family(N, m):
+        resolved += check(A, tag) > H.GAP_MIN
+        n += 1
     print(f"({N},{m}): {n} sector blocks, {resolved} with a resolved ground vector, largest coupling {tcmax:.1e}")
     assert resolved > 0
 
 
 def test_nearly_degenerate_lowest_pair():
     """two weakly coupled copies of the same block: the two lowest levels split by ~1e-11 ||A|| and by ~1e-6 ||A||"""
-    rng = np.random.default_rng(11)
-    B = rng.normal(size=(24, 24)); B = B + B.T
-    for eps in (1e-11, 1e-6, 0.0):
-        A = np.zeros((48, 48))
-        A[:24, :24] = B; A[24:, 24:] = B
-        A[0, 24] = A[24, 0] = eps
-        check(A, ("degenerate", eps))
+    for tag, A in EC.wide_degenerate_family():
+        check(A, tag)
 
 
 def test_householder_tail_that_underflows():
     """couplings 60 decades apart inside one block: the reflector of a column whose tail is ~1e-160 of its head would
     need v0^2 ~ 1e-320 (the NaN case of the per-lane solver at tc ~ 2e45); the tail is dropped instead"""
-    rng = np.random.default_rng(12)
-    s = 40
-    A = np.diag(rng.uniform(0, 4, s))
-    for i in range(1, s):
-        A[i, i - 1] = A[i - 1, i] = -2e45 * rng.uniform(0.5, 2.0)
-    for i in range(2, s):
-        A[i, 0] = A[0, i] = -1e-115 * rng.uniform(0.5, 2.0)          # scaled: ~1e-160 next to x0 ~ 1
-    A[5, 3] = A[3, 5] = -1e-15
-    check(A, "underflow")
-    A2 = A / 2e45
-    A2[np.diag_indices(s)] = rng.uniform(0, 4, s)
-    check(A2, "underflow, scaled")
+    for tag, A in EC.wide_underflow_family():
+        check(A, tag)
