@@ -16,15 +16,17 @@
 // the other (its solve / select launches wait on memory most of the time).
 #define QD_MAX_LANES 4
 struct QdLane {
-    QdPixelRec* recs; unsigned char* slabs; unsigned* gtiles;
+    QdPixelRec* recs;                                  // [chunk][C][P] candidate records (validate mode: all B envs)
+    unsigned char* slabs;                              // scratch of the ground-state kernels: one slab per batch of ppb pixels in flight
+    unsigned* gtiles;                                  // [QD_GS_NBIN] tiles per size class of the launch in flight, then the tile lists
     unsigned char* wide;                               // the wide class's lists (full space with a sector above 32 states)
-    hipStream_t run, side, side2;
-    hipEvent_t ev_fork, ev_join, ev_join2, ev_done;
-};
+    hipStream_t run, side, side2;                      // the solve launches of the size classes run on three streams: the memory solver
+    hipEvent_t ev_fork, ev_join, ev_join2, ev_done;    // of the rare 13..32-state blocks is one long latency chain, and the short
+};                                                     // register-solver launches fill each other's tails
 
 struct qd_handle {
     qd_config cfg;
-    QdLane lanes[QD_MAX_LANES]; int nlanes;            // (the fields recs / slabs / gtiles / side / ev_* below are the lane in use)
+    QdLane lanes[QD_MAX_LANES]; int nlanes;
     hipEvent_t ev_start;
     int device;
     QdLayout L;
@@ -32,8 +34,6 @@ struct qd_handle {
     int chunk;
     double *params, *state, *zraw, *plohi, *occ, *eig;
     int* steps;
-    QdPixelRec* recs;
-    size_t recs_envs;                       // envs the recs buffer holds
     float *gimg, *pimg, *bimg, *volt;
     unsigned long long* tel; int tel_words;
     unsigned long long* tstats;             // tile-search [0..15] and eigen-solver [16..31] counters (validate mode)
@@ -42,35 +42,46 @@ struct qd_handle {
     int full_m;                             // > 0: the untruncated space with at most full_m carriers per dot (qd_fullspace.h)
     QdFullTab* ftab;                        //   its sector tables (device)
     int full_spl;                           //   states per lane of its structure kernel (2, 4, 8)
-    QdWide wide;                            //   the wide class (sectors of 33..64 states): capw > 0 when the handle has one
+    QdWide wide;                            //   the wide class (sectors of 33..64 states): capw > 0 when the handle has one; buf is the lane's
     int ppb;                                // pixels per ground-state batch (slab): QD_GS_PPB, or qd_full_ppb in the full space
-    unsigned char* slabs;                   // scratch of the ground-state kernels: one slab per batch of QD_GS_PPB pixels in flight
-    unsigned* gtiles;                       // [QD_GS_NBIN] tiles per size class of the launch in flight, then the tile lists
     int gs_chunk;                           // envs per ground-state launch (<= chunk)
-    size_t gs_batches;                      // slabs allocated = gs_chunk * C * batches per image
+    size_t gs_batches;                      // slabs a lane holds = gs_chunk * C * batches per image
     int cus;                                // compute units of the device
+    int solve_grid[QD_GS_NBIN];             // persistent blocks of qd_k_gs_solve per size class: as many as are resident at once
     double* stage[2]; size_t stage_cap;     // pinned staging ring of qd_load_episodes (doubles per slot), one event per slot:
     hipEvent_t stage_ev[2]; int stage_turn; //   the call returns without waiting for the stream
     bool stage_busy[2];
-    hipStream_t side, side2;                // the solve launches of the size classes run on three streams: the memory solver of the
-    hipEvent_t ev_fork, ev_join, ev_join2;  // rare 13..32-state blocks is one long latency chain, and the short register-solver
-                                            // launches fill each other's tails
     unsigned long long obs_serial;
     // probe scans (qd_probe): one launch chunk of parameter copies, state blocks, signals and percentiles, allocated by the
     // first probe; the composite's compact channel, per-scan percentiles and select state (qd_probe_compose) likewise
     double *pparams, *pstate, *pz, *pplohi;
     double *cz, *cplohi; size_t cz_cap, cplohi_cap;
     QdSelState* sel;
-    char err[512];
+    mutable char err[512];                  // (the launchers take the handle const and still report through it)
 };
 
-static void qd_use_lane(qd_handle* h, int k) {
-    const QdLane& ln = h->lanes[k];
-    h->recs = ln.recs; h->slabs = ln.slabs; h->gtiles = ln.gtiles; h->wide.buf = ln.wide;
-    h->side = ln.side; h->side2 = ln.side2; h->ev_fork = ln.ev_fork; h->ev_join = ln.ev_join; h->ev_join2 = ln.ev_join2;
+static bool qd_validate(const qd_handle* h) { return (h->cfg.flags & QD_FLAG_VALIDATE) != 0; }
+
+// The per-env device buffers the hot launchers work on, handed to them as an argument: qd_env_bufs() is the view of the
+// handle's own envs, qd_probe fills one for its probe blocks starting from a zeroed object, so whatever a probe does not
+// set reaches the kernels as nullptr / 0 and never as the envs' pointer.
+struct QdEnvBufs {
+    double *params, *state, *zraw, *plohi, *occ, *eig;
+    int noise_flags;
+    unsigned long long* tel; int tel_words;
+    unsigned long long serial;              // number of the observation being rendered (Philox counter word)
+};
+
+static QdEnvBufs qd_env_bufs(const qd_handle* h) {
+    QdEnvBufs b{};
+    b.params = h->params; b.state = h->state; b.zraw = h->zraw; b.plohi = h->plohi; b.occ = h->occ; b.eig = h->eig;
+    b.noise_flags = h->cfg.noise_flags;
+    b.tel = h->tel; b.tel_words = h->tel_words;
+    b.serial = h->obs_serial;
+    return b;
 }
 
-static int qd_fail(qd_handle* h, int code, const char* what, hipError_t e = hipSuccess) {
+static int qd_fail(const qd_handle* h, int code, const char* what, hipError_t e = hipSuccess) {
     if (h) {
         if (e != hipSuccess) snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
         else snprintf(h->err, sizeof(h->err), "%s", what);
@@ -126,6 +137,10 @@ struct QdEventPair {
         default: return qd_fail(h, QD_ERR_ARG, "kept-set size must be 8, 16 or 32");     \
     }
 
+// a boolean template argument: NAME_ is a constexpr bool inside the statement
+#define QD_DISPATCH_BOOL(COND_, NAME_, ...)                                       \
+    { if (COND_) { constexpr bool NAME_ = true; __VA_ARGS__; } else { constexpr bool NAME_ = false; __VA_ARGS__; } }
+
 extern "C" int qd_param_block_doubles(int n) { return (n < 2 || n > QD_MAXN) ? -1 : qd_layout(n).size; }
 extern "C" int qd_state_block_doubles(int n) { return (n < 2 || n > QD_MAXN) ? -1 : qd_layout(n).s_size; }
 extern "C" int qd_layout_query(int n, int32_t* out) {
@@ -148,6 +163,20 @@ static void qd_kalman_priors(const qd_config& cfg, int N, double* km, double* kv
             km[i * N + i + 2] = km[(i + 2) * N + i] = cfg.kalman_prior_mean_nnn;
             kv[i * N + i + 2] = kv[(i + 2) * N + i] = cfg.kalman_prior_variance;
         }
+}
+
+// persistent waves: per size class as many blocks of qd_k_gs_solve as are resident at once for its register budget
+template <bool VAL, int BIN = 0>
+static hipError_t qd_solve_grids(int cus, int* grid) {
+    if constexpr (BIN < QD_GS_NBIN) {
+        int n = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, qd_k_gs_solve<BIN, VAL>, 256, 0);
+        if (e != hipSuccess) return e;
+        grid[BIN] = cus * (n < 1 ? 1 : n);
+        return qd_solve_grids<VAL, BIN + 1>(cus, grid);
+    } else {
+        return hipSuccess;
+    }
 }
 
 extern "C" const char* qd_last_error(const qd_handle* h) { return h ? h->err : "null handle"; }
@@ -226,13 +255,14 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
         if (gs_chunk < 1) return qd_fail(h, QD_ERR_ARG, "resolution too large for the tile descriptors");
         if (!val && chunk > gs_chunk) chunk = gs_chunk;
     }
-    h->chunk = chunk; h->recs_envs = (size_t)chunk;
+    h->chunk = chunk;
     h->gs_chunk = gs_chunk; h->gs_batches = (size_t)gs_chunk * batches_per_env;
     {
         hipDeviceProp_t prop;
         QD_HIP(hipGetDeviceProperties(&prop, device));
         h->cus = prop.multiProcessorCount;
     }
+    QD_HIP(val ? qd_solve_grids<true>(h->cus, h->solve_grid) : qd_solve_grids<false>(h->cus, h->solve_grid));
     QD_HIP(hipMalloc(&h->params, sizeof(double) * (size_t)h->B * h->L.size));
     QD_HIP(hipMalloc(&h->state, sizeof(double) * (size_t)h->B * h->L.s_size));
     QD_HIP(hipMalloc(&h->steps, sizeof(int) * (size_t)h->B));
@@ -241,7 +271,7 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
     QD_HIP(hipEventCreateWithFlags(&h->ev_start, hipEventDisableTiming));
     for (int k = 0; k < h->nlanes; ++k) {
         QdLane& ln = h->lanes[k];
-        QD_HIP(hipMalloc(&ln.recs, per_env_rec * h->recs_envs));
+        QD_HIP(hipMalloc(&ln.recs, per_env_rec * (size_t)h->chunk));
         QD_HIP(hipStreamCreateWithFlags(&ln.run, hipStreamNonBlocking));
         QD_HIP(hipStreamCreateWithFlags(&ln.side, hipStreamNonBlocking));
         QD_HIP(hipStreamCreateWithFlags(&ln.side2, hipStreamNonBlocking));
@@ -265,7 +295,6 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
         QD_HIP(hipMalloc(&h->lanes[k].gtiles, sizeof(unsigned) * (16 + qd_gs_tile_off(QD_GS_NBIN, h->gs_batches))));
         if (h->wide.capw) QD_HIP(hipMalloc(&h->lanes[k].wide, h->gs_batches * qd_wide_bytes(h->wide.capw)));
     }
-    qd_use_lane(h, 0);
     if (cfg->flags & QD_FLAG_VALIDATE) {
         QD_HIP(hipMalloc(&h->tstats, sizeof(unsigned long long) * 32));
         QD_HIP(hipMemset(h->tstats, 0, sizeof(unsigned long long) * 32));
@@ -418,140 +447,136 @@ static int qd_cand_blocks(int R) {
     return (tiles + per_block - 1) / per_block;
 }
 
-static QdNoiseCfg qd_noise_cfg(const qd_handle* h) {
+static QdNoiseCfg qd_noise_cfg(const qd_handle* h, const QdEnvBufs& b) {
     QdNoiseCfg nz;
-    nz.flags = h->cfg.noise_flags;
+    nz.flags = b.noise_flags;
     nz.seed = (uint32_t)(h->cfg.rng_seed ^ (h->cfg.rng_seed >> 32));
     nz.env_off = (uint32_t)h->cfg.env_id_offset;
-    nz.ser_lo = (uint32_t)h->obs_serial; nz.ser_hi = (uint32_t)(h->obs_serial >> 32);
-    nz.tel = h->tel; nz.tel_words = h->tel_words;
+    nz.ser_lo = (uint32_t)b.serial; nz.ser_hi = (uint32_t)(b.serial >> 32);
+    nz.tel = b.tel; nz.tel_words = b.tel_words;
     return nz;
 }
 
+// The stages of one launch chunk, in pipeline order; the timing hooks launch them one by one.
+enum {
+    QD_ST_TILE = 1, QD_ST_REDO = 2, QD_ST_STRUCTURE = 4, QD_ST_SOLVE = 8, QD_ST_SELECT = 16,
+    QD_ST_SEARCH = QD_ST_TILE | QD_ST_REDO,
+    QD_ST_GROUND = QD_ST_STRUCTURE | QD_ST_SOLVE | QD_ST_SELECT,
+    QD_ST_ALL = QD_ST_SEARCH | QD_ST_GROUND
+};
+
+// the stages this handle has: the full space has no candidate search, and without the tile search the redo pass is the
+// whole (per-pixel) search
+static int qd_stages(const qd_handle* h) {
+    return h->full_m ? QD_ST_GROUND : (h->tile_search ? QD_ST_ALL : QD_ST_ALL & ~QD_ST_TILE);
+}
+
 template <int BIN>
-static hipError_t qd_launch_solve(qd_handle* h, hipStream_t s) {   // s: the stream this size class runs on
-    // persistent waves: as many blocks as are resident at once for this size class's register budget
-    static int per_cu[2] = {0, 0};
-    const int v = h->eig ? 1 : 0;
-    if (!per_cu[v]) {
-        int n = 0;
-        const hipError_t e = v ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, qd_k_gs_solve<BIN, true>, 256, 0)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, qd_k_gs_solve<BIN, false>, 256, 0);
-        if (e != hipSuccess) return e;
-        per_cu[v] = n < 1 ? 1 : n;
-    }
-    const dim3 grid((unsigned)(h->cus * per_cu[v]));
-    unsigned* tilelist = h->gtiles + 16;
-    if (h->eig) qd_k_gs_solve<BIN, true><<<grid, dim3(256), 0, s>>>(h->slabs, h->gtiles, tilelist, h->gs_batches, h->tstats);
-    else        qd_k_gs_solve<BIN, false><<<grid, dim3(256), 0, s>>>(h->slabs, h->gtiles, tilelist, h->gs_batches, nullptr);
+static hipError_t qd_launch_solve(const qd_handle* h, const QdLane& ln, hipStream_t s) {   // s: the stream this size class runs on
+    const dim3 grid((unsigned)h->solve_grid[BIN]);
+    QD_DISPATCH_BOOL(qd_validate(h), VAL,
+                     qd_k_gs_solve<BIN, VAL><<<grid, dim3(256), 0, s>>>(ln.slabs, ln.gtiles, ln.gtiles + 16, h->gs_batches, h->tstats));
     return hipGetLastError();
 }
 
-// a11-a13 + a15 for the envs at list positions [base, base + cnt): structure -> solve per size class -> select, in
-// launches of at most gs_chunk envs (the slabs in flight)
-static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int cnt, hipStream_t s, int stages = 7 /*1 structure, 2 solve, 4 select*/) {
+// a11-a13 + a15 for the envs at list positions [base, base + cnt): structure -> solve per size class -> select (those of
+// them in `st`), in launches of at most gs_chunk envs (the slabs in flight)
+static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, const int32_t* env_ids, int base, int cnt,
+                            hipStream_t s, int st) {
     const int nb = (h->P + h->ppb - 1) / h->ppb;
-    unsigned* tilelist = h->gtiles + 16;
+    unsigned* tilelist = ln.gtiles + 16;
+    const bool val = qd_validate(h);
+    QdWide wide = h->wide; wide.buf = ln.wide;
     // records: product mode keeps one launch chunk (slot = position in the chunk), validate mode all envs (position in the list)
-    const int rec0 = (h->cfg.flags & QD_FLAG_VALIDATE) ? base : 0;
+    const int rec0 = val ? base : 0;
     for (int off = 0; off < cnt; off += h->gs_chunk) {
         const int n = cnt - off < h->gs_chunk ? cnt - off : h->gs_chunk;
         const QdGsGeom g{n, h->C, h->P, nb};
         const unsigned batches = (unsigned)((size_t)n * h->C * nb);
-        if (stages & 1) {
-        QD_HIP(hipMemsetAsync(h->gtiles, 0, sizeof(unsigned) * 16, s));
-        // (small launches: 16 waves per batch instead of 4, see the kernel)
-#define QD_LAUNCH_STRUCTURE(VAL_, WPB_)                                                                                          \
-        QD_DISPATCH_N(h->N, qd_k_gs_structure<NN, VAL_, WPB_><<<dim3(batches), dim3(64 * WPB_), 0, s>>>(env_ids, base + off, rec0 + off, g, h->R, \
-                      h->params, h->recs, h->state, h->cfg.noise_flags, h->slabs, h->gtiles, tilelist, h->gs_batches, h->kept))
-        const bool small = batches < (unsigned)h->cus;
-        if (h->full_m) {
-            // (shapes without a sector above 32 states have M <= 128: the kernel without the wide class, 2 states per lane)
-#define QD_LAUNCH_FULL(VAL_, SPL_, WIDE_)                                                                                         \
-            QD_DISPATCH_N(h->N, qd_k_full_structure<NN, VAL_, SPL_, WIDE_><<<dim3(batches), dim3(64 * QdFullWpb<SPL_>::v), 0, s>>>(env_ids,    \
-                          base + off, rec0 + off, g, h->ppb, h->R, h->params, h->state, h->cfg.noise_flags, h->ftab, h->recs, h->slabs,   \
-                          h->gtiles, tilelist, h->gs_batches, h->wide))
-#define QD_LAUNCH_FULL_V(VAL_)                                                                                                    \
-            do {                                                                                                                  \
-                if (!h->wide.capw && h->full_spl == 2) { QD_LAUNCH_FULL(VAL_, 2, false); }                                        \
-                else if (h->full_spl == 2) { QD_LAUNCH_FULL(VAL_, 2, true); }                                                     \
-                else if (h->full_spl == 4) { QD_LAUNCH_FULL(VAL_, 4, true); }                                                     \
-                else { QD_LAUNCH_FULL(VAL_, 8, true); }                                                                           \
-            } while (0)
-            if (h->eig) QD_LAUNCH_FULL_V(true); else QD_LAUNCH_FULL_V(false);
-#undef QD_LAUNCH_FULL_V
-#undef QD_LAUNCH_FULL
-        } else if (h->eig) { if (small) { QD_LAUNCH_STRUCTURE(true, 16); } else { QD_LAUNCH_STRUCTURE(true, 4); } }
-        else        { if (small) { QD_LAUNCH_STRUCTURE(false, 16); } else { QD_LAUNCH_STRUCTURE(false, 4); } }
-#undef QD_LAUNCH_STRUCTURE
-        QD_HIP(hipGetLastError());
-        }
-        if (stages & 2) {
-        // A hop component lies in one total-charge sector of the kept states: at most 4 states for 2 dots (16 candidates), 12 for
-        // 3 dots; the launches of size classes that cannot occur are skipped.  From 4 dots on the memory solver of the rare
-        // 13..32-state blocks (one long latency chain: 0.4 ms for 8 envs, 0.9 ms for 180) and the wide register solvers go on
-        // two side streams, whatever the batch.  Nor can a component hold more than the K kept states (K = 1: no task at all).
-        // In the full space a component is at most a sector.
-        int max_bin = h->N == 2 ? qd_gs_bin(4) : (h->N == 3 ? qd_gs_bin(12) : QD_GS_NBIN - 1);
-        if (h->full_m) {
-            int M = 0, maxsec = 0;
-            qd_full_sizes(h->N, h->full_m, M, maxsec);
-            max_bin = qd_gs_bin(maxsec < QD_K ? maxsec : QD_K);
-        } else if (h->kept < 2) max_bin = -1;
-        else if (qd_gs_bin(h->kept) < max_bin) max_bin = qd_gs_bin(h->kept);
-        const bool forked = max_bin >= 9;            // (8-dot, 4 envs: 1 760 -> 2 520 env-steps/s, 8 envs 3 390 -> 3 590; 2 and 3 dots have no memory-solver launch to hide)
-        hipStream_t s9 = forked ? h->side : s, s48 = forked ? h->side2 : s;
-        if (forked) {
-            QD_HIP(hipEventRecord(h->ev_fork, s));
-            QD_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-            QD_HIP(hipStreamWaitEvent(h->side2, h->ev_fork, 0));
-        }
-        if (h->wide.capw) {                            // the wide class first: its tasks are the longest
-            const size_t slots = (size_t)batches * h->wide.capw, full = (size_t)h->cus * 4;
-            const dim3 wgrid((unsigned)(slots < full ? slots : full));
-            if (h->eig) qd_k_full_solve_wide<true><<<wgrid, dim3(64), 0, s>>>(h->slabs, h->wide, batches, h->tstats);
-            else        qd_k_full_solve_wide<false><<<wgrid, dim3(64), 0, s>>>(h->slabs, h->wide, batches, nullptr);
+        if (st & QD_ST_STRUCTURE) {
+            QD_HIP(hipMemsetAsync(ln.gtiles, 0, sizeof(unsigned) * 16, s));
+            if (h->full_m) {
+                // (shapes without a sector above 32 states have M <= 128: the kernel without the wide class, 2 states per lane)
+#define QD_DISPATCH_FULL(...)                                                                                  \
+                if (!wide.capw && h->full_spl == 2) { constexpr int SPL = 2; constexpr bool WIDE = false; __VA_ARGS__; }  \
+                else if (h->full_spl == 2) { constexpr int SPL = 2; constexpr bool WIDE = true; __VA_ARGS__; }            \
+                else if (h->full_spl == 4) { constexpr int SPL = 4; constexpr bool WIDE = true; __VA_ARGS__; }            \
+                else { constexpr int SPL = 8; constexpr bool WIDE = true; __VA_ARGS__; }
+                QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_FULL(QD_DISPATCH_N(h->N,
+                    qd_k_full_structure<NN, VAL, SPL, WIDE><<<dim3(batches), dim3(64 * QdFullWpb<SPL>::v), 0, s>>>(env_ids, base + off,
+                        rec0 + off, g, h->ppb, h->R, b.params, b.state, b.noise_flags, h->ftab, ln.recs, ln.slabs, ln.gtiles, tilelist,
+                        h->gs_batches, wide))));
+#undef QD_DISPATCH_FULL
+            } else {
+                // (small launches: 16 waves per batch instead of 4, see the kernel)
+                QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_BOOL(batches < (unsigned)h->cus, SMALL, QD_DISPATCH_N(h->N,
+                    qd_k_gs_structure<NN, VAL, (SMALL ? 16 : 4)><<<dim3(batches), dim3(64 * (SMALL ? 16 : 4)), 0, s>>>(env_ids, base + off,
+                        rec0 + off, g, h->R, b.params, ln.recs, b.state, b.noise_flags, ln.slabs, ln.gtiles, tilelist, h->gs_batches,
+                        h->kept))));
+            }
             QD_HIP(hipGetLastError());
         }
-        if (max_bin >= 9) QD_HIP(qd_launch_solve<9>(h, s9));
-        if (forked) QD_HIP(hipEventRecord(h->ev_join, h->side));
-        if (max_bin >= 8) QD_HIP(qd_launch_solve<8>(h, s48));
-        if (max_bin >= 7) QD_HIP(qd_launch_solve<7>(h, s48));
-        if (max_bin >= 6) QD_HIP(qd_launch_solve<6>(h, s48));
-        if (max_bin >= 5) QD_HIP(qd_launch_solve<5>(h, s48));
-        if (max_bin >= 4) QD_HIP(qd_launch_solve<4>(h, s48));
-        if (forked) QD_HIP(hipEventRecord(h->ev_join2, h->side2));
-        if (max_bin >= 0) QD_HIP(qd_launch_solve<0>(h, s));
-        if (max_bin >= 1) QD_HIP(qd_launch_solve<1>(h, s));
-        if (max_bin >= 2) QD_HIP(qd_launch_solve<2>(h, s));
-        if (max_bin >= 3) QD_HIP(qd_launch_solve<3>(h, s));
-        if (forked) {
-            QD_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
-            QD_HIP(hipStreamWaitEvent(s, h->ev_join2, 0));
+        if (st & QD_ST_SOLVE) {
+            // A hop component lies in one total-charge sector of the kept states: at most 4 states for 2 dots (16 candidates), 12 for
+            // 3 dots; the launches of size classes that cannot occur are skipped.  From 4 dots on the memory solver of the rare
+            // 13..32-state blocks (one long latency chain: 0.4 ms for 8 envs, 0.9 ms for 180) and the wide register solvers go on
+            // two side streams, whatever the batch.  Nor can a component hold more than the K kept states (K = 1: no task at all).
+            // In the full space a component is at most a sector.
+            int max_bin = h->N == 2 ? qd_gs_bin(4) : (h->N == 3 ? qd_gs_bin(12) : QD_GS_NBIN - 1);
+            if (h->full_m) {
+                int M = 0, maxsec = 0;
+                qd_full_sizes(h->N, h->full_m, M, maxsec);
+                max_bin = qd_gs_bin(maxsec < QD_K ? maxsec : QD_K);
+            } else if (h->kept < 2) max_bin = -1;
+            else if (qd_gs_bin(h->kept) < max_bin) max_bin = qd_gs_bin(h->kept);
+            const bool forked = max_bin >= 9;            // (8-dot, 4 envs: 1 760 -> 2 520 env-steps/s, 8 envs 3 390 -> 3 590; 2 and 3 dots have no memory-solver launch to hide)
+            hipStream_t s9 = forked ? ln.side : s, s48 = forked ? ln.side2 : s;
+            if (forked) {
+                QD_HIP(hipEventRecord(ln.ev_fork, s));
+                QD_HIP(hipStreamWaitEvent(ln.side, ln.ev_fork, 0));
+                QD_HIP(hipStreamWaitEvent(ln.side2, ln.ev_fork, 0));
+            }
+            if (wide.capw) {                               // the wide class first: its tasks are the longest
+                const size_t slots = (size_t)batches * wide.capw, full = (size_t)h->cus * 4;
+                const dim3 wgrid((unsigned)(slots < full ? slots : full));
+                QD_DISPATCH_BOOL(val, VAL, qd_k_full_solve_wide<VAL><<<wgrid, dim3(64), 0, s>>>(ln.slabs, wide, batches, h->tstats));
+                QD_HIP(hipGetLastError());
+            }
+            if (max_bin >= 9) QD_HIP(qd_launch_solve<9>(h, ln, s9));
+            if (forked) QD_HIP(hipEventRecord(ln.ev_join, ln.side));
+            if (max_bin >= 8) QD_HIP(qd_launch_solve<8>(h, ln, s48));
+            if (max_bin >= 7) QD_HIP(qd_launch_solve<7>(h, ln, s48));
+            if (max_bin >= 6) QD_HIP(qd_launch_solve<6>(h, ln, s48));
+            if (max_bin >= 5) QD_HIP(qd_launch_solve<5>(h, ln, s48));
+            if (max_bin >= 4) QD_HIP(qd_launch_solve<4>(h, ln, s48));
+            if (forked) QD_HIP(hipEventRecord(ln.ev_join2, ln.side2));
+            if (max_bin >= 0) QD_HIP(qd_launch_solve<0>(h, ln, s));
+            if (max_bin >= 1) QD_HIP(qd_launch_solve<1>(h, ln, s));
+            if (max_bin >= 2) QD_HIP(qd_launch_solve<2>(h, ln, s));
+            if (max_bin >= 3) QD_HIP(qd_launch_solve<3>(h, ln, s));
+            if (forked) {
+                QD_HIP(hipStreamWaitEvent(s, ln.ev_join, 0));
+                QD_HIP(hipStreamWaitEvent(s, ln.ev_join2, 0));
+            }
         }
-        }
-        if (stages & 4) {
-        if (h->full_m) {
-            const unsigned blk = (unsigned)((h->ppb + 63) / 64 * 64);
-#define QD_LAUNCH_FSEL(VAL_, WIDE_, EIG_)                                                                                          \
-            QD_DISPATCH_N(h->N, qd_k_full_select<NN, VAL_, WIDE_><<<dim3(batches), dim3(blk), 0, s>>>(env_ids, base + off, rec0 + off, g,   \
-                          h->ppb, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, EIG_, h->ftab, h->slabs, h->wide))
-            if (h->eig) { if (h->wide.capw) { QD_LAUNCH_FSEL(true, true, h->eig); } else { QD_LAUNCH_FSEL(true, false, h->eig); } }
-            else { if (h->wide.capw) { QD_LAUNCH_FSEL(false, true, nullptr); } else { QD_LAUNCH_FSEL(false, false, nullptr); } }
-#undef QD_LAUNCH_FSEL
-        } else if (h->eig) {
-            QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc, qd_k_gs_select<NN, true, KK><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids,
-                          base + off, rec0 + off, g, h->R, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, h->eig, h->slabs)));
-        } else {
-            QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc, qd_k_gs_select<NN, false, KK><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids,
-                          base + off, rec0 + off, g, h->R, h->params, h->recs, h->zraw, h->occ, h->state, h->cfg.noise_flags, nullptr, h->slabs)));
-        }
-        QD_HIP(hipGetLastError());
+        if (st & QD_ST_SELECT) {
+            if (h->full_m) {
+                const unsigned blk = (unsigned)((h->ppb + 63) / 64 * 64);
+                QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_BOOL(wide.capw != 0, WIDE, QD_DISPATCH_N(h->N,
+                    qd_k_full_select<NN, VAL, WIDE><<<dim3(batches), dim3(blk), 0, s>>>(env_ids, base + off, rec0 + off, g, h->ppb,
+                        b.params, ln.recs, b.zraw, b.occ, b.state, b.noise_flags, b.eig, h->ftab, ln.slabs, wide))));
+            } else {
+                QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
+                    qd_k_gs_select<NN, VAL, KK><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids, base + off, rec0 + off, g, h->R,
+                        b.params, ln.recs, b.zraw, b.occ, b.state, b.noise_flags, b.eig, ln.slabs))));
+            }
+            QD_HIP(hipGetLastError());
         }
     }
     return QD_OK;
 }
 
+// (not QD_DISPATCH_N: qd_k_tile exists from 4 dots on)
 #define QD_DISPATCH_TILE(N_, ...)                                                 \
     switch (N_) {                                                                 \
         case 4: { constexpr int NN = 4; __VA_ARGS__; } break;                            \
@@ -562,37 +587,44 @@ static int qd_launch_ground(qd_handle* h, const int32_t* env_ids, int base, int 
         default: return qd_fail(h, QD_ERR_ARG, "tile kernels need n_dot in 4..8");      \
     }
 
-// a5-a13 for `cnt` envs starting at list position `base`.
-//   tile_search 1: tile search + exact redo pass, then the ground-state kernels;  0: per-pixel search, then the ground-state kernels.
-static int qd_launch_csd(qd_handle* h, const int32_t* env_ids, int base, int cnt, hipStream_t s, int what /*1 search, 2 ground, 3 both*/,
-                         int parts = 0 /*timing hooks only: 1 tile search alone, 2 redo pass alone; 4/8/16 structure / solve / select alone*/) {
-    const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
+// a5-a13 for `cnt` envs starting at list position `base`: those of the stages in `st` that the handle has (qd_stages) --
+// tile search + exact redo pass or the per-pixel search alone, then the ground-state kernels.
+static int qd_launch_csd(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, const int32_t* env_ids, int base, int cnt,
+                         hipStream_t s, int st) {
+    st &= qd_stages(h);
     // validate mode keeps the reference order; K < KC needs it too, the ground-state stage takes the first K
-    const int sorted = ((h->cfg.flags & QD_FLAG_VALIDATE) || h->kept != h->kc) ? 1 : 0;
-    dim3 g1(qd_cand_blocks(h->R), h->C, cnt);
-    const int tiles = ((h->R + 7) / 8) * ((h->R + 7) / 8);
-    dim3 gt(tiles, h->C, cnt);
-    if (parts & 28) return qd_launch_ground(h, env_ids, base, cnt, s, (parts >> 2) & 7);
-    if (h->full_m) return (what & 2) ? qd_launch_ground(h, env_ids, base, cnt, s) : QD_OK;   // no candidate stage
-    if (what & 1) {
-        if (h->tile_search == 1 && parts != 2) {
-            QD_DISPATCH_TILE(h->N, QD_DISPATCH_KC(h->kc, qd_k_tile<NN, KK><<<gt, dim3(64), 0, s>>>(env_ids, base, h->R, h->params, h->state,
-                             h->recs, sorted, h->cfg.noise_flags, h->tstats)));
-            QD_HIP(hipGetLastError());
-        }
-        if (parts != 1) {
-            if (h->tile_search) {
-                QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc, qd_k_candidates<NN, true, KK><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R,
-                                                                                  h->params, h->state, h->recs, sorted, h->cfg.noise_flags)));
-            } else {
-                QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc, qd_k_candidates<NN, false, KK><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R,
-                                                                                   h->params, h->state, h->recs, sorted, h->cfg.noise_flags)));
-            }
-            QD_HIP(hipGetLastError());
-        }
+    const int sorted = (qd_validate(h) || h->kept != h->kc) ? 1 : 0;
+    if (st & QD_ST_TILE) {
+        const int tiles = ((h->R + 7) / 8) * ((h->R + 7) / 8);
+        QD_DISPATCH_TILE(h->N, QD_DISPATCH_KC(h->kc, qd_k_tile<NN, KK><<<dim3(tiles, h->C, cnt), dim3(64), 0, s>>>(env_ids, base, h->R,
+                         b.params, b.state, ln.recs, sorted, b.noise_flags, h->tstats)));
+        QD_HIP(hipGetLastError());
     }
-    if (what & 2) return qd_launch_ground(h, env_ids, base, cnt, s);
+    if (st & QD_ST_REDO) {
+        const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
+        const dim3 g1(qd_cand_blocks(h->R), h->C, cnt);
+        QD_DISPATCH_BOOL(h->tile_search != 0, TILED, QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
+            qd_k_candidates<NN, TILED, KK><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R, b.params, b.state, ln.recs, sorted,
+                                                                              b.noise_flags))));
+        QD_HIP(hipGetLastError());
+    }
+    if (st & QD_ST_GROUND) return qd_launch_ground(h, b, ln, env_ids, base, cnt, s, st);
     return QD_OK;
+}
+
+// a16 on the signal of `n` envs (their list `ids`, or 0..n-1), in place
+static int qd_launch_sensor(const qd_handle* h, const QdEnvBufs& b, const int32_t* ids, int n, hipStream_t s) {
+    const dim3 g3((h->P + 255) / 256, h->C, n);
+    QD_DISPATCH_N(h->N, qd_k_sensor<NN><<<g3, dim3(256), 0, s>>>(ids, h->R, b.params, b.state, b.zraw, qd_noise_cfg(h, b)));
+    QD_HIP(hipGetLastError());
+    return QD_OK;
+}
+
+// a17: one block per row of `count` values; the keys stay in registers where a block can hold them
+// (the caller checks hipGetLastError)
+static void qd_launch_percentile(const int32_t* ids, unsigned blocks, long count, const double* z, double* plohi, hipStream_t s) {
+    QD_DISPATCH_BOOL(count <= (long)QD_PCT_KPT * QD_PCT_BLOCK, CACHED,
+                     qd_k_percentile<CACHED><<<dim3(blocks), dim3(QD_PCT_BLOCK), 0, s>>>(ids, count, z, plohi));
 }
 
 extern "C" int qd_observe(qd_handle* h, const int32_t* env_ids, int n, void* stream) {
@@ -604,16 +636,16 @@ extern "C" int qd_observe(qd_handle* h, const int32_t* env_ids, int n, void* str
     if (n > h->B) return qd_fail(h, QD_ERR_ARG, "qd_observe: n > batch");
     const QdLayout& L = h->L;
     h->obs_serial++;
-    if (h->cfg.noise_flags & QD_NOISE_SENSOR) {
+    const QdEnvBufs b = qd_env_bufs(h);
+    if (b.noise_flags & QD_NOISE_SENSOR) {
         const int nt = n * h->C;
-        qd_k_telegraph<<<dim3((nt + 63) / 64), dim3(64), 0, s>>>(env_ids, n, h->C, h->P, L.size, L.noise, h->params, h->tel, qd_noise_cfg(h));
+        qd_k_telegraph<<<dim3((nt + 63) / 64), dim3(64), 0, s>>>(env_ids, n, h->C, h->P, L.size, L.noise, b.params, b.tel, qd_noise_cfg(h, b));
         QD_HIP(hipGetLastError());
     }
     if (h->nlanes == 1 || n <= h->chunk) {
-        qd_use_lane(h, 0);
         for (int base = 0; base < n; base += h->chunk) {
             const int cnt = (n - base < h->chunk) ? n - base : h->chunk;
-            int rc = qd_launch_csd(h, env_ids, base, cnt, s, 3);
+            int rc = qd_launch_csd(h, b, h->lanes[0], env_ids, base, cnt, s, QD_ST_ALL);
             if (rc) return rc;
         }
     } else {
@@ -625,31 +657,22 @@ extern "C" int qd_observe(qd_handle* h, const int32_t* env_ids, int n, void* str
         int i = 0;
         for (int base = 0; base < n; base += h->chunk, ++i) {
             const int cnt = (n - base < h->chunk) ? n - base : h->chunk;
-            const int ln = i % h->nlanes;
-            qd_use_lane(h, ln);
-            int rc = qd_launch_csd(h, env_ids, base, cnt, h->lanes[ln].run, 3);
-            if (rc) { qd_use_lane(h, 0); return rc; }
+            const QdLane& ln = h->lanes[i % h->nlanes];
+            int rc = qd_launch_csd(h, b, ln, env_ids, base, cnt, ln.run, QD_ST_ALL);
+            if (rc) return rc;
         }
-        qd_use_lane(h, 0);
         for (int k = 0; k < h->nlanes; ++k) {
             QD_HIP(hipEventRecord(h->lanes[k].ev_done, h->lanes[k].run));
             QD_HIP(hipStreamWaitEvent(s, h->lanes[k].ev_done, 0));
         }
     }
-    if (h->cfg.noise_flags & QD_NOISE_LATCH) {
+    if (b.noise_flags & QD_NOISE_LATCH) {
         const int nt = n * h->C;
-        QD_DISPATCH_N(h->N, qd_k_latch<NN><<<dim3((nt + 63) / 64), dim3(64), 0, s>>>(env_ids, n, h->R, h->params, h->state, h->occ, h->zraw, qd_noise_cfg(h)));
+        QD_DISPATCH_N(h->N, qd_k_latch<NN><<<dim3((nt + 63) / 64), dim3(64), 0, s>>>(env_ids, n, h->R, b.params, b.state, b.occ, b.zraw, qd_noise_cfg(h, b)));
         QD_HIP(hipGetLastError());
     }
-    {
-        dim3 g3((h->P + 255) / 256, h->C, n);
-        QD_DISPATCH_N(h->N, qd_k_sensor<NN><<<g3, dim3(256), 0, s>>>(env_ids, h->R, h->params, h->state, h->zraw, qd_noise_cfg(h)));
-        QD_HIP(hipGetLastError());
-    }
-    if ((long)h->C * h->P <= (long)QD_PCT_KPT * QD_PCT_BLOCK)
-        qd_k_percentile<true><<<dim3(n), dim3(QD_PCT_BLOCK), 0, s>>>(env_ids, (long)h->C * h->P, h->zraw, h->plohi);
-    else
-        qd_k_percentile<false><<<dim3(n), dim3(QD_PCT_BLOCK), 0, s>>>(env_ids, (long)h->C * h->P, h->zraw, h->plohi);
+    if (int rc = qd_launch_sensor(h, b, env_ids, n, s)) return rc;
+    qd_launch_percentile(env_ids, (unsigned)n, (long)h->C * h->P, b.zraw, b.plohi, s);
     QD_HIP(hipGetLastError());
     if (h->gimg || h->pimg || h->bimg || h->volt) {
         dim3 g4((h->P + 255) / 256, n);
@@ -713,43 +736,6 @@ extern "C" int qd_snapshot(qd_handle* h, const int32_t* env_ids, int n, float* g
     return QD_OK;
 }
 
-// The env buffers the launchers read from the handle, pointed at the probe's for the lifetime of this object: the hot
-// kernels run on the probe blocks with noise_flags 0 and nothing of the envs is written.
-// The boundary: under this scope only qd_launch_csd / qd_launch_ground / qd_launch_solve, qd_k_sensor (with qd_noise_cfg)
-// and qd_k_percentile run, and of the per-env handle fields they read exactly the six swapped here
-//   params, state, zraw, plohi, occ, cfg.noise_flags
-// (tel and obs_serial go into qd_noise_cfg but are dead with flags 0; eig / tstats are NULL: validate handles are refused;
-// recs, slabs, gtiles, wide are launch scratch of lane 0).  steps, tel, the bound outputs gimg / pimg / bimg / volt and
-// the staging ring are NOT swapped: a launcher that starts to read one of them must get a probe twin here first, or it
-// acts on env data during a probe (tests/test_gpu_probe.py, the bit-identity and the no-footprint test, would show it).
-struct QdProbeScope {
-    qd_handle* h; double *params, *state, *zraw, *plohi, *occ; int noise_flags;
-    explicit QdProbeScope(qd_handle* h_) : h(h_), params(h_->params), state(h_->state), zraw(h_->zraw), plohi(h_->plohi),
-                                           occ(h_->occ), noise_flags(h_->cfg.noise_flags) {
-        h->params = h->pparams; h->state = h->pstate; h->zraw = h->pz; h->plohi = h->pplohi; h->occ = nullptr;
-        h->cfg.noise_flags = 0;
-        qd_use_lane(h, 0);
-    }
-    ~QdProbeScope() {
-        h->params = params; h->state = state; h->zraw = zraw; h->plohi = plohi; h->occ = occ; h->cfg.noise_flags = noise_flags;
-    }
-};
-
-static int qd_probe_chunk(qd_handle* h, int cnt, hipStream_t s) {
-    QdProbeScope scope(h);
-    int rc = qd_launch_csd(h, nullptr, 0, cnt, s, 3);
-    if (rc) return rc;
-    dim3 g3((h->P + 255) / 256, h->C, cnt);
-    QD_DISPATCH_N(h->N, qd_k_sensor<NN><<<g3, dim3(256), 0, s>>>(nullptr, h->R, h->params, h->state, h->zraw, qd_noise_cfg(h)));
-    QD_HIP(hipGetLastError());
-    if ((long)h->C * h->P <= (long)QD_PCT_KPT * QD_PCT_BLOCK)
-        qd_k_percentile<true><<<dim3(cnt), dim3(QD_PCT_BLOCK), 0, s>>>(nullptr, (long)h->C * h->P, h->zraw, h->plohi);
-    else
-        qd_k_percentile<false><<<dim3(cnt), dim3(QD_PCT_BLOCK), 0, s>>>(nullptr, (long)h->C * h->P, h->zraw, h->plohi);
-    QD_HIP(hipGetLastError());
-    return QD_OK;
-}
-
 extern "C" int qd_probe(qd_handle* h, const int32_t* env_of_query, int nq, const double* gate_v, const double* barrier_v,
                         const double* sensor_v, const double* window, double* raw_dst, float* image_dst, double* plohi_dst,
                         void* stream) {
@@ -770,13 +756,18 @@ extern "C" int qd_probe(qd_handle* h, const int32_t* env_of_query, int nq, const
         QD_HIP(hipMalloc(&h->pz, sizeof(double) * (size_t)pc * h->C * h->P));
         QD_HIP(hipMalloc(&h->pplohi, sizeof(double) * 2 * (size_t)pc));
     }
+    // the hot launchers run on the probe blocks, without noise, occupations or eigenvalues; nothing of the envs is written
+    QdEnvBufs pb{};
+    pb.params = h->pparams; pb.state = h->pstate; pb.zraw = h->pz; pb.plohi = h->pplohi;
     const QdProbeQuery Q{env_of_query, gate_v, barrier_v, sensor_v, window};
     for (int base = 0; base < nq; base += pc) {
         const int cnt = nq - base < pc ? nq - base : pc;
         qd_k_probe_gather<<<dim3(cnt), dim3(QD_PROBE_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params, h->state, h->pparams, h->pstate);
         QD_HIP(hipGetLastError());
-        int rc = qd_probe_chunk(h, cnt, s);
-        if (rc) return rc;
+        if (int rc = qd_launch_csd(h, pb, h->lanes[0], nullptr, 0, cnt, s, QD_ST_ALL)) return rc;
+        if (int rc = qd_launch_sensor(h, pb, nullptr, cnt, s)) return rc;
+        qd_launch_percentile(nullptr, (unsigned)cnt, (long)h->C * h->P, pb.zraw, pb.plohi, s);
+        QD_HIP(hipGetLastError());
         if (raw_dst || image_dst || plohi_dst) {
             qd_k_probe_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(env_of_query, base, h->B, h->C, h->P, h->pz, h->pplohi,
                                                                                  raw_dst, image_dst, plohi_dst);
@@ -854,10 +845,7 @@ extern "C" int qd_probe_compose(qd_handle* h, const double* raw, int nx, int ny,
     }
     const int per_scan = mode == QD_MAP_PER_SCAN ? 1 : 0;
     if (per_scan) {
-        if ((long)h->P <= (long)QD_PCT_KPT * QD_PCT_BLOCK)
-            qd_k_percentile<true><<<dim3((unsigned)nq), dim3(QD_PCT_BLOCK), 0, s>>>(nullptr, (long)h->P, h->cz, h->cplohi);
-        else
-            qd_k_percentile<false><<<dim3((unsigned)nq), dim3(QD_PCT_BLOCK), 0, s>>>(nullptr, (long)h->P, h->cz, h->cplohi);
+        qd_launch_percentile(nullptr, (unsigned)nq, (long)h->P, h->cz, h->cplohi, s);
         QD_HIP(hipGetLastError());
     } else {
         rc = qd_launch_select(h, h->cz, n, h->cplohi, plohi_dst, s);
@@ -866,6 +854,27 @@ extern "C" int qd_probe_compose(qd_handle* h, const double* raw, int nx, int ny,
     qd_k_map_place<<<dim3((h->P + 255) / 256, (unsigned)nq), dim3(256), 0, s>>>(h->cz, nx, ny, h->R, per_scan, per_scan, h->cplohi,
                                                                                composite_dst, plohi_dst);
     QD_HIP(hipGetLastError());
+    return QD_OK;
+}
+
+// Mean duration in milliseconds of a launch sequence on `s`: `rounds` times prep() untimed, then `reps` times timed() back to
+// back between two events.  prep and timed return a QD_ code.
+template <class Prep, class Timed>
+static int qd_time_mean(const qd_handle* h, hipStream_t s, int rounds, int reps, Prep prep, Timed timed, float* mean_ms) {
+    QdEventPair ev;
+    if (!ev.ok) return qd_fail(h, QD_ERR_HIP, "hipEventCreate");
+    float total = 0.f;
+    for (int r = 0; r < rounds; ++r) {
+        if (int rc = prep()) return rc;
+        QD_HIP(hipEventRecord(ev.a, s));
+        for (int i = 0; i < reps; ++i) if (int rc = timed()) return rc;
+        QD_HIP(hipEventRecord(ev.b, s));
+        QD_HIP(hipEventSynchronize(ev.b));
+        float ms = 0.f;
+        QD_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+        total += ms;
+    }
+    *mean_ms = total / ((float)rounds * (float)reps);
     return QD_OK;
 }
 
@@ -878,24 +887,12 @@ extern "C" int qd_time_select(qd_handle* h, const double* z_dev, long long n, in
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
     if (!h->sel) QD_HIP(hipMalloc(&h->sel, sizeof(QdSelState)));
-    QdEventPair ev;
-    if (!ev.ok) return qd_fail(h, QD_ERR_HIP, "hipEventCreate");
-    QD_HIP(hipEventRecord(ev.a, s));
-    for (int i = 0; i < iters; ++i) {
-        if (single_block) {
-            qd_k_percentile<false><<<dim3(1), dim3(QD_PCT_BLOCK), 0, s>>>(nullptr, (long)n, z_dev, out_dev);
-            QD_HIP(hipGetLastError());
-        } else {
-            int rc = qd_launch_select(h, z_dev, (long)n, out_dev, nullptr, s);
-            if (rc) return rc;
-        }
-    }
-    QD_HIP(hipEventRecord(ev.b, s));
-    QD_HIP(hipEventSynchronize(ev.b));
-    float ms = 0.f;
-    QD_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
-    *mean_ms = ms / iters;
-    return QD_OK;
+    return qd_time_mean(h, s, 1, iters, [] { return QD_OK; }, [&]() -> int {
+        if (!single_block) return qd_launch_select(h, z_dev, (long)n, out_dev, nullptr, s);
+        qd_launch_percentile(nullptr, 1, (long)n, z_dev, out_dev, s);
+        QD_HIP(hipGetLastError());
+        return QD_OK;
+    }, mean_ms);
 }
 
 extern "C" int qd_get_state(qd_handle* h, double* state, int32_t* steps) {
@@ -945,7 +942,7 @@ extern "C" int qd_get_candidates(qd_handle* h, int32_t* states) {
     const int N = h->N;
     for (size_t r0 = 0; r0 < nrec; r0 += slice) {
         const size_t cnt = nrec - r0 < slice ? nrec - r0 : slice;
-        hipError_t e_ = hipMemcpy(host, h->recs + r0, cnt * sizeof(QdPixelRec), hipMemcpyDeviceToHost);
+        hipError_t e_ = hipMemcpy(host, h->lanes[0].recs + r0, cnt * sizeof(QdPixelRec), hipMemcpyDeviceToHost);
         if (e_ != hipSuccess) { free(host); return qd_fail(h, QD_ERR_HIP, "hipMemcpy(recs)", e_); }
         // slots 0..K-1: the kept states (|0..0> padding from nvalid on); slots K..31: -1
         for (size_t r = 0; r < cnt; ++r) {
@@ -1000,38 +997,24 @@ extern "C" int qd_set_rng_state(qd_handle* h, uint64_t obs_serial) {
     return QD_OK;
 }
 
+// `rounds` x (`prep` stages untimed, then `reps` x the `timed` stages) of lane 0 on the first launch chunk of the envs
+static int qd_time_stages(qd_handle* h, hipStream_t s, int rounds, int reps, int prep, int timed, float* mean_ms) {
+    const QdEnvBufs b = qd_env_bufs(h);
+    const int cnt = h->chunk < h->B ? h->chunk : h->B;
+    return qd_time_mean(h, s, rounds, reps, [&] { return qd_launch_csd(h, b, h->lanes[0], nullptr, 0, cnt, s, prep); },
+                        [&] { return qd_launch_csd(h, b, h->lanes[0], nullptr, 0, cnt, s, timed); }, mean_ms);
+}
+
 extern "C" int qd_time_ground_kernel(qd_handle* h, int iters, float* mean_ms, void* stream) {
     if (!h || iters < 1 || !mean_ms) return QD_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
-    QdEventPair ev;
-    if (!ev.ok) return qd_fail(h, QD_ERR_HIP, "hipEventCreate");
-    const int cnt = h->chunk < h->B ? h->chunk : h->B;
-    QD_HIP(hipEventRecord(ev.a, s));
-    for (int i = 0; i < iters; ++i) { int rc = qd_launch_csd(h, nullptr, 0, cnt, s, 2); if (rc) return rc; }
-    QD_HIP(hipEventRecord(ev.b, s));
-    QD_HIP(hipEventSynchronize(ev.b));
-    float ms = 0.f;
-    QD_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
-    *mean_ms = ms / iters;
-    return QD_OK;
+    return qd_time_stages(h, (hipStream_t)stream, 1, iters, 0, QD_ST_GROUND, mean_ms);
 }
 
 extern "C" int qd_time_candidates_kernel(qd_handle* h, int iters, float* mean_ms, void* stream) {
     if (!h || iters < 1 || !mean_ms) return QD_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
-    QdEventPair ev;
-    if (!ev.ok) return qd_fail(h, QD_ERR_HIP, "hipEventCreate");
-    const int cnt = h->chunk < h->B ? h->chunk : h->B;
-    QD_HIP(hipEventRecord(ev.a, s));
-    for (int i = 0; i < iters; ++i) { int rc = qd_launch_csd(h, nullptr, 0, cnt, s, 1); if (rc) return rc; }
-    QD_HIP(hipEventRecord(ev.b, s));
-    QD_HIP(hipEventSynchronize(ev.b));
-    float ms = 0.f;
-    QD_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
-    *mean_ms = ms / iters;
-    return QD_OK;
+    return qd_time_stages(h, (hipStream_t)stream, 1, iters, 0, QD_ST_SEARCH, mean_ms);
 }
 
 extern "C" const char* qd_timed_kernel_name(int k) {
@@ -1041,28 +1024,15 @@ extern "C" const char* qd_timed_kernel_name(int k) {
 
 extern "C" int qd_time_kernels(qd_handle* h, int iters, float* mean_ms_out, void* stream) {
     if (!h || iters < 1 || !mean_ms_out) return QD_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
-    QdEventPair ev;
-    if (!ev.ok) return qd_fail(h, QD_ERR_HIP, "hipEventCreate");
-    const int cnt = h->chunk < h->B ? h->chunk : h->B;
     // (the redo pass consumes the tile search's flags and the solvers overwrite their input blocks: the producing kernel is
     // re-run, untimed, in front of each of their launches)
+    static const int stage[QD_TIMED_KERNELS] = {QD_ST_TILE, QD_ST_REDO, QD_ST_STRUCTURE, QD_ST_SOLVE, QD_ST_SELECT};
+    static const int producer[QD_TIMED_KERNELS] = {0, QD_ST_TILE, 0, QD_ST_STRUCTURE, 0};
     for (int k = 0; k < QD_TIMED_KERNELS; ++k) {
-        if (h->full_m && k < 2) { mean_ms_out[k] = 0.f; continue; }     // the full space runs no candidate search
-        float total = 0.f;
-        for (int i = 0; i < iters; ++i) {
-            if (k == 1 && h->tile_search == 1) { int rc = qd_launch_csd(h, nullptr, 0, cnt, s, 1, 1); if (rc) return rc; }
-            if (k == 3) { int rc = qd_launch_csd(h, nullptr, 0, cnt, s, 1, 4); if (rc) return rc; }
-            QD_HIP(hipEventRecord(ev.a, s));
-            if (!(k == 0 && h->tile_search != 1)) { int rc = qd_launch_csd(h, nullptr, 0, cnt, s, 1, 1 << k); if (rc) return rc; }
-            QD_HIP(hipEventRecord(ev.b, s));
-            QD_HIP(hipEventSynchronize(ev.b));
-            float ms = 0.f;
-            QD_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
-            total += ms;
-        }
-        mean_ms_out[k] = total / iters;
+        mean_ms_out[k] = 0.f;                                            // a stage the handle does not have
+        if (!(qd_stages(h) & stage[k])) continue;
+        if (int rc = qd_time_stages(h, (hipStream_t)stream, iters, 1, producer[k], stage[k], &mean_ms_out[k])) return rc;
     }
     return QD_OK;
 }

@@ -624,6 +624,43 @@ def test_batch_split_over_the_two_lanes_is_bit_identical_to_one_launch():
         env.close()
 
 
+@pytest.mark.parametrize("validate", [False, True])
+def test_timing_hooks_leave_nothing_behind(validate):
+    """The timing hooks launch single stages of the pipeline on the handle's own buffers and scratch (tile search on:
+    N = 4, R = 32).  A handle that was timed renders the same bits afterwards as a twin that never was, and every one of
+    the five kernel groups is reported; without the tile search `qd_k_tile` reports 0 and the redo pass is the search."""
+    from qadapt_hip.vec_env import VecQuantumDeviceEnv, SyntheticCapacitanceModel
+    N, R, B = 4, 32, 3
+    mk = lambda b=B, **kw: VecQuantumDeviceEnv(b, num_dots=N, resolution=R, seed=53, capacitance_model=SyntheticCapacitanceModel(7), **kw)
+    timed, twin = mk(validate=validate), mk(validate=validate)
+    for env in (timed, twin):
+        env.reset()
+    t = timed.time_kernels(iters=1)
+    ground, search = timed.time_ground_kernel(1), timed.time_candidates_kernel(1)
+    print(t, ground, search)
+    assert list(t) == ["qd_k_tile", "qd_k_candidates", "qd_k_gs_structure", "qd_k_gs_solve", "qd_k_gs_select"]
+    assert all(np.isfinite(v) and v > 0 for v in t.values()), t
+    assert np.isfinite(ground) and np.isfinite(search)
+    outs = []
+    for env in (timed, twin):
+        obs = env.observe()
+        out = [obs["image"].cpu().numpy().copy(), *env.raw()]
+        if validate:
+            out += [env.get_state()[0], env.candidates(), env.occupations(), env.eigen()]
+        outs.append(out)
+    for a, b in zip(*outs):
+        assert a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    assert np.ptp(outs[0][1]) > 0
+    for env in (timed, twin):
+        env.close()
+    if not validate:
+        pix = mk(2, pixel_search=True)
+        pix.reset()
+        t = pix.time_kernels(iters=1)
+        assert t["qd_k_tile"] == 0.0 and t["qd_k_candidates"] > 0, t
+        pix.close()
+
+
 @pytest.mark.parametrize("seed", range(14))
 def test_randomised_scene_sweep(seed):
     """Wider net than the hand-picked cases above: random array size, resolution, regime and device per seed;

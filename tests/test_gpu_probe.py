@@ -124,11 +124,17 @@ def test_probe_has_the_bits_of_set_state_and_observe(tmp_path, N, R, K, m):
 
 
 # ------------------------------------------------------------------ 2. no footprint
-def test_probes_leave_no_footprint_on_a_noisy_run(tmp_path):
+@pytest.mark.parametrize("R,env_chunk", [(16, 0), (16, 2), (32, 2)])
+def test_probes_leave_no_footprint_on_a_noisy_run(tmp_path, R, env_chunk):
+    """env_chunk = 2: an observe of the B = 5 envs runs three chunks over the two launch lanes, and the probes (13, 1 or 5
+    queries) run between them in chunks of 2 on lane 0's scratch.  R = 32 has the tile search and its redo pass (N = 4)."""
     import torch
-    N, R, B, seed, max_steps = 4, 16, 5, 31337, 3
+    N, B, seed, max_steps = 4, 5, 31337, 3
     path = _cfg(tmp_path, max_steps=max_steps)
-    envs = [_vec(tmp_path, B, N, R, seed, config_path=path, noise=("sensor", "radial", "latch")) for _ in range(2)]
+    mk = lambda chunk: _vec(tmp_path, B, N, R, seed, config_path=path, noise=("sensor", "radial", "latch"), env_chunk=chunk)
+    envs = [mk(env_chunk) for _ in range(2)]
+    if env_chunk:
+        assert all(env.chunk_envs() == env_chunk for env in envs)
     plain, probed = envs
     L = layout(N)
     prng = np.random.default_rng(3)
@@ -161,6 +167,15 @@ def test_probes_leave_no_footprint_on_a_noisy_run(tmp_path):
     trace = [[], []]
     for k, env in enumerate(envs):
         trace[k].append(snapshot(env, env.reset(seed=seed)))
+    if env_chunk:
+        # the lanes do not change the result: one launch of all B envs renders the same bits, noise included
+        one = mk(B)
+        assert one.chunk_envs() == B
+        first = snapshot(one, one.reset(seed=seed))
+        assert first.keys() == trace[0][0].keys()
+        for key in first:
+            assert _same(first[key], trace[0][0][key]), key
+        one.close()
     poke()
     acts = np.random.default_rng(11).uniform(-1, 1, (6, B, 2 * N - 1)).astype(np.float32)
     truncations = 0
