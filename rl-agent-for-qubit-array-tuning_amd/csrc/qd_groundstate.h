@@ -9,7 +9,7 @@
 //
 //   A  STRUCTURE (qd_k_gs_structure), one pixel per half-wave, one basis state per lane (qd_ground_structure):
 //      hop neighbours (states i, j couple over the adjacent pair d iff s_j - s_i = -+e_d +-e_{d+1}; with 4-bit-spaced
-//      delta codes that is a borrow-free nibble difference of 0x1F << 4q or 0xF1 << 4q), coefficients
+//      delta codes that is a plain integer difference of +-15 << 4q: qd_gs_hop), coefficients
 //      H_ij = -t_d sqrt(n_from (n_to + 1)) with the occupations of the ROW state (hamiltonian_build.py:125-131),
 //      connected components (hopping conserves the total charge, so H is block diagonal; the padding copies of
 //      |0..0> are always isolated), Gershgorin pruning (a component whose lower bound min(F - sum|H_ij|) exceeds
@@ -29,17 +29,39 @@
 #include "qd_pixel.h"
 #include "qd_eig.h"
 
+#define QD_GS_PPB 256               // pixels per batch (4 waves x 32 iterations x 2 pixels)
+// size classes: 2 .. 8 states exactly, 9-10 (solved as 10), 11-12 (as 12), 13-32 (memory solver)
+#define QD_GS_NBIN 10
+QD_HD constexpr int qd_gs_bin(int s) { return s <= 8 ? s - 2 : (s <= 10 ? 7 : (s <= 12 ? 8 : 9)); }
+QD_HD constexpr int qd_gs_bin_min(int bin) { return bin <= 6 ? bin + 2 : (bin == 7 ? 9 : (bin == 8 ? 11 : 13)); }
+
+// Hop test of two states.  ci, cj: their delta codes with one digit (0..3) per nibble, nibble q = dot N-1-q; tcq: bit 4q set
+// iff the adjacent pair N-2-q couples.  cj - ci = sum d_k 16^k with |d_k| <= 3, and a base-16 representation with digits in
+// -7..7 is unique, so |cj - ci| == 15 << 4q exactly when d_{q+1} = +-1, d_q = -+1 and every other digit agrees: one electron
+// moved between the adjacent dots of pair N-2-q.  A difference 15 << tz with tz no multiple of 4 (30 = 2 * 16 - 2, ...) finds
+// no bit in tcq.  Equal codes (the same state, the copies of the |0..0> padding): ay = 0, tz = 31, ay >> tz = 0, no hop.
+QD_HD unsigned qd_gs_hop(unsigned ci, unsigned cj, unsigned tcq) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    unsigned ay;
+    asm("v_sad_u32 %0, %1, %2, 0" : "=v"(ay) : "v"(ci), "v"(cj));
+#else
+    const unsigned ay = ci > cj ? ci - cj : cj - ci;
+#endif
+    const int tz = __builtin_ctz(ay | 0x80000000u);
+    // x == 0 iff ay == 15 << tz (mod 2^32; -15 is odd, so ay = 0 with tz = 31 leaves x = 1 << 31); the verdict is the pair's
+    // bit where x == 0 and 0 elsewhere, as a saturating t - x: branch-free on purpose (the compiler otherwise builds a
+    // divergent branch per round), and free of compares
+    const unsigned x = ay + (0xFFFFFFF1u << tz);
+    const unsigned t = (tcq >> tz) & 1u;
+    return t > x ? t - x : 0u;
+}
+
 #if defined(__HIPCC__)
 
 #ifndef QD_NBREG
 #define QD_NBREG 6                  // neighbour slots kept in registers; the other 2*(N-1) - 6 live in LDS (8 dots: 21 KB per block)
 #endif
 #define QD_GS_BLOCK 256
-#define QD_GS_PPB 256               // pixels per batch (4 waves x 32 iterations x 2 pixels)
-// size classes: 2 .. 8 states exactly, 9-10 (solved as 10), 11-12 (as 12), 13-32 (memory solver)
-#define QD_GS_NBIN 10
-__host__ __device__ inline int qd_gs_bin(int s) { return s <= 8 ? s - 2 : (s <= 10 ? 7 : (s <= 12 ? 8 : 9)); }
-__host__ __device__ inline int qd_gs_bin_min(int bin) { return bin <= 6 ? bin + 2 : (bin == 7 ? 9 : (bin == 8 ? 11 : 13)); }
 #define QD_LINK_NONE 0xFFFFFFFFu    // state whose component cannot hold the ground state (Gershgorin)
 #define QD_LINK_SINGLE 0xFFFFFFFEu  // isolated state that can: T = [F]
 
@@ -77,8 +99,32 @@ struct QdBlockLds {
 struct QdSlab {
     double* pool; unsigned* link; unsigned char* rank; unsigned* lists; double* aux; unsigned* cnt; double* lam;
 };
-__host__ __device__ inline int qd_gs_list_cap(int bin) { return QD_GS_PPB * (32 / qd_gs_bin_min(bin)); }
-__host__ __device__ inline int qd_gs_list_off(int bin) { int o = 0; for (int b = 0; b < bin; ++b) o += qd_gs_list_cap(b); return o; }
+// Lists of the size classes, back to back: class b can hold 32 / qd_gs_bin_min(b) tasks per pixel.  Capacities and offsets
+// in units of QD_GS_PPB tasks, as tables packed into one word each (5 and 6 bits per class), so that the structure kernel,
+// which looks the offset up with a run-time class, shifts a constant instead of summing the capacities with a division
+// per class; the static_asserts below tie the tables to that definition.
+constexpr int QD_GS_CAP_TAB[QD_GS_NBIN + 1] = {16, 10, 8, 6, 5, 4, 4, 3, 2, 2, 2};
+constexpr int QD_GS_OFF_TAB[QD_GS_NBIN + 1] = {0, 16, 26, 34, 40, 45, 49, 53, 56, 58, 60};
+constexpr unsigned long long qd_gs_pack_tab(const int* tab, int n, int bits) {
+    unsigned long long w = 0;
+    for (int b = 0; b < n; ++b) w |= (unsigned long long)tab[b] << (bits * b);
+    return w;
+}
+constexpr unsigned long long QD_GS_CAP_WORD = qd_gs_pack_tab(QD_GS_CAP_TAB, QD_GS_NBIN + 1, 5);
+constexpr unsigned long long QD_GS_OFF_WORD = qd_gs_pack_tab(QD_GS_OFF_TAB, QD_GS_NBIN, 6);     // (the total is not packed)
+QD_HD constexpr int qd_gs_list_cap(int bin) { return QD_GS_PPB * (int)((QD_GS_CAP_WORD >> (5 * bin)) & 31u); }
+QD_HD constexpr int qd_gs_list_off(int bin) {
+    return QD_GS_PPB * (bin >= QD_GS_NBIN ? QD_GS_OFF_TAB[QD_GS_NBIN] : (int)((QD_GS_OFF_WORD >> (6 * bin)) & 63u));
+}
+constexpr bool qd_gs_lists_match_definition() {
+    int o = 0;
+    for (int b = 0; b <= QD_GS_NBIN; ++b) {
+        if (qd_gs_list_off(b) != o || qd_gs_list_cap(b) != QD_GS_PPB * (32 / qd_gs_bin_min(b))) return false;
+        o += QD_GS_PPB * (32 / qd_gs_bin_min(b));
+    }
+    return true;
+}
+static_assert(qd_gs_lists_match_definition(), "QD_GS_CAP_TAB / QD_GS_OFF_TAB: capacity 32 / qd_gs_bin_min(b) per pixel, offsets their running sum");
 __host__ __device__ inline int qd_gs_task_doubles(int s, bool validate) {
     const int ne = s * (s + 1) / 2;
     const int n = 2 + ne + (s > QD_EIG_REG ? 4 * s + (validate ? ne : 0) : 0);
@@ -128,6 +174,32 @@ __device__ __forceinline__ int qd_wave_max_int(int v) {
     return __builtin_amdgcn_readfirstlane(v);
 }
 
+// v of lane (m + J) mod 32 (UP) or (m - J) mod 32 (!UP) of the same half-wave, J a constant: ds_swizzle in rotate mode moves
+// the data without an address register (a __shfl spends three instructions on the ds_bpermute address of every round).
+// A swizzle reads 0 from a lane that is switched off: the caller runs with all 64 lanes on -- the two halves of a wave work
+// in lock step and the clamped duplicate beyond the image is computed, not switched off.
+#ifndef QD_GS_ROT_SWIZZLE
+#define QD_GS_ROT_SWIZZLE 1         // 0: the same exchange with __shfl (diagnostic)
+#endif
+template <int J, bool UP>
+__device__ __forceinline__ unsigned qd_half_rot(unsigned v) {
+#if QD_GS_ROT_SWIZZLE
+    return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0xC000 | ((UP ? 0 : 1) << 10) | (J << 5));
+#else
+    return (unsigned)__shfl((int)v, ((int)(threadIdx.x & 31) + (UP ? J : 32 - J)) & 31, 32);
+#endif
+}
+// rounds J .. 16 of the all-pairs hop test (qd_ground_structure, phase 2), unrolled at compile time
+template <int J>
+__device__ __forceinline__ void qd_gs_hop_rounds(unsigned ecode, unsigned tcq, unsigned& acc) {
+    const unsigned hop = qd_gs_hop(ecode, qd_half_rot<J, true>(ecode), tcq);
+    acc |= hop << J;
+    if constexpr (J < 16) {                                // (round 16 pairs m with m + 16 from both sides already)
+        acc |= qd_half_rot<J, false>(hop) << (32 - J);
+        qd_gs_hop_rounds<J + 1>(ecode, tcq, acc);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Phase A.  rec: this half's pixel record (states, their free energies from the candidate search, tunnel couplings);
 // ps: the pixel's slot in the batch; live: false for the clamped duplicate beyond the image (nothing is emitted);
@@ -172,32 +244,16 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
     unsigned tcnz = 0;
 #pragma unroll
     for (int d = 0; d < N - 1; ++d) tcnz |= (pvv[9 + d] != 0.0 ? 1u : 0u) << d;
-    // nibble q of ecode is the digit of dot N-1-q.  (cj | 0x8..8) - ecode holds 8 + (digit_j - digit_i)
-    // in every nibble (no borrows), so Z = that ^ 0x8..8 has nibble 0 where the digits agree, 1 for +1
-    // and 0xF for -1: j is a hop neighbour iff Z == 0x1F << 4q or 0xF1 << 4q (one electron moved
-    // between the adjacent dots of pair N-2-q) and that pair's coupling is non-zero.
-    unsigned tcq = 0;                                     // bit 4q set iff pair N-2-q couples
+    unsigned tcq = 0;                                     // bit 4q set iff pair N-2-q couples (nibble q of ecode is the digit of dot N-1-q)
 #pragma unroll
     for (int q = 0; q < N - 1; ++q) tcq |= ((tcnz >> (N - 2 - q)) & 1u) << (4 * q);
     // The relation is symmetric, so every pair is tested once: in round j lane m tests its partner (m + j) mod 32 and hands the
     // verdict to that partner as well (which receives it from lane (m - j) mod 32) -- 16 rounds instead of 32 tests per lane.
-    unsigned nbrmask = 0;
-#pragma unroll 4
-    for (int j = 1; j <= 16; ++j) {
-        const int pj = (m + j) & 31;
-        const unsigned cj = __shfl(ecode, pj, 32);
-        const unsigned Z = ((cj | 0x88888888u) - ecode) ^ 0x88888888u;
-        const int tz = __builtin_ctz(Z | 0x80000000u);     // Z == 0 (same state): tz = 31, Zs = 0, no hop (a nibble of Z is never 8)
-        const unsigned Zs = Z >> tz;
-        // branch-free on purpose (bitwise, not short-circuit): the compiler otherwise builds a divergent branch per j
-        const unsigned hop = ((unsigned)(Zs == 0x1Fu) | (unsigned)(Zs == 0xF1u)) & (tcq >> tz) & 1u;
-        nbrmask |= hop << pj;
-        if (j < 16) {                                      // (round 16 pairs m with m + 16 from both sides already)
-            const int qj = (m - j) & 31;
-            const unsigned back = (unsigned)__shfl((int)hop, qj, 32);
-            nbrmask |= back << qj;
-        }
-    }
+    // Both exchanges are rotations of the half-wave by the constant j (qd_half_rot).  The verdicts are collected in the frame
+    // of the lane, bit b = partner (m + b) mod 32, with constant shifts, and rotated into place once at the end.
+    unsigned acc = 0;
+    qd_gs_hop_rounds<1>(ecode, tcq, acc);
+    unsigned nbrmask = __builtin_rotateleft32(acc, (unsigned)m);
     // states beyond the valid count (|0..0> padding, and everything from slot K on) neither hop nor are hopped to
     nbrmask = (valid && live) ? (nbrmask & (nvalid >= 32 ? 0xFFFFFFFFu : ((1u << nvalid) - 1u))) : 0u;
 #if defined(QD_ABLATE) && QD_ABLATE == 4
@@ -227,8 +283,8 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
                 const int nd1 = (int)W.pfl[hh][d + 1] + (int)((ecode >> (4 * q)) & 3u) - 1;
                 const double t = pvv[9 + d];
                 // Y < 0: s_j = s_i - e_d + e_{d+1} (forward); else backward
-                const double prod = (Y < 0) ? (double)nd * ((double)nd1 + 1.0)
-                                            : (double)nd1 * ((double)nd + 1.0);
+                // (small integers: the product is formed exactly either way, so it is converted once)
+                const double prod = (double)((Y < 0) ? nd * (nd1 + 1) : nd1 * (nd + 1));
                 double sq_ = 0.0;
                 if (prod > 0.0) sq_ = qd_sqrt1(prod);
                 c = -t * sq_;

@@ -294,7 +294,7 @@ __device__ __forceinline__ void qd_gs_publish_tiles(const QdBlockLds& sB, const 
 }
 
 #ifndef QD_GS_WAVES
-#define QD_GS_WAVES 7            // 72 VGPRs (28 B of scratch per lane) and 7 x 21 KB of LDS per CU (8 dots).  The kernel is latency
+#define QD_GS_WAVES 7            // 72 VGPRs (24 B of scratch per lane) and 7 x 21 KB of LDS per CU (8 dots).  The kernel is latency
                                  // bound (ds_bpermute / LDS chains): measured per env-step 4 waves per SIMD 26.8 us, 5: 22.6, 6: 20.5, 7: 19.6,
                                  // 8 (64 VGPRs, 116 B of scratch): 31.2
 #endif
