@@ -219,6 +219,45 @@ int qd_probe(qd_handle* h, const int32_t* env_of_query_dev, int nq, const double
              const double* barrier_v_dev, const double* sensor_v_dev, const double* window_dev,
              double* raw_dst, float* image_dst, double* plohi_dst, void* stream);
 
+/* Point evaluation: TunnelCoupledChargeSensed.charge_sensor_open(vg, vb) -> (signal, n_open) and ground_state_open(vg, vb)
+ * (TunnelCoupledChargeSensed.py:312-380, ground_state.py:24-166) at arbitrary PHYSICAL voltages, np points in one call:
+ * line cuts, plunger-versus-barrier scans, scans of non-adjacent pairs, simplex vertices, the occupations at one voltage.
+ * Points come in ng groups; group g evaluates rows group_start_host[g] .. group_start_host[g + 1] on the device (parameter
+ * block) of env group_env_host[g].  An env may be named by many groups.
+ *   group_env_host   [ng]        int32, HOST, each in [0, B)
+ *   group_start_host [ng + 1]    int64, HOST, non-decreasing, >= 0; np = group_start_host[ng]
+ *   vg_dev           [np][N+1]   physical gate voltages, sensor gate last, as charge_sensor_open takes them: no virtual
+ *                                gate matrix and no origin are applied
+ *   vb_dev           [np][N-1]   barrier voltages
+ *   gamma_host       [ng]        HOST, the peak width of each group's sensor signal, or NULL: each env's own
+ *                                coulomb_peak_width (scal[1] of its parameter block)
+ *   signal_dst       [np]        float64 sensor signal, sum over the 10 peaks; may be NULL
+ *   occ_dst          [np][N]     float64 expectation occupations <n>; may be NULL
+ * vg_dev, vb_dev, signal_dst and occ_dst are caller-owned DEVICE memory; rows before group_start_host[0] and past np are
+ * neither read nor written.  The call is stream-ordered on `stream` and DETERMINISTIC, as probes are: no sensor noise, no
+ * radial noise, no latching, whatever the handle's noise_flags.  A point takes the place of a pixel: its record is filled
+ * from the caller's voltages, then the per-pixel candidate search, the ground-state kernels and the sensor expression of
+ * qd_observe run on it, so a point at the voltages of a scan's pixel has the bits of that pixel in a noise-free scan of a
+ * QD_FLAG_PIXEL_SEARCH handle with a constant peak width.  The voltage-dependent capacitance model applies as in scans.
+ * The occupations have the bits qd_get_occupations gives for that pixel on a QD_FLAG_VALIDATE handle.  Those two paths
+ * solve the kept states in different orders when num_charge_states is 8, 16 or 32 (a product handle keeps the search
+ * order, a validate handle the reference order by (E, index)) and their eigenvectors differ by rounding; so with both
+ * destinations given the signal is solved first, the records are sorted and the ground-state stage runs again for the
+ * occupations.  With one destination, or any other num_charge_states, it runs once.
+ * The call changes nothing that qd_step, qd_observe, qd_probe or any qd_get_* function can see.
+ * Points run in slots of C*P (one env each; a group takes ceil(n / (C*P)) slots, the last one padded with records that
+ * cost neither a search nor an eigen task), at most min(qd_chunk_envs, QD_POINTS_SLOTS) slots per launch.  Scratch (per
+ * slot in flight: a parameter copy, a state block, C*P doubles of sensor constants, C*P*N doubles of occupations -- 1.8 MB
+ * at 8 dots and 64x64, so about 117 MB at most) is allocated by the first call with hipMalloc and freed by qd_destroy.
+ * QD_ERR_ARG, found without reading the device: group_env_host, group_start_host, vg_dev or vb_dev NULL, ng < 0,
+ * group_start_host decreasing or negative, an env id outside [0, B).  QD_ERR_STATE: a QD_FLAG_VALIDATE handle (as
+ * qd_probe), and a handle in the full charge-state space, whose structure kernel synthesises its own voltages (a point
+ * front end for it is not built).  ng == 0 or np == group_start_host[0] does nothing.  Works for num_charge_states 1..32. */
+#define QD_POINTS_SLOTS 64
+int qd_eval_points(qd_handle* h, const int32_t* group_env_host, const int64_t* group_start_host, int ng,
+                   const double* vg_dev, const double* vb_dev, const double* gamma_host,
+                   double* signal_dst, double* occ_dst, void* stream);
+
 /* Stitches one channel of nx*ny probe signals into one composite image on the device (map_device_range.py:134-170,
  * map_full_device_range.py:168-194).  raw_dev [nx*ny][C][P] as qd_probe wrote it, query index i*ny + j for scan (i, j);
  * composite_dst [ny*R][nx*R] float32; both DEVICE memory, stream-ordered, no host wait.

@@ -10,6 +10,7 @@
 #include "qd_kernels.h"
 #include "qd_fullspace.h"
 #include "qd_probe.h"
+#include "qd_points.h"
 
 // Scratch + streams of one launch chunk in flight.  Product mode keeps TWO: consecutive chunks alternate between them on
 // two internal streams, so the candidate search of one chunk (float64 VALU bound) runs beside the ground-state stage of
@@ -57,6 +58,9 @@ struct qd_handle {
     double *pparams, *pstate, *pz, *pplohi;
     double *cz, *cplohi; size_t cz_cap, cplohi_cap;
     QdSelState* sel;
+    // point evaluation (qd_eval_points): parameter and state copies, sensor constants and occupations of the slots in flight,
+    // allocated by the first call
+    double *qparams, *qstate, *qz, *qocc;
     mutable char err[512];                  // (the launchers take the handle const and still report through it)
 };
 
@@ -327,7 +331,8 @@ extern "C" int qd_destroy(qd_handle* h) {
     if (!h) return QD_ERR_ARG;
     QdDeviceGuard guard_(h->device);
     void* bufs[] = {h->params, h->state, h->steps, h->zraw, h->plohi, h->occ, h->tel, h->eig, h->tstats, h->ftab,
-                    h->pparams, h->pstate, h->pz, h->pplohi, h->cz, h->cplohi, h->sel};
+                    h->pparams, h->pstate, h->pz, h->pplohi, h->cz, h->cplohi, h->sel,
+                    h->qparams, h->qstate, h->qz, h->qocc};
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (int k = 0; k < QD_MAX_LANES; ++k) {
         void* lb[] = {h->lanes[k].recs, h->lanes[k].slabs, h->lanes[k].gtiles, h->lanes[k].wide};
@@ -775,6 +780,97 @@ extern "C" int qd_probe(qd_handle* h, const int32_t* env_of_query, int nq, const
         }
     }
     return QD_OK;
+}
+
+// slots in flight of qd_eval_points: one launch chunk of lane 0's records, at most QD_POINTS_SLOTS
+static int qd_points_slots(const qd_handle* h) { return h->chunk < QD_POINTS_MAX_SLOTS ? h->chunk : QD_POINTS_MAX_SLOTS; }
+
+extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
+                              const double* vb, const double* gamma, double* signal_dst, double* occ_dst, void* stream) {
+    static_assert(QD_POINTS_MAX_SLOTS == QD_POINTS_SLOTS, "qdsim.h states the bound");
+    if (!h) return QD_ERR_ARG;
+    if (ng < 0) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: ng < 0");
+    if (!group_env || !group_start) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: group_env_host or group_start_host is NULL");
+    if (!vg || !vb) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: vg_dev or vb_dev is NULL");
+    if (group_start[0] < 0) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: group_start is negative");
+    for (int g = 0; g < ng; ++g) {
+        if (group_start[g + 1] < group_start[g]) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: group_start is not non-decreasing");
+        if (group_env[g] < 0 || group_env[g] >= h->B) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: env id out of range");
+    }
+    if (h->cfg.flags & QD_FLAG_VALIDATE)
+        return qd_fail(h, QD_ERR_STATE, "qd_eval_points: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
+                                        "B envs' last observe and evaluates no points; use a handle without the flag");
+    if (h->full_m)
+        return qd_fail(h, QD_ERR_STATE, "qd_eval_points: the full charge-state space synthesises its own voltages "
+                                        "(qd_k_full_structure); a point front end for it is not built yet");
+    if (ng == 0 || group_start[ng] == group_start[0]) return QD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    QD_ON_DEVICE(h);
+    const int ps = qd_points_slots(h);
+    const long long CP = (long long)h->C * h->P;
+    if (!h->qparams) {
+        QD_HIP(hipMalloc(&h->qparams, sizeof(double) * (size_t)ps * h->L.size));
+        QD_HIP(hipMalloc(&h->qstate, sizeof(double) * (size_t)ps * h->L.s_size));
+        QD_HIP(hipMalloc(&h->qz, sizeof(double) * (size_t)ps * CP));
+        QD_HIP(hipMalloc(&h->qocc, sizeof(double) * (size_t)ps * CP * h->N));
+    }
+    // the ground-state launcher runs on the point buffers, without noise or eigenvalues; nothing of the envs is written
+    QdEnvBufs qb{};
+    qb.params = h->qparams; qb.state = h->qstate; qb.zraw = h->qz; qb.occ = h->qocc;
+    const QdLane& ln = h->lanes[0];
+    const int sorted = h->kept != h->kc ? 1 : 0;              // as qd_launch_csd: K < KC takes the first K of the ordered list
+    QdPointSlots T;
+    memset(&T, 0, sizeof(T));
+    T.own_gamma = gamma ? 0 : 1;
+    int n = 0;
+    // one launch per `ps` slots: gather -> front end -> per-pixel search of the handed-over records -> ground state -> write
+    auto flush = [&]() -> int {
+        if (n == 0) return QD_OK;
+        const dim3 grid((unsigned)((CP + QD_POINTS_BLOCK - 1) / QD_POINTS_BLOCK), n);
+        qd_k_points_gather<<<dim3(n), dim3(QD_POINTS_BLOCK), 0, s>>>(T, h->N, h->params, h->state, h->qparams, h->qstate);
+        QD_HIP(hipGetLastError());
+        QD_DISPATCH_N(h->N, qd_k_points_front<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, vg, vb, h->qparams, ln.recs));
+        QD_HIP(hipGetLastError());
+        // (launched directly: qd_launch_csd would pick the non-redo instantiation on handles without a tile search and
+        // overwrite the front end)
+        const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
+        QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
+            qd_k_candidates<NN, true, KK><<<dim3(qd_cand_blocks(h->R), h->C, n), dim3(QD_CAND_BLOCK), shm, s>>>(nullptr, 0, h->R,
+                h->qparams, h->qstate, ln.recs, sorted, 0)));
+        QD_HIP(hipGetLastError());
+        // The signal comes from the list as the search left it, which is what qd_observe and qd_probe solve: the probe's bits.
+        // The occupations come from the list in the reference order, which is what a validate handle solves and
+        // qd_get_occupations returns: with K == KC (search order) the records are sorted and the ground-state stage runs again.
+        const bool resort = !sorted && occ_dst;
+        if (signal_dst || !resort) {
+            if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND)) return rc;
+            if (signal_dst || occ_dst) {
+                QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, h->qparams, h->qz, h->qocc,
+                                                                                               signal_dst, resort ? nullptr : occ_dst));
+                QD_HIP(hipGetLastError());
+            }
+        }
+        if (resort) {
+            const long nrec = (long)n * CP;
+            QD_DISPATCH_KC(h->kc, qd_k_points_sort<KK><<<dim3((unsigned)((nrec + 63) / 64)), dim3(64), 0, s>>>(ln.recs, nrec));
+            QD_HIP(hipGetLastError());
+            if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND)) return rc;
+            QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, h->qparams, h->qz, h->qocc,
+                                                                                           nullptr, occ_dst));
+            QD_HIP(hipGetLastError());
+        }
+        n = 0;
+        return QD_OK;
+    };
+    for (int g = 0; g < ng; ++g) {
+        for (long long p0 = group_start[g]; p0 < group_start[g + 1]; p0 += CP) {
+            const long long left = group_start[g + 1] - p0;
+            T.start[n] = p0; T.env[n] = group_env[g]; T.cnt[n] = (int)(left < CP ? left : CP);
+            T.gamma[n] = gamma ? gamma[g] : 0.0;
+            if (++n == ps) if (int rc = flush()) return rc;
+        }
+    }
+    return flush();
 }
 
 // numpy 'linear' percentile ranks of n values, as qd_k_percentile takes them

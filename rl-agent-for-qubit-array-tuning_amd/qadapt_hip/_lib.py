@@ -16,6 +16,7 @@ QD_NOISE_SENSOR = 1
 QD_NOISE_RADIAL = 2
 QD_NOISE_LATCH = 4
 QD_MAP_GLOBAL, QD_MAP_PER_SCAN = 0, 1
+QD_POINTS_SLOTS = 64
 QD_ERR_ARG, QD_ERR_HIP, QD_ERR_STATE = 1, 2, 3
 
 EXPORTS = [
@@ -24,7 +25,7 @@ EXPORTS = [
     "qd_update_capacitance", "qd_step", "qd_snapshot", "qd_get_state", "qd_set_state", "qd_get_raw",
     "qd_get_occupations", "qd_get_candidates", "qd_get_eigen", "qd_get_search_stats", "qd_get_solver_stats", "qd_get_rng_state", "qd_set_rng_state",
     "qd_time_ground_kernel", "qd_time_candidates_kernel", "qd_time_kernels", "qd_timed_kernel_name", "qd_chunk_envs",
-    "qd_probe", "qd_probe_compose", "qd_time_select",
+    "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points",
 ]
 
 QD_CURVES = {"constant": 0, "polynomial": 1, "exponential": 2, "linear": 3}
@@ -119,6 +120,9 @@ def lib():
     L.qd_probe_compose.restype = ctypes.c_int
     L.qd_time_select.argtypes = [vp, dp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, dp, ctypes.POINTER(ctypes.c_float), vp]
     L.qd_time_select.restype = ctypes.c_int
+    L.qd_eval_points.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, dp, dp, ctypes.POINTER(ctypes.c_double),
+                                 dp, dp, vp]
+    L.qd_eval_points.restype = ctypes.c_int
     _LIB = L
     return L
 

@@ -11,17 +11,55 @@ qadapt_hip.multi_agent.MultiAgentEnvWrapper unchanged.
 """
 from __future__ import annotations
 
-import types
-
 import numpy as np
 
 from . import spaces
 from .device_model import load_yaml
 
 
+class ModelFacade:
+    """`env.array.model` of the reference (a TunnelCoupledChargeSensed) as far as it is built: `cgd_full`, the peak width
+    `coulomb_peak_width` and the point functions `charge_sensor_open(vg, vb)` / `ground_state_open(vg, vb)`
+    (TunnelCoupledChargeSensed.py:312-380), evaluated by the backend's `eval_points` on the env's current device without
+    touching the episode and without noise.  `coulomb_peak_width` is the device's own at every reset and is read at call
+    time, so it may be assigned as the reference's `_get_obs` does (qarray_base_class.py:192-196)."""
+
+    def __init__(self, backend, num_dots):
+        self._b = backend
+        self.n_dot = int(num_dots)
+        self.cgd_full = None
+        self.coulomb_peak_width = None
+
+    def _points(self, vg, vb, outputs):
+        if vb is None:
+            raise NotImplementedError(
+                "charge_sensor_open / ground_state_open without barrier voltages: the reference's barrier-less branch uses a "
+                "constant model.tc that the env never sets, and cgd_full has 2N columns (gates and barriers) in barrier "
+                "mode, so it cannot run there either; pass vb")
+        N = self.n_dot
+        vg, vb = np.asarray(vg, np.float64), np.asarray(vb, np.float64)
+        if vg.shape[-1:] != (N + 1,) or vb.shape[-1:] != (N - 1,) or vg.shape[:-1] != vb.shape[:-1]:
+            raise ValueError(f"vg must be (..., {N + 1}) and vb (..., {N - 1}) with equal leading shapes; "
+                             f"got {vg.shape} and {vb.shape}")
+        lead = vg.shape[:-1]
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        out = self._b.eval_points([0], vg.reshape(1, -1, N + 1), vb.reshape(1, -1, N - 1), gamma=gamma, outputs=outputs)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        signal = host(out["signal"]).astype(np.float64).reshape(lead + (1,)) if "signal" in outputs else None
+        return signal, host(out["occupations"]).astype(np.float64).reshape(lead + (N,))
+
+    def charge_sensor_open(self, vg, vb=None):
+        """(signal (..., 1), n_open (..., N)) float64 at physical gate voltages vg (..., N+1) and barrier voltages vb (..., N-1)."""
+        return self._points(vg, vb, ("signal", "occupations"))
+
+    def ground_state_open(self, vg, vb=None):
+        """n_open (..., N) float64."""
+        return self._points(vg, vb, ("occupations",))[1]
+
+
 class ArrayFacade:
     """`env.array` of the reference (a QarrayBaseClass) as far as its users outside step() need it: `model.cgd_full`,
-    `barrier_alpha`, `gate_ground_truth`, the scan geometry (`obs_voltage_min`, `obs_voltage_max`, `obs_image_size`,
+    `model.charge_sensor_open` / `model.ground_state_open` (ModelFacade), `barrier_alpha`, `gate_ground_truth`, the scan geometry (`obs_voltage_min`, `obs_voltage_max`, `obs_image_size`,
     `num_dots`, `num_barrier_voltages`) and the stateless `_get_obs` (qarray_base_class.py:171-229), rendered by the
     backend's probe on the current device without touching the episode.  The window is
     (obs_voltage_max - obs_voltage_min) / 2 around each gate voltage; it follows the device (`window_delta`) at every
@@ -30,7 +68,7 @@ class ArrayFacade:
 
     def __init__(self, backend, num_dots, resolution):
         self._b = backend
-        self.model = types.SimpleNamespace(cgd_full=None)
+        self.model = ModelFacade(backend, num_dots)
         self.barrier_alpha = None
         self.gate_ground_truth = None
         self.num_dots = int(num_dots)
@@ -156,6 +194,7 @@ class QuantumDeviceEnv:
         if ep is not None and L is not None:                    # a new device brings its own window (window_delta)
             w = float(ep.params[0, L.scal + 2])
             self.array.obs_voltage_min, self.array.obs_voltage_max = -w, w
+            self.array.model.coulomb_peak_width = float(ep.params[0, L.scal + 1])
         return self._observation(obs), self._get_info()
 
     def step(self, action, skip_obs=False):

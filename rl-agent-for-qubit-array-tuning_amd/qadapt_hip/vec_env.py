@@ -329,6 +329,77 @@ class VecQuantumDeviceEnv:
         _lib.check(self._h, rc, "qd_probe_compose")
         return comp, plohi
 
+    # ------------------------------------------------------------------ point evaluation
+    def eval_points(self, env_ids, vg, vb, gamma=None, outputs=("signal", "occupations")):
+        """The reference model's point function (qd_eval_points): `charge_sensor_open(vg, vb)` and `ground_state_open(vg, vb)`
+        (TunnelCoupledChargeSensed.py:312-380) at arbitrary PHYSICAL voltages, on the devices of the listed envs.  Nothing of
+        the episodes changes and no noise stage runs; an env may be named many times.
+          env_ids   (n,) ints
+          vg        (n, m, N+1) physical gate voltages, sensor gate last (no virtual gate matrix is applied); vb (n, m, N-1);
+                    numpy or device tensors -- or lists of n arrays (m_i, N+1) / (m_i, N-1) of different lengths
+          gamma     None (each env's own coulomb_peak_width), a scalar or (n,) peak widths
+          outputs   which of "signal" and "occupations" to compute.  The signal is solved from the kept states in the order
+                    qd_observe and qd_probe solve them (their bits), the occupations from the reference order a validate
+                    handle keeps (the bits of `occupations()`); with num_charge_states 8, 16 or 32 those orders differ and
+                    asking for both runs the ground-state stage twice
+        Returns device tensors {"signal": (n, m) float64, "occupations": (n, m, N) float64}; for list input, lists of n
+        tensors (m_i,) and (m_i, N)."""
+        outputs = tuple(outputs)
+        if not outputs or any(o not in ("signal", "occupations") for o in outputs):
+            raise ValueError(f"outputs must name 'signal' and / or 'occupations', got {outputs!r}")
+        N, C = self.N, self.C
+        ids = np.asarray(env_ids.detach().cpu().numpy() if isinstance(env_ids, torch.Tensor) else env_ids, np.int32).reshape(-1)
+        n = int(ids.size)
+        ragged = isinstance(vg, (list, tuple))
+        if ragged != isinstance(vb, (list, tuple)):
+            raise ValueError("vg and vb must both be arrays or both be lists of per-env arrays")
+
+        def rows(x, width):
+            if isinstance(x, torch.Tensor):
+                return x.to(device=self.device, dtype=torch.float64).reshape(-1, width)
+            a = np.asarray(x, np.float64).reshape(-1, width)
+            return self._to_dev(a, torch.float64, a.shape)
+
+        if ragged:
+            if len(vg) != n or len(vb) != n:
+                raise ValueError(f"{n} env ids, {len(vg)} vg arrays and {len(vb)} vb arrays")
+            gs, bs = [rows(x, N + 1) for x in vg], [rows(x, C) for x in vb]
+            counts = [int(g.shape[0]) for g in gs]
+            if counts != [int(b.shape[0]) for b in bs]:
+                raise ValueError("vg and vb hold different numbers of points")
+            g_all = torch.cat(gs) if gs else torch.empty((0, N + 1), dtype=torch.float64, device=self.device)
+            b_all = torch.cat(bs) if bs else torch.empty((0, C), dtype=torch.float64, device=self.device)
+        else:
+            lead = tuple(vg.shape[:-1])
+            if len(lead) != 2 or lead[0] != n or vg.shape[-1] != N + 1 or tuple(vb.shape) != lead + (C,):
+                raise ValueError(f"vg must be ({n}, m, {N + 1}) and vb ({n}, m, {C}); got {tuple(vg.shape)} and {tuple(vb.shape)}")
+            counts = [int(lead[1])] * n
+            g_all, b_all = rows(vg, N + 1), rows(vb, C)
+        g_all, b_all = g_all.contiguous(), b_all.contiguous()
+        start = np.zeros(n + 1, np.int64)
+        start[1:] = np.cumsum(counts)
+        total = int(start[-1])
+        gam = None
+        if gamma is not None:
+            gam = np.ascontiguousarray(np.broadcast_to(np.asarray(
+                gamma.detach().cpu().numpy() if isinstance(gamma, torch.Tensor) else gamma, np.float64), (n,)))
+        signal = torch.empty((total,), dtype=torch.float64, device=self.device) if "signal" in outputs else None
+        occ = torch.empty((total, N), dtype=torch.float64, device=self.device) if "occupations" in outputs else None
+        rc = 0 if total == 0 else self._lib.qd_eval_points(          # (an empty tensor has no address to hand over)
+            self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
+            ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
+            None if gam is None else gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+            None if signal is None else ctypes.c_void_p(signal.data_ptr()),
+            None if occ is None else ctypes.c_void_p(occ.data_ptr()), self._stream())
+        _lib.check(self._h, rc, "qd_eval_points")
+        out = {}
+        m = counts[0] if n else 0
+        if signal is not None:
+            out["signal"] = [signal[start[i]:start[i + 1]] for i in range(n)] if ragged else signal.reshape(n, m)
+        if occ is not None:
+            out["occupations"] = [occ[start[i]:start[i + 1]] for i in range(n)] if ragged else occ.reshape(n, m, N)
+        return out
+
     # ------------------------------------------------------------------ reset
     def load_new_devices(self, env_ids=None, seed=None):
         """Sample new random devices for the listed envs and upload their parameter / initial
