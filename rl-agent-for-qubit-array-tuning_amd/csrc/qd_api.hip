@@ -11,63 +11,63 @@
 #include "qd_fullspace.h"
 #include "qd_probe.h"
 #include "qd_points.h"
+#include "qd_scratch.h"
+
+// The owners of a stream and of an event.  With the two memory policies of qd_scratch.h these are the only places that
+// allocate, create, free or destroy.
+struct QdStream : QdNoCopy {
+    hipStream_t s = nullptr;
+    ~QdStream() { if (s) (void)hipStreamDestroy(s); }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+};
+struct QdEvent : QdNoCopy {
+    hipEvent_t e = nullptr;
+    ~QdEvent() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDisableTiming) { return hipEventCreateWithFlags(&e, flags); }
+};
 
 // Scratch + streams of one launch chunk in flight.  Product mode keeps TWO: consecutive chunks alternate between them on
 // two internal streams, so the candidate search of one chunk (float64 VALU bound) runs beside the ground-state stage of
 // the other (its solve / select launches wait on memory most of the time).
 #define QD_MAX_LANES 4
 struct QdLane {
-    QdPixelRec* recs;                                  // [chunk][C][P] candidate records (validate mode: all B envs)
-    unsigned char* slabs;                              // scratch of the ground-state kernels: one slab per batch of ppb pixels in flight
-    unsigned* gtiles;                                  // [QD_GS_NBIN] tiles per size class of the launch in flight, then the tile lists
-    unsigned char* wide;                               // the wide class's lists (full space with a sector above 32 states)
-    hipStream_t run, side, side2;                      // the solve launches of the size classes run on three streams: the memory solver
-    hipEvent_t ev_fork, ev_join, ev_join2, ev_done;    // of the rare 13..32-state blocks is one long latency chain, and the short
+    QdDev<QdPixelRec> recs;                            // [chunk][C][P] candidate records (validate mode: all B envs)
+    QdDev<unsigned char> slabs;                        // scratch of the ground-state kernels: one slab per batch of ppb pixels in flight
+    QdDev<unsigned> gtiles;                            // [QD_GS_NBIN] tiles per size class of the launch in flight, then the tile lists
+    QdDev<unsigned char> wide;                         // the wide class's lists (full space with a sector above 32 states)
+    QdStream run, side, side2;                         // the solve launches of the size classes run on three streams: the memory solver
+    QdEvent ev_fork, ev_join, ev_join2, ev_done;       // of the rare 13..32-state blocks is one long latency chain, and the short
 };                                                     // register-solver launches fill each other's tails
 
-struct qd_handle {
-    qd_config cfg;
-    QdLane lanes[QD_MAX_LANES]; int nlanes;
-    hipEvent_t ev_start;
-    int device;
-    QdLayout L;
-    int N, R, B, C, P;
-    int chunk;
-    double *params, *state, *zraw, *plohi, *occ, *eig;
-    int* steps;
-    float *gimg, *pimg, *bimg, *volt;
-    unsigned long long* tel; int tel_words;
-    unsigned long long* tstats;             // tile-search [0..15] and eigen-solver [16..31] counters (validate mode)
-    int tile_search;                        // 0: per-pixel search only; 1: tile-shared candidate search + exact redo pass
-    int kept, kc;                           // K = num_charge_states (1..32) and the kept-set size the candidate stage runs (8, 16, 32)
-    int full_m;                             // > 0: the untruncated space with at most full_m carriers per dot (qd_fullspace.h)
-    QdFullTab* ftab;                        //   its sector tables (device)
-    int full_spl;                           //   states per lane of its structure kernel (2, 4, 8)
-    QdWide wide;                            //   the wide class (sectors of 33..64 states): capw > 0 when the handle has one; buf is the lane's
-    int ppb;                                // pixels per ground-state batch (slab): QD_GS_PPB, or qd_full_ppb in the full space
-    int gs_chunk;                           // envs per ground-state launch (<= chunk)
-    size_t gs_batches;                      // slabs a lane holds = gs_chunk * C * batches per image
-    int cus;                                // compute units of the device
-    int solve_grid[QD_GS_NBIN];             // persistent blocks of qd_k_gs_solve per size class: as many as are resident at once
-    double* stage[2]; size_t stage_cap;     // pinned staging ring of qd_load_episodes (doubles per slot), one event per slot:
-    hipEvent_t stage_ev[2]; int stage_turn; //   the call returns without waiting for the stream
-    bool stage_busy[2];
-    unsigned long long obs_serial;
-    // probe scans (qd_probe): one launch chunk of parameter copies, state blocks, signals and percentiles, allocated by the
-    // first probe; the composite's compact channel, per-scan percentiles and select state (qd_probe_compose) likewise
-    double *pparams, *pstate, *pz, *pplohi;
-    double *cz, *cplohi; size_t cz_cap, cplohi_cap;
-    QdSelState* sel;
-    // point evaluation (qd_eval_points): parameter and state copies, sensor constants and occupations of the slots in flight,
-    // allocated by the first call
-    double *qparams, *qstate, *qz, *qocc;
-    mutable char err[512];                  // (the launchers take the handle const and still report through it)
+// Pinned two-slot staging ring of qd_load_episodes (doubles per slot) with one event per slot that says when the stream
+// has consumed it: the call returns without waiting for the stream.
+struct QdStageRing {
+    QdBuf<double, QdPinned> slot[2];
+    QdEvent ev[2];
+    bool busy[2] = {false, false}; int turn = 0;
+    ~QdStageRing() { for (int k = 0; k < 2; ++k) (void)wait(k); }      // (runs before the slots are freed)
+    hipError_t wait(int k) {
+        const hipError_t e = busy[k] ? hipEventSynchronize(ev[k].e) : hipSuccess;
+        if (e == hipSuccess) busy[k] = false;
+        return e;
+    }
+    // room for `need` doubles in both slots; growing waits for the slots in use
+    hipError_t room(size_t need) {
+        if (need <= slot[0].cap) return hipSuccess;
+        for (int k = 0; k < 2; ++k) {
+            if (hipError_t e = wait(k)) return e;
+            if (!ev[k].e) if (hipError_t e = ev[k].create()) return e;
+        }
+        QdBuf<double, QdPinned>* const both[] = {&slot[0], &slot[1]};
+        const size_t n[] = {need, need};
+        return qd_reserve_group(both, n);
+    }
+    // the next slot, free to be written
+    hipError_t take(int& k) { k = turn; turn ^= 1; return wait(k); }
 };
 
-static bool qd_validate(const qd_handle* h) { return (h->cfg.flags & QD_FLAG_VALIDATE) != 0; }
-
 // The per-env device buffers the hot launchers work on, handed to them as an argument: qd_env_bufs() is the view of the
-// handle's own envs, qd_probe fills one for its probe blocks starting from a zeroed object, so whatever a probe does not
+// handle's own envs, a QdScratchSet gives one of its blocks starting from a zeroed object, so whatever a probe does not
 // set reaches the kernels as nullptr / 0 and never as the envs' pointer.
 struct QdEnvBufs {
     double *params, *state, *zraw, *plohi, *occ, *eig;
@@ -76,11 +76,67 @@ struct QdEnvBufs {
     unsigned long long serial;              // number of the observation being rendered (Philox counter word)
 };
 
+// A second set of per-env buffers for the slots in flight of qd_probe or qd_eval_points: parameter copies, state blocks
+// and signals, with percentiles (probes) or occupations (points).  One group: all of them are there, or none.
+struct QdScratchSet {
+    QdDev<double> params, state, z, plohi, occ;
+    hipError_t reserve(const QdLayout& L, size_t CP, size_t slots, size_t plohi_per_slot, size_t occ_per_slot) {
+        QdDev<double>* const all[] = {&params, &state, &z, &plohi, &occ};
+        const size_t n[] = {slots * L.size, slots * L.s_size, slots * CP, slots * plohi_per_slot, slots * occ_per_slot};
+        return qd_reserve_group(all, n);
+    }
+    // without noise, eigenvalues or telegraph words
+    QdEnvBufs view() const {
+        QdEnvBufs b{};
+        b.params = params.p; b.state = state.p; b.zraw = z.p; b.plohi = plohi.p; b.occ = occ.p;
+        return b;
+    }
+};
+
+struct qd_handle {
+    qd_config cfg;
+    QdLane lanes[QD_MAX_LANES]; int nlanes;
+    QdEvent ev_start;
+    int device;
+    QdLayout L;
+    int N, R, B, C, P;
+    int chunk;
+    QdDev<double> params, state, zraw, plohi, occ, eig;
+    QdDev<int> steps;
+    float *gimg, *pimg, *bimg, *volt;
+    QdDev<unsigned long long> tel; int tel_words;
+    QdDev<unsigned long long> tstats;       // tile-search [0..15] and eigen-solver [16..31] counters (validate mode)
+    int tile_search;                        // 0: per-pixel search only; 1: tile-shared candidate search + exact redo pass
+    int kept, kc;                           // K = num_charge_states (1..32) and the kept-set size the candidate stage runs (8, 16, 32)
+    int full_m;                             // > 0: the untruncated space with at most full_m carriers per dot (qd_fullspace.h)
+    QdDev<QdFullTab> ftab;                  //   its sector tables (device)
+    int full_spl;                           //   states per lane of its structure kernel (2, 4, 8)
+    QdWide wide;                            //   the wide class (sectors of 33..64 states): capw > 0 when the handle has one; buf is the lane's
+    int ppb;                                // pixels per ground-state batch (slab): QD_GS_PPB, or qd_full_ppb in the full space
+    int gs_chunk;                           // envs per ground-state launch (<= chunk)
+    size_t gs_batches;                      // slabs a lane holds = gs_chunk * C * batches per image
+    int cus;                                // compute units of the device
+    int solve_grid[QD_GS_NBIN];             // persistent blocks of qd_k_gs_solve per size class: as many as are resident at once
+    QdStageRing stage;
+    unsigned long long obs_serial;
+    // probe scans (qd_probe): one launch chunk of parameter copies, state blocks, signals and percentiles, allocated by the
+    // first probe; the composite's compact channel, per-scan percentiles and select state (qd_probe_compose) likewise
+    QdScratchSet probe;
+    QdDev<double> cz, cplohi;
+    QdDev<QdSelState> sel;
+    // point evaluation (qd_eval_points): parameter and state copies, sensor constants and occupations of the slots in flight,
+    // allocated by the first call
+    QdScratchSet points;
+    mutable char err[512];                  // (the launchers take the handle const and still report through it)
+};
+
+static bool qd_validate(const qd_handle* h) { return (h->cfg.flags & QD_FLAG_VALIDATE) != 0; }
+
 static QdEnvBufs qd_env_bufs(const qd_handle* h) {
     QdEnvBufs b{};
-    b.params = h->params; b.state = h->state; b.zraw = h->zraw; b.plohi = h->plohi; b.occ = h->occ; b.eig = h->eig;
+    b.params = h->params.p; b.state = h->state.p; b.zraw = h->zraw.p; b.plohi = h->plohi.p; b.occ = h->occ.p; b.eig = h->eig.p;
     b.noise_flags = h->cfg.noise_flags;
-    b.tel = h->tel; b.tel_words = h->tel_words;
+    b.tel = h->tel.p; b.tel_words = h->tel_words;
     b.serial = h->obs_serial;
     return b;
 }
@@ -111,13 +167,8 @@ struct QdDeviceGuard {
 
 // two events that are destroyed on every exit path
 struct QdEventPair {
-    hipEvent_t a, b; bool ok;
-    QdEventPair() : a(nullptr), b(nullptr), ok(false) {
-        if (hipEventCreate(&a) != hipSuccess) { a = nullptr; return; }
-        if (hipEventCreate(&b) != hipSuccess) { b = nullptr; return; }
-        ok = true;
-    }
-    ~QdEventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    QdEvent a, b; bool ok;
+    QdEventPair() : ok(a.create(hipEventDefault) == hipSuccess && b.create(hipEventDefault) == hipSuccess) {}
 };
 
 #define QD_DISPATCH_N(N_, ...)                                                    \
@@ -195,7 +246,6 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
     if (cfg->num_charge_states < 0 && !qd_full_supported(cfg->n_dot, -cfg->num_charge_states)) return QD_ERR_ARG;
     qd_handle* h = new (std::nothrow) qd_handle();
     if (!h) return QD_ERR_NOMEM;
-    memset(h, 0, sizeof(*h));
     h->cfg = *cfg; h->device = device;
     h->N = cfg->n_dot; h->R = cfg->resolution; h->B = cfg->batch;
     h->C = h->N - 1; h->P = h->R * h->R; h->L = qd_layout(h->N);
@@ -214,8 +264,8 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
         if (h->ppb < 1) return qd_fail(h, QD_ERR_ARG, "the full charge-state space of this shape does not fit a slab");
         h->full_spl = qd_full_spl(ftab.M);
         if (qd_full_wide(ftab.maxsec)) h->wide.capw = (unsigned)((h->ppb * qd_full_wide_tasks(ftab) + 1) & ~1);
-        QD_HIP(hipMalloc(&h->ftab, sizeof(QdFullTab)));
-        QD_HIP(hipMemcpy(h->ftab, &ftab, sizeof(QdFullTab), hipMemcpyHostToDevice));
+        QD_HIP(h->ftab.reserve(1));
+        QD_HIP(hipMemcpy(h->ftab.p, &ftab, sizeof(QdFullTab), hipMemcpyHostToDevice));
     }
     const size_t per_env_rec = (size_t)h->C * h->P * sizeof(QdPixelRec);
     const size_t batches_per_env = (size_t)h->C * ((h->P + h->ppb - 1) / h->ppb);
@@ -267,48 +317,43 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
         h->cus = prop.multiProcessorCount;
     }
     QD_HIP(val ? qd_solve_grids<true>(h->cus, h->solve_grid) : qd_solve_grids<false>(h->cus, h->solve_grid));
-    QD_HIP(hipMalloc(&h->params, sizeof(double) * (size_t)h->B * h->L.size));
-    QD_HIP(hipMalloc(&h->state, sizeof(double) * (size_t)h->B * h->L.s_size));
-    QD_HIP(hipMalloc(&h->steps, sizeof(int) * (size_t)h->B));
-    QD_HIP(hipMalloc(&h->zraw, sizeof(double) * (size_t)h->B * h->C * h->P));
-    QD_HIP(hipMalloc(&h->plohi, sizeof(double) * 2 * (size_t)h->B));
-    QD_HIP(hipEventCreateWithFlags(&h->ev_start, hipEventDisableTiming));
+    QD_HIP(h->params.reserve((size_t)h->B * h->L.size));
+    QD_HIP(h->state.reserve((size_t)h->B * h->L.s_size));
+    QD_HIP(h->steps.reserve((size_t)h->B));
+    QD_HIP(h->zraw.reserve((size_t)h->B * h->C * h->P));
+    QD_HIP(h->plohi.reserve(2 * (size_t)h->B));
+    QD_HIP(h->ev_start.create());
     for (int k = 0; k < h->nlanes; ++k) {
         QdLane& ln = h->lanes[k];
-        QD_HIP(hipMalloc(&ln.recs, per_env_rec * (size_t)h->chunk));
-        QD_HIP(hipStreamCreateWithFlags(&ln.run, hipStreamNonBlocking));
-        QD_HIP(hipStreamCreateWithFlags(&ln.side, hipStreamNonBlocking));
-        QD_HIP(hipStreamCreateWithFlags(&ln.side2, hipStreamNonBlocking));
-        QD_HIP(hipEventCreateWithFlags(&ln.ev_fork, hipEventDisableTiming));
-        QD_HIP(hipEventCreateWithFlags(&ln.ev_join, hipEventDisableTiming));
-        QD_HIP(hipEventCreateWithFlags(&ln.ev_join2, hipEventDisableTiming));
-        QD_HIP(hipEventCreateWithFlags(&ln.ev_done, hipEventDisableTiming));
+        QD_HIP(ln.recs.reserve(per_env_rec / sizeof(QdPixelRec) * (size_t)h->chunk));
+        for (QdStream* q : {&ln.run, &ln.side, &ln.side2}) QD_HIP(q->create());
+        for (QdEvent* ev : {&ln.ev_fork, &ln.ev_join, &ln.ev_join2, &ln.ev_done}) QD_HIP(ev->create());
     }
     h->tel_words = (h->P + 63) / 64;
     if (cfg->noise_flags & QD_NOISE_SENSOR) {
-        QD_HIP(hipMalloc(&h->tel, sizeof(unsigned long long) * (size_t)h->B * h->C * h->tel_words));
-        QD_HIP(hipMemset(h->tel, 0, sizeof(unsigned long long) * (size_t)h->B * h->C * h->tel_words));
+        QD_HIP(h->tel.reserve((size_t)h->B * h->C * h->tel_words));
+        QD_HIP(hipMemset(h->tel.p, 0, sizeof(unsigned long long) * (size_t)h->B * h->C * h->tel_words));
     }
     if ((cfg->flags & QD_FLAG_VALIDATE) || (cfg->noise_flags & QD_NOISE_LATCH))
-        QD_HIP(hipMalloc(&h->occ, sizeof(double) * (size_t)h->B * h->C * h->P * h->N));
+        QD_HIP(h->occ.reserve((size_t)h->B * h->C * h->P * h->N));
     // the tile-shared search pays off where neighbouring pixels are close in voltage (fine grids) and needs >= 32
     // candidates valid across a tile (N >= 4); otherwise every pixel is searched on its own
     h->tile_search = (h->N >= 4 && h->R >= 32 && !(cfg->flags & QD_FLAG_PIXEL_SEARCH) && !h->full_m) ? 1 : 0;
     for (int k = 0; k < h->nlanes; ++k) {
-        QD_HIP(hipMalloc(&h->lanes[k].slabs, h->gs_batches * qd_gs_slab_bytes(val)));
-        QD_HIP(hipMalloc(&h->lanes[k].gtiles, sizeof(unsigned) * (16 + qd_gs_tile_off(QD_GS_NBIN, h->gs_batches))));
-        if (h->wide.capw) QD_HIP(hipMalloc(&h->lanes[k].wide, h->gs_batches * qd_wide_bytes(h->wide.capw)));
+        QD_HIP(h->lanes[k].slabs.reserve(h->gs_batches * qd_gs_slab_bytes(val)));
+        QD_HIP(h->lanes[k].gtiles.reserve(16 + qd_gs_tile_off(QD_GS_NBIN, h->gs_batches)));
+        if (h->wide.capw) QD_HIP(h->lanes[k].wide.reserve(h->gs_batches * qd_wide_bytes(h->wide.capw)));
     }
     if (cfg->flags & QD_FLAG_VALIDATE) {
-        QD_HIP(hipMalloc(&h->tstats, sizeof(unsigned long long) * 32));
-        QD_HIP(hipMemset(h->tstats, 0, sizeof(unsigned long long) * 32));
-        QD_HIP(hipMalloc(&h->eig, sizeof(double) * 2 * (size_t)h->B * h->C * h->P));
-        QD_HIP(hipMemset(h->eig, 0, sizeof(double) * 2 * (size_t)h->B * h->C * h->P));
+        QD_HIP(h->tstats.reserve(32));
+        QD_HIP(hipMemset(h->tstats.p, 0, sizeof(unsigned long long) * 32));
+        QD_HIP(h->eig.reserve(2 * (size_t)h->B * h->C * h->P));
+        QD_HIP(hipMemset(h->eig.p, 0, sizeof(double) * 2 * (size_t)h->B * h->C * h->P));
     }
-    QD_HIP(hipMemset(h->params, 0, sizeof(double) * (size_t)h->B * h->L.size));
-    QD_HIP(hipMemset(h->steps, 0, sizeof(int) * (size_t)h->B));
-    QD_HIP(hipMemset(h->zraw, 0, sizeof(double) * (size_t)h->B * h->C * h->P));
-    QD_HIP(hipMemset(h->plohi, 0, sizeof(double) * 2 * (size_t)h->B));
+    QD_HIP(hipMemset(h->params.p, 0, sizeof(double) * (size_t)h->B * h->L.size));
+    QD_HIP(hipMemset(h->steps.p, 0, sizeof(int) * (size_t)h->B));
+    QD_HIP(hipMemset(h->zraw.p, 0, sizeof(double) * (size_t)h->B * h->C * h->P));
+    QD_HIP(hipMemset(h->plohi.p, 0, sizeof(double) * 2 * (size_t)h->B));
     // Kalman priors into every env's state block
     {
         const int N = h->N;
@@ -319,7 +364,7 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
             for (int i = 0; i < N + 1; ++i) st[h->L.s_vgm + i * (N + 1) + i] = -1.0;
             qd_kalman_priors(*cfg, N, st + h->L.s_kmean, st + h->L.s_kvar);
         }
-        hipError_t e_ = hipMemcpy(h->state, host, sizeof(double) * (size_t)h->B * h->L.s_size, hipMemcpyHostToDevice);
+        hipError_t e_ = hipMemcpy(h->state.p, host, sizeof(double) * (size_t)h->B * h->L.s_size, hipMemcpyHostToDevice);
         free(host);
         if (e_ != hipSuccess) return qd_fail(h, QD_ERR_HIP, "hipMemcpy(state)", e_);
     }
@@ -330,27 +375,6 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
 extern "C" int qd_destroy(qd_handle* h) {
     if (!h) return QD_ERR_ARG;
     QdDeviceGuard guard_(h->device);
-    void* bufs[] = {h->params, h->state, h->steps, h->zraw, h->plohi, h->occ, h->tel, h->eig, h->tstats, h->ftab,
-                    h->pparams, h->pstate, h->pz, h->pplohi, h->cz, h->cplohi, h->sel,
-                    h->qparams, h->qstate, h->qz, h->qocc};
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    for (int k = 0; k < QD_MAX_LANES; ++k) {
-        void* lb[] = {h->lanes[k].recs, h->lanes[k].slabs, h->lanes[k].gtiles, h->lanes[k].wide};
-        for (void* b : lb) if (b) (void)hipFree(b);
-    }
-    for (int k = 0; k < 2; ++k) {
-        if (h->stage_busy[k]) (void)hipEventSynchronize(h->stage_ev[k]);
-        if (h->stage[k]) (void)hipHostFree(h->stage[k]);
-        if (h->stage_ev[k]) (void)hipEventDestroy(h->stage_ev[k]);
-    }
-    for (int k = 0; k < QD_MAX_LANES; ++k) {
-        QdLane& ln = h->lanes[k];
-        hipStream_t st[] = {ln.run, ln.side, ln.side2};
-        for (hipStream_t q : st) if (q) (void)hipStreamDestroy(q);
-        hipEvent_t evs[] = {ln.ev_fork, ln.ev_join, ln.ev_join2, ln.ev_done};
-        for (hipEvent_t ev : evs) if (ev) (void)hipEventDestroy(ev);
-    }
-    if (h->ev_start) (void)hipEventDestroy(h->ev_start);
     delete h;
     return QD_OK;
 }
@@ -379,21 +403,10 @@ extern "C" int qd_load_episodes(qd_handle* h, const int32_t* env_ids, int n, con
     // to queue the resets' observation and the next step while the GPU is still busy with the previous one.
     const size_t prow = (size_t)L.size, srow = (size_t)L.s_size;
     const size_t need = (size_t)n * (prow + srow);
-    if (need > h->stage_cap) {
-        for (int k = 0; k < 2; ++k) {
-            if (h->stage_busy[k]) { QD_HIP(hipEventSynchronize(h->stage_ev[k])); h->stage_busy[k] = false; }
-            if (h->stage[k]) { QD_HIP(hipHostFree(h->stage[k])); h->stage[k] = nullptr; }
-        }
-        size_t cap = need < (size_t)64 * (prow + srow) ? (size_t)64 * (prow + srow) : need;
-        for (int k = 0; k < 2; ++k) {
-            QD_HIP(hipHostMalloc((void**)&h->stage[k], sizeof(double) * cap, hipHostMallocDefault));
-            if (!h->stage_ev[k]) QD_HIP(hipEventCreateWithFlags(&h->stage_ev[k], hipEventDisableTiming));
-        }
-        h->stage_cap = cap;
-    }
-    const int slot = h->stage_turn; h->stage_turn ^= 1;
-    if (h->stage_busy[slot]) { QD_HIP(hipEventSynchronize(h->stage_ev[slot])); h->stage_busy[slot] = false; }
-    double* sp = h->stage[slot];
+    QD_HIP(h->stage.room(need < (size_t)64 * (prow + srow) ? (size_t)64 * (prow + srow) : need));   // (64 rows at the least)
+    int slot;
+    QD_HIP(h->stage.take(slot));
+    double* sp = h->stage.slot[slot].p;
     double* ss = sp + (size_t)n * prow;
     memcpy(sp, params, sizeof(double) * (size_t)n * prow);
     memcpy(ss, state, sizeof(double) * (size_t)n * srow);
@@ -412,23 +425,23 @@ extern "C" int qd_load_episodes(qd_handle* h, const int32_t* env_ids, int n, con
     hipError_t er = hipSuccess;
     if (contiguous) {
         const int e0 = env_ids[0];
-        er = hipMemcpyAsync(h->params + (size_t)e0 * prow, sp, sizeof(double) * prow * n, hipMemcpyHostToDevice, s);
+        er = hipMemcpyAsync(h->params.p + (size_t)e0 * prow, sp, sizeof(double) * prow * n, hipMemcpyHostToDevice, s);
         if (er == hipSuccess)
-            er = hipMemcpy2DAsync(h->state + (size_t)e0 * srow, sizeof(double) * srow, ss,
+            er = hipMemcpy2DAsync(h->state.p + (size_t)e0 * srow, sizeof(double) * srow, ss,
                                   sizeof(double) * srow, sizeof(double) * width, n, hipMemcpyHostToDevice, s);
-        if (er == hipSuccess) er = hipMemsetAsync(h->steps + e0, 0, sizeof(int) * n, s);
+        if (er == hipSuccess) er = hipMemsetAsync(h->steps.p + e0, 0, sizeof(int) * n, s);
     } else {
         for (int k = 0; k < n && er == hipSuccess; ++k) {
             const int e = env_ids[k];
-            er = hipMemcpyAsync(h->params + (size_t)e * prow, sp + (size_t)k * prow, sizeof(double) * prow, hipMemcpyHostToDevice, s);
+            er = hipMemcpyAsync(h->params.p + (size_t)e * prow, sp + (size_t)k * prow, sizeof(double) * prow, hipMemcpyHostToDevice, s);
             if (er == hipSuccess)
-                er = hipMemcpyAsync(h->state + (size_t)e * srow, ss + (size_t)k * srow, sizeof(double) * width, hipMemcpyHostToDevice, s);
-            if (er == hipSuccess) er = hipMemsetAsync(h->steps + e, 0, sizeof(int), s);
+                er = hipMemcpyAsync(h->state.p + (size_t)e * srow, ss + (size_t)k * srow, sizeof(double) * width, hipMemcpyHostToDevice, s);
+            if (er == hipSuccess) er = hipMemsetAsync(h->steps.p + e, 0, sizeof(int), s);
         }
     }
-    if (er == hipSuccess) er = hipEventRecord(h->stage_ev[slot], s);
+    if (er == hipSuccess) er = hipEventRecord(h->stage.ev[slot].e, s);
     if (er != hipSuccess) return qd_fail(h, QD_ERR_HIP, "qd_load_episodes: copy", er);
-    h->stage_busy[slot] = true;
+    h->stage.busy[slot] = true;
     return QD_OK;
 }
 
@@ -441,8 +454,8 @@ extern "C" int qd_apply_actions(qd_handle* h, const float* actions, double* rewa
                    c.use_deltas, c.sparse_reward, c.gate_curve_type, c.delta_max, c.gate_curve_exponent,
                    c.plunger_radius, c.outer_plunger_radius, c.outer_plunger_reward_max, c.barrier_radius};
     const int blk = 64, grd = (h->B + blk - 1) / blk;
-    QD_DISPATCH_N(h->N, qd_k_actions<NN><<<dim3(grd), dim3(blk), 0, s>>>(h->B, h->params,
-                                            h->state, h->steps, actions, rewards, truncated, rc));
+    QD_DISPATCH_N(h->N, qd_k_actions<NN><<<dim3(grd), dim3(blk), 0, s>>>(h->B, h->params.p,
+                                            h->state.p, h->steps.p, actions, rewards, truncated, rc));
     QD_HIP(hipGetLastError());
     return QD_OK;
 }
@@ -480,7 +493,7 @@ template <int BIN>
 static hipError_t qd_launch_solve(const qd_handle* h, const QdLane& ln, hipStream_t s) {   // s: the stream this size class runs on
     const dim3 grid((unsigned)h->solve_grid[BIN]);
     QD_DISPATCH_BOOL(qd_validate(h), VAL,
-                     qd_k_gs_solve<BIN, VAL><<<grid, dim3(256), 0, s>>>(ln.slabs, ln.gtiles, ln.gtiles + 16, h->gs_batches, h->tstats));
+                     qd_k_gs_solve<BIN, VAL><<<grid, dim3(256), 0, s>>>(ln.slabs.p, ln.gtiles.p, ln.gtiles.p + 16, h->gs_batches, h->tstats.p));
     return hipGetLastError();
 }
 
@@ -489,9 +502,9 @@ static hipError_t qd_launch_solve(const qd_handle* h, const QdLane& ln, hipStrea
 static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, const int32_t* env_ids, int base, int cnt,
                             hipStream_t s, int st) {
     const int nb = (h->P + h->ppb - 1) / h->ppb;
-    unsigned* tilelist = ln.gtiles + 16;
+    unsigned* tilelist = ln.gtiles.p + 16;
     const bool val = qd_validate(h);
-    QdWide wide = h->wide; wide.buf = ln.wide;
+    QdWide wide = h->wide; wide.buf = ln.wide.p;
     // records: product mode keeps one launch chunk (slot = position in the chunk), validate mode all envs (position in the list)
     const int rec0 = val ? base : 0;
     for (int off = 0; off < cnt; off += h->gs_chunk) {
@@ -499,7 +512,7 @@ static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane
         const QdGsGeom g{n, h->C, h->P, nb};
         const unsigned batches = (unsigned)((size_t)n * h->C * nb);
         if (st & QD_ST_STRUCTURE) {
-            QD_HIP(hipMemsetAsync(ln.gtiles, 0, sizeof(unsigned) * 16, s));
+            QD_HIP(hipMemsetAsync(ln.gtiles.p, 0, sizeof(unsigned) * 16, s));
             if (h->full_m) {
                 // (shapes without a sector above 32 states have M <= 128: the kernel without the wide class, 2 states per lane)
 #define QD_DISPATCH_FULL(...)                                                                                  \
@@ -509,14 +522,14 @@ static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane
                 else { constexpr int SPL = 8; constexpr bool WIDE = true; __VA_ARGS__; }
                 QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_FULL(QD_DISPATCH_N(h->N,
                     qd_k_full_structure<NN, VAL, SPL, WIDE><<<dim3(batches), dim3(64 * QdFullWpb<SPL>::v), 0, s>>>(env_ids, base + off,
-                        rec0 + off, g, h->ppb, h->R, b.params, b.state, b.noise_flags, h->ftab, ln.recs, ln.slabs, ln.gtiles, tilelist,
+                        rec0 + off, g, h->ppb, h->R, b.params, b.state, b.noise_flags, h->ftab.p, ln.recs.p, ln.slabs.p, ln.gtiles.p, tilelist,
                         h->gs_batches, wide))));
 #undef QD_DISPATCH_FULL
             } else {
                 // (small launches: 16 waves per batch instead of 4, see the kernel)
                 QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_BOOL(batches < (unsigned)h->cus, SMALL, QD_DISPATCH_N(h->N,
                     qd_k_gs_structure<NN, VAL, (SMALL ? 16 : 4)><<<dim3(batches), dim3(64 * (SMALL ? 16 : 4)), 0, s>>>(env_ids, base + off,
-                        rec0 + off, g, h->R, b.params, ln.recs, b.state, b.noise_flags, ln.slabs, ln.gtiles, tilelist, h->gs_batches,
+                        rec0 + off, g, h->R, b.params, ln.recs.p, b.state, b.noise_flags, ln.slabs.p, ln.gtiles.p, tilelist, h->gs_batches,
                         h->kept))));
             }
             QD_HIP(hipGetLastError());
@@ -535,33 +548,33 @@ static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane
             } else if (h->kept < 2) max_bin = -1;
             else if (qd_gs_bin(h->kept) < max_bin) max_bin = qd_gs_bin(h->kept);
             const bool forked = max_bin >= 9;            // (8-dot, 4 envs: 1 760 -> 2 520 env-steps/s, 8 envs 3 390 -> 3 590; 2 and 3 dots have no memory-solver launch to hide)
-            hipStream_t s9 = forked ? ln.side : s, s48 = forked ? ln.side2 : s;
+            hipStream_t s9 = forked ? ln.side.s : s, s48 = forked ? ln.side2.s : s;
             if (forked) {
-                QD_HIP(hipEventRecord(ln.ev_fork, s));
-                QD_HIP(hipStreamWaitEvent(ln.side, ln.ev_fork, 0));
-                QD_HIP(hipStreamWaitEvent(ln.side2, ln.ev_fork, 0));
+                QD_HIP(hipEventRecord(ln.ev_fork.e, s));
+                QD_HIP(hipStreamWaitEvent(ln.side.s, ln.ev_fork.e, 0));
+                QD_HIP(hipStreamWaitEvent(ln.side2.s, ln.ev_fork.e, 0));
             }
             if (wide.capw) {                               // the wide class first: its tasks are the longest
                 const size_t slots = (size_t)batches * wide.capw, full = (size_t)h->cus * 4;
                 const dim3 wgrid((unsigned)(slots < full ? slots : full));
-                QD_DISPATCH_BOOL(val, VAL, qd_k_full_solve_wide<VAL><<<wgrid, dim3(64), 0, s>>>(ln.slabs, wide, batches, h->tstats));
+                QD_DISPATCH_BOOL(val, VAL, qd_k_full_solve_wide<VAL><<<wgrid, dim3(64), 0, s>>>(ln.slabs.p, wide, batches, h->tstats.p));
                 QD_HIP(hipGetLastError());
             }
             if (max_bin >= 9) QD_HIP(qd_launch_solve<9>(h, ln, s9));
-            if (forked) QD_HIP(hipEventRecord(ln.ev_join, ln.side));
+            if (forked) QD_HIP(hipEventRecord(ln.ev_join.e, ln.side.s));
             if (max_bin >= 8) QD_HIP(qd_launch_solve<8>(h, ln, s48));
             if (max_bin >= 7) QD_HIP(qd_launch_solve<7>(h, ln, s48));
             if (max_bin >= 6) QD_HIP(qd_launch_solve<6>(h, ln, s48));
             if (max_bin >= 5) QD_HIP(qd_launch_solve<5>(h, ln, s48));
             if (max_bin >= 4) QD_HIP(qd_launch_solve<4>(h, ln, s48));
-            if (forked) QD_HIP(hipEventRecord(ln.ev_join2, ln.side2));
+            if (forked) QD_HIP(hipEventRecord(ln.ev_join2.e, ln.side2.s));
             if (max_bin >= 0) QD_HIP(qd_launch_solve<0>(h, ln, s));
             if (max_bin >= 1) QD_HIP(qd_launch_solve<1>(h, ln, s));
             if (max_bin >= 2) QD_HIP(qd_launch_solve<2>(h, ln, s));
             if (max_bin >= 3) QD_HIP(qd_launch_solve<3>(h, ln, s));
             if (forked) {
-                QD_HIP(hipStreamWaitEvent(s, ln.ev_join, 0));
-                QD_HIP(hipStreamWaitEvent(s, ln.ev_join2, 0));
+                QD_HIP(hipStreamWaitEvent(s, ln.ev_join.e, 0));
+                QD_HIP(hipStreamWaitEvent(s, ln.ev_join2.e, 0));
             }
         }
         if (st & QD_ST_SELECT) {
@@ -569,11 +582,11 @@ static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane
                 const unsigned blk = (unsigned)((h->ppb + 63) / 64 * 64);
                 QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_BOOL(wide.capw != 0, WIDE, QD_DISPATCH_N(h->N,
                     qd_k_full_select<NN, VAL, WIDE><<<dim3(batches), dim3(blk), 0, s>>>(env_ids, base + off, rec0 + off, g, h->ppb,
-                        b.params, ln.recs, b.zraw, b.occ, b.state, b.noise_flags, b.eig, h->ftab, ln.slabs, wide))));
+                        b.params, ln.recs.p, b.zraw, b.occ, b.state, b.noise_flags, b.eig, h->ftab.p, ln.slabs.p, wide))));
             } else {
                 QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
                     qd_k_gs_select<NN, VAL, KK><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids, base + off, rec0 + off, g, h->R,
-                        b.params, ln.recs, b.zraw, b.occ, b.state, b.noise_flags, b.eig, ln.slabs))));
+                        b.params, ln.recs.p, b.zraw, b.occ, b.state, b.noise_flags, b.eig, ln.slabs.p))));
             }
             QD_HIP(hipGetLastError());
         }
@@ -602,14 +615,14 @@ static int qd_launch_csd(const qd_handle* h, const QdEnvBufs& b, const QdLane& l
     if (st & QD_ST_TILE) {
         const int tiles = ((h->R + 7) / 8) * ((h->R + 7) / 8);
         QD_DISPATCH_TILE(h->N, QD_DISPATCH_KC(h->kc, qd_k_tile<NN, KK><<<dim3(tiles, h->C, cnt), dim3(64), 0, s>>>(env_ids, base, h->R,
-                         b.params, b.state, ln.recs, sorted, b.noise_flags, h->tstats)));
+                         b.params, b.state, ln.recs.p, sorted, b.noise_flags, h->tstats.p)));
         QD_HIP(hipGetLastError());
     }
     if (st & QD_ST_REDO) {
         const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
         const dim3 g1(qd_cand_blocks(h->R), h->C, cnt);
         QD_DISPATCH_BOOL(h->tile_search != 0, TILED, QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
-            qd_k_candidates<NN, TILED, KK><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R, b.params, b.state, ln.recs, sorted,
+            qd_k_candidates<NN, TILED, KK><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R, b.params, b.state, ln.recs.p, sorted,
                                                                               b.noise_flags))));
         QD_HIP(hipGetLastError());
     }
@@ -655,20 +668,20 @@ extern "C" int qd_observe(qd_handle* h, const int32_t* env_ids, int n, void* str
         }
     } else {
         // consecutive chunks go round the lanes (own scratch, own stream): search and ground state of different chunks overlap
-        QD_HIP(hipEventRecord(h->ev_start, s));
-        for (int k = 0; k < h->nlanes; ++k) QD_HIP(hipStreamWaitEvent(h->lanes[k].run, h->ev_start, 0));
+        QD_HIP(hipEventRecord(h->ev_start.e, s));
+        for (int k = 0; k < h->nlanes; ++k) QD_HIP(hipStreamWaitEvent(h->lanes[k].run.s, h->ev_start.e, 0));
         // (measured: 2 lanes 11 520 env-steps/s, 3 lanes 10 920, 4 lanes 11 350; starting the second lane half a chunk out of
         // phase: 11 310 against 11 620 in the same run)
         int i = 0;
         for (int base = 0; base < n; base += h->chunk, ++i) {
             const int cnt = (n - base < h->chunk) ? n - base : h->chunk;
             const QdLane& ln = h->lanes[i % h->nlanes];
-            int rc = qd_launch_csd(h, b, ln, env_ids, base, cnt, ln.run, QD_ST_ALL);
+            int rc = qd_launch_csd(h, b, ln, env_ids, base, cnt, ln.run.s, QD_ST_ALL);
             if (rc) return rc;
         }
         for (int k = 0; k < h->nlanes; ++k) {
-            QD_HIP(hipEventRecord(h->lanes[k].ev_done, h->lanes[k].run));
-            QD_HIP(hipStreamWaitEvent(s, h->lanes[k].ev_done, 0));
+            QD_HIP(hipEventRecord(h->lanes[k].ev_done.e, h->lanes[k].run.s));
+            QD_HIP(hipStreamWaitEvent(s, h->lanes[k].ev_done.e, 0));
         }
     }
     if (b.noise_flags & QD_NOISE_LATCH) {
@@ -681,8 +694,8 @@ extern "C" int qd_observe(qd_handle* h, const int32_t* env_ids, int n, void* str
     QD_HIP(hipGetLastError());
     if (h->gimg || h->pimg || h->bimg || h->volt) {
         dim3 g4((h->P + 255) / 256, n);
-        QD_DISPATCH_N(h->N, qd_k_write_obs<NN><<<g4, dim3(256), 0, s>>>(env_ids, h->R, h->params,
-                                                h->state, h->zraw, h->plohi, h->gimg, h->pimg, h->bimg, h->volt));
+        QD_DISPATCH_N(h->N, qd_k_write_obs<NN><<<g4, dim3(256), 0, s>>>(env_ids, h->R, h->params.p,
+                                                h->state.p, h->zraw.p, h->plohi.p, h->gimg, h->pimg, h->bimg, h->volt));
         QD_HIP(hipGetLastError());
     }
     return QD_OK;
@@ -698,8 +711,8 @@ extern "C" int qd_update_capacitance(qd_handle* h, const int32_t* env_ids, int n
     QdKalmanCfg kc{h->cfg.kalman_variance_threshold, h->cfg.kalman_process_noise, h->cfg.update_method == QD_UPDATE_DIRECT ? 1 : 0,
                    h->cfg.cnn_outputs};
     const int blk = QD_UPD_BLOCK, grd = n;                           // one wave per env
-    QD_DISPATCH_N(h->N, qd_k_update<NN><<<dim3(grd), dim3(blk), 0, s>>>(env_ids, n, h->params,
-                                            h->state, values, log_vars, recompute_gt, kc));
+    QD_DISPATCH_N(h->N, qd_k_update<NN><<<dim3(grd), dim3(blk), 0, s>>>(env_ids, n, h->params.p,
+                                            h->state.p, values, log_vars, recompute_gt, kc));
     QD_HIP(hipGetLastError());
     return QD_OK;
 }
@@ -728,9 +741,9 @@ extern "C" int qd_snapshot(qd_handle* h, const int32_t* env_ids, int n, float* g
         {h->pimg, plunger_dst, (long long)sizeof(float) * N * P * 2},
         {h->bimg, barrier_dst, (long long)sizeof(float) * C * P},
         {h->volt, voltages_dst, (long long)sizeof(float) * (2 * N - 1)},
-        {h->state, state_dst, (long long)sizeof(double) * h->L.s_size},
-        {h->params, params_dst, (long long)sizeof(double) * h->L.size},
-        {h->steps, steps_dst, (long long)sizeof(int32_t)}};
+        {h->state.p, state_dst, (long long)sizeof(double) * h->L.s_size},
+        {h->params.p, params_dst, (long long)sizeof(double) * h->L.size},
+        {h->steps.p, steps_dst, (long long)sizeof(int32_t)}};
     QdSnapArgs a{};
     int k = 0;
     for (const auto& w : want)                            // unbound outputs and NULL destinations are skipped
@@ -755,26 +768,20 @@ extern "C" int qd_probe(qd_handle* h, const int32_t* env_of_query, int nq, const
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
     const int pc = h->chunk;                                  // queries in flight = envs per launch chunk (lane 0's scratch)
-    if (!h->pparams) {
-        QD_HIP(hipMalloc(&h->pparams, sizeof(double) * (size_t)pc * h->L.size));
-        QD_HIP(hipMalloc(&h->pstate, sizeof(double) * (size_t)pc * h->L.s_size));
-        QD_HIP(hipMalloc(&h->pz, sizeof(double) * (size_t)pc * h->C * h->P));
-        QD_HIP(hipMalloc(&h->pplohi, sizeof(double) * 2 * (size_t)pc));
-    }
+    QD_HIP(h->probe.reserve(h->L, (size_t)h->C * h->P, (size_t)pc, 2, 0));
     // the hot launchers run on the probe blocks, without noise, occupations or eigenvalues; nothing of the envs is written
-    QdEnvBufs pb{};
-    pb.params = h->pparams; pb.state = h->pstate; pb.zraw = h->pz; pb.plohi = h->pplohi;
+    const QdEnvBufs pb = h->probe.view();
     const QdProbeQuery Q{env_of_query, gate_v, barrier_v, sensor_v, window};
     for (int base = 0; base < nq; base += pc) {
         const int cnt = nq - base < pc ? nq - base : pc;
-        qd_k_probe_gather<<<dim3(cnt), dim3(QD_PROBE_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params, h->state, h->pparams, h->pstate);
+        qd_k_probe_gather<<<dim3(cnt), dim3(QD_PROBE_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, pb.params, pb.state);
         QD_HIP(hipGetLastError());
         if (int rc = qd_launch_csd(h, pb, h->lanes[0], nullptr, 0, cnt, s, QD_ST_ALL)) return rc;
         if (int rc = qd_launch_sensor(h, pb, nullptr, cnt, s)) return rc;
         qd_launch_percentile(nullptr, (unsigned)cnt, (long)h->C * h->P, pb.zraw, pb.plohi, s);
         QD_HIP(hipGetLastError());
         if (raw_dst || image_dst || plohi_dst) {
-            qd_k_probe_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(env_of_query, base, h->B, h->C, h->P, h->pz, h->pplohi,
+            qd_k_probe_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(env_of_query, base, h->B, h->C, h->P, pb.zraw, pb.plohi,
                                                                                  raw_dst, image_dst, plohi_dst);
             QD_HIP(hipGetLastError());
         }
@@ -808,15 +815,9 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
     QD_ON_DEVICE(h);
     const int ps = qd_points_slots(h);
     const long long CP = (long long)h->C * h->P;
-    if (!h->qparams) {
-        QD_HIP(hipMalloc(&h->qparams, sizeof(double) * (size_t)ps * h->L.size));
-        QD_HIP(hipMalloc(&h->qstate, sizeof(double) * (size_t)ps * h->L.s_size));
-        QD_HIP(hipMalloc(&h->qz, sizeof(double) * (size_t)ps * CP));
-        QD_HIP(hipMalloc(&h->qocc, sizeof(double) * (size_t)ps * CP * h->N));
-    }
+    QD_HIP(h->points.reserve(h->L, (size_t)CP, (size_t)ps, 0, (size_t)CP * h->N));
     // the ground-state launcher runs on the point buffers, without noise or eigenvalues; nothing of the envs is written
-    QdEnvBufs qb{};
-    qb.params = h->qparams; qb.state = h->qstate; qb.zraw = h->qz; qb.occ = h->qocc;
+    const QdEnvBufs qb = h->points.view();
     const QdLane& ln = h->lanes[0];
     const int sorted = h->kept != h->kc ? 1 : 0;              // as qd_launch_csd: K < KC takes the first K of the ordered list
     QdPointSlots T;
@@ -827,16 +828,16 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
     auto flush = [&]() -> int {
         if (n == 0) return QD_OK;
         const dim3 grid((unsigned)((CP + QD_POINTS_BLOCK - 1) / QD_POINTS_BLOCK), n);
-        qd_k_points_gather<<<dim3(n), dim3(QD_POINTS_BLOCK), 0, s>>>(T, h->N, h->params, h->state, h->qparams, h->qstate);
+        qd_k_points_gather<<<dim3(n), dim3(QD_POINTS_BLOCK), 0, s>>>(T, h->N, h->params.p, h->state.p, qb.params, qb.state);
         QD_HIP(hipGetLastError());
-        QD_DISPATCH_N(h->N, qd_k_points_front<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, vg, vb, h->qparams, ln.recs));
+        QD_DISPATCH_N(h->N, qd_k_points_front<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, vg, vb, qb.params, ln.recs.p));
         QD_HIP(hipGetLastError());
         // (launched directly: qd_launch_csd would pick the non-redo instantiation on handles without a tile search and
         // overwrite the front end)
         const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
         QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
             qd_k_candidates<NN, true, KK><<<dim3(qd_cand_blocks(h->R), h->C, n), dim3(QD_CAND_BLOCK), shm, s>>>(nullptr, 0, h->R,
-                h->qparams, h->qstate, ln.recs, sorted, 0)));
+                qb.params, qb.state, ln.recs.p, sorted, 0)));
         QD_HIP(hipGetLastError());
         // The signal comes from the list as the search left it, which is what qd_observe and qd_probe solve: the probe's bits.
         // The occupations come from the list in the reference order, which is what a validate handle solves and
@@ -845,17 +846,17 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
         if (signal_dst || !resort) {
             if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND)) return rc;
             if (signal_dst || occ_dst) {
-                QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, h->qparams, h->qz, h->qocc,
+                QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, qb.params, qb.zraw, qb.occ,
                                                                                                signal_dst, resort ? nullptr : occ_dst));
                 QD_HIP(hipGetLastError());
             }
         }
         if (resort) {
             const long nrec = (long)n * CP;
-            QD_DISPATCH_KC(h->kc, qd_k_points_sort<KK><<<dim3((unsigned)((nrec + 63) / 64)), dim3(64), 0, s>>>(ln.recs, nrec));
+            QD_DISPATCH_KC(h->kc, qd_k_points_sort<KK><<<dim3((unsigned)((nrec + 63) / 64)), dim3(64), 0, s>>>(ln.recs.p, nrec));
             QD_HIP(hipGetLastError());
             if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND)) return rc;
-            QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, h->qparams, h->qz, h->qocc,
+            QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, qb.params, qb.zraw, qb.occ,
                                                                                            nullptr, occ_dst));
             QD_HIP(hipGetLastError());
         }
@@ -891,30 +892,22 @@ static int qd_launch_select(qd_handle* h, const double* z, long n, double* plohi
     const long full = (long)h->cus * 8;
     if (blocks > full) blocks = full;
     if (blocks < 1) blocks = 1;
-    qd_k_sel_init<<<dim3(1), dim3(512), 0, s>>>(h->sel, ip[0], ip[1]);
+    qd_k_sel_init<<<dim3(1), dim3(512), 0, s>>>(h->sel.p, ip[0], ip[1]);
     for (int pass = 7; pass >= 0; --pass) {
-        qd_k_sel_hist<<<dim3((unsigned)blocks), dim3(QD_SEL_BLOCK), 0, s>>>(z, n, pass, h->sel);
-        qd_k_sel_pick<<<dim3(1), dim3(128), 0, s>>>(pass, h->sel);
+        qd_k_sel_hist<<<dim3((unsigned)blocks), dim3(QD_SEL_BLOCK), 0, s>>>(z, n, pass, h->sel.p);
+        qd_k_sel_pick<<<dim3(1), dim3(128), 0, s>>>(pass, h->sel.p);
     }
-    qd_k_sel_rank<<<dim3((unsigned)blocks), dim3(QD_SEL_BLOCK), 0, s>>>(z, n, h->sel);
-    qd_k_sel_finish<<<dim3(1), dim3(64), 0, s>>>(h->sel, ip[0], ip[1], in[0], in[1], g[0], g[1], plohi, plohi_dst);
+    qd_k_sel_rank<<<dim3((unsigned)blocks), dim3(QD_SEL_BLOCK), 0, s>>>(z, n, h->sel.p);
+    qd_k_sel_finish<<<dim3(1), dim3(64), 0, s>>>(h->sel.p, ip[0], ip[1], in[0], in[1], g[0], g[1], plohi, plohi_dst);
     QD_HIP(hipGetLastError());
     return QD_OK;
 }
 
+// the composite's compact channel, per-scan percentiles and select state
 static int qd_compose_scratch(qd_handle* h, size_t nq) {
-    const size_t need = nq * (size_t)h->P;
-    if (need > h->cz_cap) {
-        if (h->cz) { QD_HIP(hipFree(h->cz)); h->cz = nullptr; h->cz_cap = 0; }
-        QD_HIP(hipMalloc(&h->cz, sizeof(double) * need));
-        h->cz_cap = need;
-    }
-    if (nq > h->cplohi_cap) {
-        if (h->cplohi) { QD_HIP(hipFree(h->cplohi)); h->cplohi = nullptr; h->cplohi_cap = 0; }
-        QD_HIP(hipMalloc(&h->cplohi, sizeof(double) * 2 * nq));
-        h->cplohi_cap = nq;
-    }
-    if (!h->sel) QD_HIP(hipMalloc(&h->sel, sizeof(QdSelState)));
+    QD_HIP(h->cz.reserve(nq * (size_t)h->P));
+    QD_HIP(h->cplohi.reserve(2 * nq));
+    QD_HIP(h->sel.reserve(1));
     return QD_OK;
 }
 
@@ -936,18 +929,18 @@ extern "C" int qd_probe_compose(qd_handle* h, const double* raw, int nx, int ny,
     {
         long blocks = (n + 1023) / 1024;
         if (blocks > (long)h->cus * 8) blocks = (long)h->cus * 8;
-        qd_k_map_extract<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(raw, nq, h->C, h->P, channel, h->cz);
+        qd_k_map_extract<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(raw, nq, h->C, h->P, channel, h->cz.p);
         QD_HIP(hipGetLastError());
     }
     const int per_scan = mode == QD_MAP_PER_SCAN ? 1 : 0;
     if (per_scan) {
-        qd_launch_percentile(nullptr, (unsigned)nq, (long)h->P, h->cz, h->cplohi, s);
+        qd_launch_percentile(nullptr, (unsigned)nq, (long)h->P, h->cz.p, h->cplohi.p, s);
         QD_HIP(hipGetLastError());
     } else {
-        rc = qd_launch_select(h, h->cz, n, h->cplohi, plohi_dst, s);
+        rc = qd_launch_select(h, h->cz.p, n, h->cplohi.p, plohi_dst, s);
         if (rc) return rc;
     }
-    qd_k_map_place<<<dim3((h->P + 255) / 256, (unsigned)nq), dim3(256), 0, s>>>(h->cz, nx, ny, h->R, per_scan, per_scan, h->cplohi,
+    qd_k_map_place<<<dim3((h->P + 255) / 256, (unsigned)nq), dim3(256), 0, s>>>(h->cz.p, nx, ny, h->R, per_scan, per_scan, h->cplohi.p,
                                                                                composite_dst, plohi_dst);
     QD_HIP(hipGetLastError());
     return QD_OK;
@@ -962,12 +955,12 @@ static int qd_time_mean(const qd_handle* h, hipStream_t s, int rounds, int reps,
     float total = 0.f;
     for (int r = 0; r < rounds; ++r) {
         if (int rc = prep()) return rc;
-        QD_HIP(hipEventRecord(ev.a, s));
+        QD_HIP(hipEventRecord(ev.a.e, s));
         for (int i = 0; i < reps; ++i) if (int rc = timed()) return rc;
-        QD_HIP(hipEventRecord(ev.b, s));
-        QD_HIP(hipEventSynchronize(ev.b));
+        QD_HIP(hipEventRecord(ev.b.e, s));
+        QD_HIP(hipEventSynchronize(ev.b.e));
         float ms = 0.f;
-        QD_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+        QD_HIP(hipEventElapsedTime(&ms, ev.a.e, ev.b.e));
         total += ms;
     }
     *mean_ms = total / ((float)rounds * (float)reps);
@@ -982,7 +975,7 @@ extern "C" int qd_time_select(qd_handle* h, const double* z_dev, long long n, in
         return qd_fail(h, QD_ERR_ARG, "qd_time_select: bad argument");
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
-    if (!h->sel) QD_HIP(hipMalloc(&h->sel, sizeof(QdSelState)));
+    QD_HIP(h->sel.reserve(1));
     return qd_time_mean(h, s, 1, iters, [] { return QD_OK; }, [&]() -> int {
         if (!single_block) return qd_launch_select(h, z_dev, (long)n, out_dev, nullptr, s);
         qd_launch_percentile(nullptr, 1, (long)n, z_dev, out_dev, s);
@@ -995,32 +988,32 @@ extern "C" int qd_get_state(qd_handle* h, double* state, int32_t* steps) {
     if (!h) return QD_ERR_ARG;
     QD_ON_DEVICE(h);
     QD_HIP(hipDeviceSynchronize());
-    if (state) QD_HIP(hipMemcpy(state, h->state, sizeof(double) * (size_t)h->B * h->L.s_size, hipMemcpyDeviceToHost));
-    if (steps) QD_HIP(hipMemcpy(steps, h->steps, sizeof(int) * (size_t)h->B, hipMemcpyDeviceToHost));
+    if (state) QD_HIP(hipMemcpy(state, h->state.p, sizeof(double) * (size_t)h->B * h->L.s_size, hipMemcpyDeviceToHost));
+    if (steps) QD_HIP(hipMemcpy(steps, h->steps.p, sizeof(int) * (size_t)h->B, hipMemcpyDeviceToHost));
     return QD_OK;
 }
 extern "C" int qd_set_state(qd_handle* h, const double* state, const int32_t* steps) {
     if (!h) return QD_ERR_ARG;
     QD_ON_DEVICE(h);
     QD_HIP(hipDeviceSynchronize());
-    if (state) QD_HIP(hipMemcpy(h->state, state, sizeof(double) * (size_t)h->B * h->L.s_size, hipMemcpyHostToDevice));
-    if (steps) QD_HIP(hipMemcpy(h->steps, steps, sizeof(int) * (size_t)h->B, hipMemcpyHostToDevice));
+    if (state) QD_HIP(hipMemcpy(h->state.p, state, sizeof(double) * (size_t)h->B * h->L.s_size, hipMemcpyHostToDevice));
+    if (steps) QD_HIP(hipMemcpy(h->steps.p, steps, sizeof(int) * (size_t)h->B, hipMemcpyHostToDevice));
     return QD_OK;
 }
 extern "C" int qd_get_raw(qd_handle* h, double* raw, double* plohi) {
     if (!h) return QD_ERR_ARG;
     QD_ON_DEVICE(h);
     QD_HIP(hipDeviceSynchronize());
-    if (raw) QD_HIP(hipMemcpy(raw, h->zraw, sizeof(double) * (size_t)h->B * h->C * h->P, hipMemcpyDeviceToHost));
-    if (plohi) QD_HIP(hipMemcpy(plohi, h->plohi, sizeof(double) * 2 * (size_t)h->B, hipMemcpyDeviceToHost));
+    if (raw) QD_HIP(hipMemcpy(raw, h->zraw.p, sizeof(double) * (size_t)h->B * h->C * h->P, hipMemcpyDeviceToHost));
+    if (plohi) QD_HIP(hipMemcpy(plohi, h->plohi.p, sizeof(double) * 2 * (size_t)h->B, hipMemcpyDeviceToHost));
     return QD_OK;
 }
 extern "C" int qd_get_occupations(qd_handle* h, double* occ) {
     if (!h || !occ) return QD_ERR_ARG;
-    if (!h->occ) return qd_fail(h, QD_ERR_STATE, "qd_get_occupations needs QD_FLAG_VALIDATE");
+    if (!h->occ.p) return qd_fail(h, QD_ERR_STATE, "qd_get_occupations needs QD_FLAG_VALIDATE");
     QD_ON_DEVICE(h);
     QD_HIP(hipDeviceSynchronize());
-    QD_HIP(hipMemcpy(occ, h->occ, sizeof(double) * (size_t)h->B * h->C * h->P * h->N, hipMemcpyDeviceToHost));
+    QD_HIP(hipMemcpy(occ, h->occ.p, sizeof(double) * (size_t)h->B * h->C * h->P * h->N, hipMemcpyDeviceToHost));
     return QD_OK;
 }
 extern "C" int qd_get_candidates(qd_handle* h, int32_t* states) {
@@ -1038,7 +1031,7 @@ extern "C" int qd_get_candidates(qd_handle* h, int32_t* states) {
     const int N = h->N;
     for (size_t r0 = 0; r0 < nrec; r0 += slice) {
         const size_t cnt = nrec - r0 < slice ? nrec - r0 : slice;
-        hipError_t e_ = hipMemcpy(host, h->lanes[0].recs + r0, cnt * sizeof(QdPixelRec), hipMemcpyDeviceToHost);
+        hipError_t e_ = hipMemcpy(host, h->lanes[0].recs.p + r0, cnt * sizeof(QdPixelRec), hipMemcpyDeviceToHost);
         if (e_ != hipSuccess) { free(host); return qd_fail(h, QD_ERR_HIP, "hipMemcpy(recs)", e_); }
         // slots 0..K-1: the kept states (|0..0> padding from nvalid on); slots K..31: -1
         for (size_t r = 0; r < cnt; ++r) {
@@ -1057,28 +1050,28 @@ extern "C" int qd_get_candidates(qd_handle* h, int32_t* states) {
 
 extern "C" int qd_get_eigen(qd_handle* h, double* eig) {
     if (!h || !eig) return QD_ERR_ARG;
-    if (!h->eig) return qd_fail(h, QD_ERR_STATE, "qd_get_eigen needs QD_FLAG_VALIDATE");
+    if (!h->eig.p) return qd_fail(h, QD_ERR_STATE, "qd_get_eigen needs QD_FLAG_VALIDATE");
     QD_ON_DEVICE(h);
     QD_HIP(hipDeviceSynchronize());
-    QD_HIP(hipMemcpy(eig, h->eig, sizeof(double) * 2 * (size_t)h->B * h->C * h->P, hipMemcpyDeviceToHost));
+    QD_HIP(hipMemcpy(eig, h->eig.p, sizeof(double) * 2 * (size_t)h->B * h->C * h->P, hipMemcpyDeviceToHost));
     return QD_OK;
 }
 
 extern "C" int qd_get_search_stats(qd_handle* h, uint64_t* out16) {
     if (!h || !out16) return QD_ERR_ARG;
-    if (!h->tstats) return qd_fail(h, QD_ERR_STATE, "qd_get_search_stats needs QD_FLAG_VALIDATE");
+    if (!h->tstats.p) return qd_fail(h, QD_ERR_STATE, "qd_get_search_stats needs QD_FLAG_VALIDATE");
     QD_ON_DEVICE(h);
     QD_HIP(hipDeviceSynchronize());
-    QD_HIP(hipMemcpy(out16, h->tstats, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost));
+    QD_HIP(hipMemcpy(out16, h->tstats.p, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost));
     return QD_OK;
 }
 
 extern "C" int qd_get_solver_stats(qd_handle* h, uint64_t* out16) {
     if (!h || !out16) return QD_ERR_ARG;
-    if (!h->tstats) return qd_fail(h, QD_ERR_STATE, "qd_get_solver_stats needs QD_FLAG_VALIDATE");
+    if (!h->tstats.p) return qd_fail(h, QD_ERR_STATE, "qd_get_solver_stats needs QD_FLAG_VALIDATE");
     QD_ON_DEVICE(h);
     QD_HIP(hipDeviceSynchronize());
-    QD_HIP(hipMemcpy(out16, h->tstats + 16, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost));
+    QD_HIP(hipMemcpy(out16, h->tstats.p + 16, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost));
     return QD_OK;
 }
 

@@ -4,11 +4,13 @@
 // eigen-solver of the ground-state kernel can be checked against the oracle /
 // numpy in the no-GPU test tier.  It is NOT part of the product: nothing in
 // qadapt_hip loads it (the hop structure / task emission / selection phases of the
-// ground-state kernel only exist as HIP code).  Built by tests/hosttest/Makefile.
+// ground-state kernel only exist as HIP code).  It also drives the buffer owner of qd_scratch.h on a fake memory policy
+// (tests/test_scratch_cpu.py).  Built by tests/hosttest/Makefile.
 #include <string.h>
 #include "qd_pixel.h"
 #include "qd_rng.h"
 #include "qd_eig.h"
+#include "qd_scratch.h"
 #include <stdlib.h>
 
 template <int N>
@@ -100,4 +102,48 @@ extern "C" int qdh_eig_lowest(int s, const double* packed, double* lam, double* 
     memcpy(x, M + ne + 3 * s, sizeof(double) * s);
     free(M);
     return 0;
+}
+
+// ---- qd_scratch.h: QdBuf and qd_reserve_group on a memory policy that counts live blocks, records the sizes asked for,
+// fails the k-th next allocation on request, and checks IN alloc() that no more blocks are alive than buffers exist
+// (a growing buffer has given its old block back by then)
+struct QdhFake {
+    static long long live, limit, over, allocs, releases, last_bytes, fail_in;
+    static int alloc(void** p, size_t bytes) {
+        ++allocs; last_bytes = (long long)bytes;
+        if (live + 1 > limit) over = 1;
+        if (fail_in > 0 && --fail_in == 0) return 2;
+        *p = malloc(bytes);
+        if (!*p) return 2;
+        ++live;
+        return 0;
+    }
+    static int release(void* p) { ++releases; --live; free(p); return 0; }
+};
+long long QdhFake::live, QdhFake::limit, QdhFake::over, QdhFake::allocs, QdhFake::releases, QdhFake::last_bytes, QdhFake::fail_in;
+
+struct QdhScratch { QdBuf<double, QdhFake> b[4]; };
+
+// nbuf: how many of the four buffers the caller is going to use (the fake's bound on live blocks)
+extern "C" void* qdh_scr_new(int nbuf) {
+    QdhFake::live = QdhFake::over = QdhFake::allocs = QdhFake::releases = QdhFake::last_bytes = QdhFake::fail_in = 0;
+    QdhFake::limit = nbuf;
+    return new QdhScratch();
+}
+extern "C" void qdh_scr_delete(void* o) { delete (QdhScratch*)o; }
+extern "C" int qdh_scr_reserve(void* o, int k, long long n) { return ((QdhScratch*)o)->b[k].reserve((size_t)n); }
+extern "C" int qdh_scr_reserve_group(void* o, const long long* n4) {
+    QdhScratch* t = (QdhScratch*)o;
+    QdBuf<double, QdhFake>* const g[] = {&t->b[0], &t->b[1], &t->b[2], &t->b[3]};
+    const size_t n[] = {(size_t)n4[0], (size_t)n4[1], (size_t)n4[2], (size_t)n4[3]};
+    return qd_reserve_group(g, n);
+}
+extern "C" void qdh_scr_fail_in(int k) { QdhFake::fail_in = k; }
+// out[0..3]: the buffers' pointers (as integers), out[4..7]: their capacities
+extern "C" void qdh_scr_bufs(void* o, long long* out) {
+    for (int k = 0; k < 4; ++k) { out[k] = (long long)(size_t)((QdhScratch*)o)->b[k].p; out[4 + k] = (long long)((QdhScratch*)o)->b[k].cap; }
+}
+// out[0..4]: live blocks, bound exceeded (0 / 1), alloc calls, release calls, bytes of the last request
+extern "C" void qdh_scr_fake(long long* out) {
+    out[0] = QdhFake::live; out[1] = QdhFake::over; out[2] = QdhFake::allocs; out[3] = QdhFake::releases; out[4] = QdhFake::last_bytes;
 }
