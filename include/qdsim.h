@@ -201,9 +201,9 @@ int qd_snapshot(qd_handle* h, const int32_t* env_ids_dev, int n,
  *   image_dst        [nq][R][R][C] float32, normalised per query with its own 0.5 / 99.5 percentiles, as the
  *                                  global_image of qd_observe; may be NULL
  *   plohi_dst        [nq][2]       those percentiles; may be NULL
- * Probes are DETERMINISTIC: every launch runs with noise flags 0 whatever the handle's noise_flags are (no sensor noise,
- * no radial noise, no latching); stochastic probes are not built.  The hot kernels are the ones qd_observe runs, on
- * probe copies of the parameter and state blocks, so a probe at an env's own voltages, sensor voltage and window equals
+ * qd_probe is DETERMINISTIC: every launch runs with noise flags 0 whatever the handle's noise_flags are (no sensor noise,
+ * no radial noise, no latching); qd_probe_ex below runs the stochastic stages on the queries.  The hot kernels are the
+ * ones qd_observe runs, on probe copies of the parameter and state blocks, so a probe at an env's own voltages, sensor voltage and window equals
  * the raw signal, percentiles and image of a noise-free qd_observe bit for bit.
  * The call changes nothing that qd_step, qd_observe or any qd_get_* function can see: not the state blocks, step
  * counters or Kalman state, not the bound outputs, raw signal or percentiles of the last observe, not the observation
@@ -214,10 +214,56 @@ int qd_snapshot(qd_handle* h, const int32_t* env_ids_dev, int n,
  * nq == 0 does nothing.  QD_ERR_ARG, found without reading the device: nq < 0, env_of_query_dev, gate_v_dev or
  * barrier_v_dev NULL.  An id outside [0, B) leaves its destination slots untouched, as at qd_snapshot.  A handle created
  * with QD_FLAG_VALIDATE answers QD_ERR_STATE: its record, occupation and eigenvalue buffers hold B envs and belong to
- * the last observe.  Works for num_charge_states 1..32 and in the full charge-state space. */
+ * the last observe.  Works for num_charge_states 1..32 and in the full charge-state space.
+ * qd_probe(...) is qd_probe_ex(..., NULL, stream). */
 int qd_probe(qd_handle* h, const int32_t* env_of_query_dev, int nq, const double* gate_v_dev,
              const double* barrier_v_dev, const double* sensor_v_dev, const double* window_dev,
              double* raw_dst, float* image_dst, double* plohi_dst, void* stream);
+
+/* Probe scans with the stochastic stages and the occupations.  In the reference the stateless _get_obs is not
+ * deterministic: it runs the configured sensor noise, the radial noise or white-noise replacement and the latching model
+ * exactly as a step does (qarray_base_class.py:171-229, 444-493, TunnelCoupledChargeSensed.py:354, ground_state.py:164),
+ * and its point function returns (signal, n_open).  The ten data arguments are those of qd_probe; opts == NULL is
+ * qd_probe, bit for bit.
+ *   noise_flags   the QD_NOISE_* stages to run on the queries, whatever the handle was created with (0: none)
+ *   serial        the observation-number word of the Philox counter.  The caller owns it: two probes with the same
+ *                 serial, stream_base and query index draw the same numbers.  A step's serial (qd_get_rng_state) counts
+ *                 up from 1 and never reaches 2^63, so side questions should set the top bit: they then never share a
+ *                 stream with a step
+ *   stream_base   query q draws from the streams of global env id stream_base + q (low 32 bits), keyed by the handle's
+ *                 folded rng_seed
+ *   occ_dst       [nq][C][P][N] float64 DEVICE, layout of qd_get_occupations, or NULL: the occupations the signal was
+ *                 formed from, after latching if QD_NOISE_LATCH ran.  A channel that the radial stage replaced by white
+ *                 noise is never solved: its occupations are NaN.  Ids outside [0, B) leave their slots untouched.
+ *                 Asking for them only adds stores: the raw signal keeps the bits of a probe without occ_dst
+ * Per launch chunk the order is qd_observe's, on the probe buffers: gather, telegraph chains (SENSOR), candidate search
+ * and ground state (a replaced channel is skipped as in a step), latching (LATCH; one lane per raster row,
+ * csrc/qd_latch.h, same bits as the step's one-thread walk), sensor stage, percentiles, write.
+ * Contracts:
+ *   chunk independence   a query's results do not depend on qd_chunk_envs
+ *   nothing of the envs moves   state blocks, step counters, Kalman state, bound outputs, qd_get_raw,
+ *                        qd_get_occupations, qd_get_rng_state and the envs' telegraph words are as before the call
+ *   equivalence with a step   nq = B, env_of_query = 0..B-1, each env's own gate and barrier voltages and sensor slot,
+ *                        window_dev = NULL, noise_flags = the handle's, stream_base = env_id_offset, serial = S: raw,
+ *                        percentiles and image have the bits of the qd_observe whose observation number
+ *                        (qd_get_rng_state afterwards) is S, and with QD_NOISE_LATCH occ_dst has the bits of
+ *                        qd_get_occupations in every channel that was not replaced
+ * Scratch beyond qd_probe's, per query in flight: C*P*N doubles of occupations from the first call with QD_NOISE_LATCH or
+ * occ_dst, C*ceil(P/64) telegraph words from the first call with QD_NOISE_SENSOR; handles that never ask allocate
+ * nothing more than qd_probe does.  QD_ERR_ARG, found without touching the device, besides qd_probe's: a struct_size
+ * that is not sizeof(qd_probe_opts), a noise_flags bit outside QD_NOISE_SENSOR | QD_NOISE_RADIAL | QD_NOISE_LATCH.
+ * A QD_FLAG_VALIDATE handle answers QD_ERR_STATE.  Channel sub-ranges, asymmetric windows and a virtual gate matrix
+ * or noise centre per query are not built. */
+typedef struct qd_probe_opts {
+    int32_t  struct_size;   /* = sizeof(qd_probe_opts) */
+    int32_t  noise_flags;   /* QD_NOISE_* stages to run on the queries; 0 = none.  Independent of the handle's noise_flags */
+    uint64_t serial;        /* the observation-number word of the Philox counter */
+    int64_t  stream_base;   /* query q draws from the streams of global env id stream_base + q (mod 2^32) */
+    double*  occ_dst;       /* [nq][C][P][N] float64 DEVICE, layout of qd_get_occupations; or NULL */
+} qd_probe_opts;
+int qd_probe_ex(qd_handle* h, const int32_t* env_of_query_dev, int nq, const double* gate_v_dev,
+                const double* barrier_v_dev, const double* sensor_v_dev, const double* window_dev,
+                double* raw_dst, float* image_dst, double* plohi_dst, const qd_probe_opts* opts, void* stream);
 
 /* Point evaluation: TunnelCoupledChargeSensed.charge_sensor_open(vg, vb) -> (signal, n_open) and ground_state_open(vg, vb)
  * (TunnelCoupledChargeSensed.py:312-380, ground_state.py:24-166) at arbitrary PHYSICAL voltages, np points in one call:

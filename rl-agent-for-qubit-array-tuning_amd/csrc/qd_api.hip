@@ -10,6 +10,7 @@
 #include "qd_kernels.h"
 #include "qd_fullspace.h"
 #include "qd_probe.h"
+#include "qd_latch.h"
 #include "qd_points.h"
 #include "qd_scratch.h"
 
@@ -74,16 +75,25 @@ struct QdEnvBufs {
     int noise_flags;
     unsigned long long* tel; int tel_words;
     unsigned long long serial;              // number of the observation being rendered (Philox counter word)
+    uint32_t env_off;                       // global env id of block 0 (Philox key word = env_off + block index)
 };
 
 // A second set of per-env buffers for the slots in flight of qd_probe or qd_eval_points: parameter copies, state blocks
-// and signals, with percentiles (probes) or occupations (points).  One group: all of them are there, or none.
+// and signals, with percentiles (probes), occupations (points; probes that latch or hand them out) or telegraph words
+// (probes with sensor noise).  One group: all of them are there, or none.  A member asked for with 0 per slot keeps what
+// an earlier call gave it, so a set only grows.
 struct QdScratchSet {
     QdDev<double> params, state, z, plohi, occ;
-    hipError_t reserve(const QdLayout& L, size_t CP, size_t slots, size_t plohi_per_slot, size_t occ_per_slot) {
+    QdDev<unsigned long long> tel;
+    hipError_t reserve(const QdLayout& L, size_t CP, size_t slots, size_t plohi_per_slot, size_t occ_per_slot,
+                       size_t tel_per_slot = 0) {
         QdDev<double>* const all[] = {&params, &state, &z, &plohi, &occ};
         const size_t n[] = {slots * L.size, slots * L.s_size, slots * CP, slots * plohi_per_slot, slots * occ_per_slot};
-        return qd_reserve_group(all, n);
+        hipError_t e = qd_reserve_group(all, n);
+        if (e == hipSuccess && (e = tel.reserve(slots * tel_per_slot)) != hipSuccess)
+            for (QdDev<double>* b : all) b->release();
+        if (e != hipSuccess) tel.release();
+        return e;
     }
     // without noise, eigenvalues or telegraph words
     QdEnvBufs view() const {
@@ -138,6 +148,7 @@ static QdEnvBufs qd_env_bufs(const qd_handle* h) {
     b.noise_flags = h->cfg.noise_flags;
     b.tel = h->tel.p; b.tel_words = h->tel_words;
     b.serial = h->obs_serial;
+    b.env_off = (uint32_t)h->cfg.env_id_offset;
     return b;
 }
 
@@ -469,7 +480,7 @@ static QdNoiseCfg qd_noise_cfg(const qd_handle* h, const QdEnvBufs& b) {
     QdNoiseCfg nz;
     nz.flags = b.noise_flags;
     nz.seed = (uint32_t)(h->cfg.rng_seed ^ (h->cfg.rng_seed >> 32));
-    nz.env_off = (uint32_t)h->cfg.env_id_offset;
+    nz.env_off = b.env_off;
     nz.ser_lo = (uint32_t)b.serial; nz.ser_hi = (uint32_t)(b.serial >> 32);
     nz.tel = b.tel; nz.tel_words = b.tel_words;
     return nz;
@@ -754,29 +765,61 @@ extern "C" int qd_snapshot(qd_handle* h, const int32_t* env_ids, int n, float* g
     return QD_OK;
 }
 
-extern "C" int qd_probe(qd_handle* h, const int32_t* env_of_query, int nq, const double* gate_v, const double* barrier_v,
-                        const double* sensor_v, const double* window, double* raw_dst, float* image_dst, double* plohi_dst,
-                        void* stream) {
+extern "C" int qd_probe_ex(qd_handle* h, const int32_t* env_of_query, int nq, const double* gate_v, const double* barrier_v,
+                           const double* sensor_v, const double* window, double* raw_dst, float* image_dst, double* plohi_dst,
+                           const qd_probe_opts* opts, void* stream) {
     if (!h) return QD_ERR_ARG;
     if (nq < 0) return qd_fail(h, QD_ERR_ARG, "qd_probe: nq < 0");
     if (!env_of_query) return qd_fail(h, QD_ERR_ARG, "qd_probe: env_of_query_dev is NULL");
     if (!gate_v || !barrier_v) return qd_fail(h, QD_ERR_ARG, "qd_probe: gate_v_dev or barrier_v_dev is NULL");
+    if (opts && opts->struct_size != (int32_t)sizeof(qd_probe_opts))
+        return qd_fail(h, QD_ERR_ARG, "qd_probe_ex: opts->struct_size is not sizeof(qd_probe_opts)");
+    if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_RADIAL | QD_NOISE_LATCH)))
+        return qd_fail(h, QD_ERR_ARG, "qd_probe_ex: opts->noise_flags has a bit that is no QD_NOISE_* stage");
     if (h->cfg.flags & QD_FLAG_VALIDATE)
         return qd_fail(h, QD_ERR_STATE, "qd_probe: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
                                         "B envs' last observe and renders no probes; use a handle without the flag");
     if (nq == 0) return QD_OK;
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
+    const int flags = opts ? opts->noise_flags : 0;
+    double* const occ_dst = opts ? opts->occ_dst : nullptr;
+    const bool want_occ = (flags & QD_NOISE_LATCH) || occ_dst, want_tel = (flags & QD_NOISE_SENSOR) != 0;
     const int pc = h->chunk;                                  // queries in flight = envs per launch chunk (lane 0's scratch)
-    QD_HIP(h->probe.reserve(h->L, (size_t)h->C * h->P, (size_t)pc, 2, 0));
-    // the hot launchers run on the probe blocks, without noise, occupations or eigenvalues; nothing of the envs is written
-    const QdEnvBufs pb = h->probe.view();
+    const size_t CP = (size_t)h->C * h->P;
+    QD_HIP(h->probe.reserve(h->L, CP, (size_t)pc, 2, want_occ ? CP * h->N : 0, want_tel ? (size_t)h->C * h->tel_words : 0));
+    // the hot launchers run on the probe blocks, without eigenvalues; occupations, telegraph words and noise only as asked
+    // for, keyed by the caller's serial and stream base; nothing of the envs is written
+    QdEnvBufs pb = h->probe.view();
+    pb.occ = want_occ ? h->probe.occ.p : nullptr;
+    pb.noise_flags = flags;
+    if (want_tel) { pb.tel = h->probe.tel.p; pb.tel_words = h->tel_words; }
+    pb.serial = opts ? opts->serial : 0;
     const QdProbeQuery Q{env_of_query, gate_v, barrier_v, sensor_v, window};
     for (int base = 0; base < nq; base += pc) {
         const int cnt = nq - base < pc ? nq - base : pc;
+        pb.env_off = (uint32_t)((opts ? opts->stream_base : 0) + base);      // slot k of the chunk draws as global env stream_base + base + k
         qd_k_probe_gather<<<dim3(cnt), dim3(QD_PROBE_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, pb.params, pb.state);
         QD_HIP(hipGetLastError());
+        if (want_tel) {
+            const int nt = cnt * h->C;
+            qd_k_telegraph<<<dim3((nt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, h->C, h->P, h->L.size, h->L.noise, pb.params, pb.tel,
+                                                                     qd_noise_cfg(h, pb));
+            QD_HIP(hipGetLastError());
+        }
         if (int rc = qd_launch_csd(h, pb, h->lanes[0], nullptr, 0, cnt, s, QD_ST_ALL)) return rc;
+        if (flags & QD_NOISE_LATCH) {
+#ifdef QD_PROBE_SERIAL_LATCH        // (measurement only, DESIGN.md 7: the one-thread walk of qd_observe on the probe buffers)
+            QD_DISPATCH_N(h->N, qd_k_latch<NN><<<dim3((cnt * h->C + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, h->R, pb.params, pb.state,
+                                                                                               pb.occ, pb.zraw, qd_noise_cfg(h, pb)));
+#else
+            const long rows = (long)cnt * h->C * h->R;
+            QD_DISPATCH_N(h->N, qd_k_latch_rows<NN><<<dim3((unsigned)((rows + QD_LATCH_ROWS_BLOCK - 1) / QD_LATCH_ROWS_BLOCK)),
+                                                      dim3(QD_LATCH_ROWS_BLOCK), 0, s>>>(cnt, h->R, pb.params, pb.state, pb.occ, pb.zraw,
+                                                                                         qd_noise_cfg(h, pb)));
+#endif
+            QD_HIP(hipGetLastError());
+        }
         if (int rc = qd_launch_sensor(h, pb, nullptr, cnt, s)) return rc;
         qd_launch_percentile(nullptr, (unsigned)cnt, (long)h->C * h->P, pb.zraw, pb.plohi, s);
         QD_HIP(hipGetLastError());
@@ -785,8 +828,19 @@ extern "C" int qd_probe(qd_handle* h, const int32_t* env_of_query, int nq, const
                                                                                  raw_dst, image_dst, plohi_dst);
             QD_HIP(hipGetLastError());
         }
+        if (occ_dst) {
+            qd_k_probe_write_occ<<<dim3((h->P * h->N + 255) / 256, h->C, cnt), dim3(256), 0, s>>>(env_of_query, base, h->B, h->N, h->P,
+                                                                                                  pb.params, pb.state, flags, pb.occ, occ_dst);
+            QD_HIP(hipGetLastError());
+        }
     }
     return QD_OK;
+}
+
+extern "C" int qd_probe(qd_handle* h, const int32_t* env_of_query, int nq, const double* gate_v, const double* barrier_v,
+                        const double* sensor_v, const double* window, double* raw_dst, float* image_dst, double* plohi_dst,
+                        void* stream) {
+    return qd_probe_ex(h, env_of_query, nq, gate_v, barrier_v, sensor_v, window, raw_dst, image_dst, plohi_dst, nullptr, stream);
 }
 
 // slots in flight of qd_eval_points: one launch chunk of lane 0's records, at most QD_POINTS_SLOTS

@@ -62,6 +62,25 @@ __global__ void qd_k_probe_write(const int* __restrict__ env_of_query, int base,
 }
 
 // ---------------------------------------------------------------------------
+// write, occupations (qd_probe_ex with occ_dst): probe slot k -> the caller's slot base + k, [nq][C][P][N] float64 as
+// qd_get_occupations lays them out.  A channel the radial stage replaced by white noise (qd_radial_replaced on the probe's
+// own parameter and state copies) was never solved: its occupations are NaN.  Ids outside [0, B) are skipped.
+// grid = (ceil(P N / 256), C, cnt).
+// ---------------------------------------------------------------------------
+__global__ void qd_k_probe_write_occ(const int* __restrict__ env_of_query, int base, int B, int N, int P, const double* __restrict__ pparams,
+                                     const double* __restrict__ pstate, int noise_flags, const double* __restrict__ pocc,
+                                     double* __restrict__ occ_dst) {
+    const int k = blockIdx.z, ch = blockIdx.y, q = base + k, C = N - 1;
+    const int e = env_of_query[q];
+    if (e < 0 || e >= B) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P * N) return;
+    const QdLayout L = qd_layout(N);
+    const bool replaced = qd_radial_replaced(pparams + (size_t)k * L.size, pstate + (size_t)k * L.s_size, L, ch, noise_flags);
+    occ_dst[((size_t)q * C + ch) * P * N + i] = replaced ? NAN : pocc[((size_t)k * C + ch) * P * N + i];
+}
+
+// ---------------------------------------------------------------------------
 // composite, step 1: one channel of the probe signals, compact: cz[q][p] = raw[q][channel][p].  grid-stride.
 // ---------------------------------------------------------------------------
 __global__ void qd_k_map_extract(const double* __restrict__ raw, long nq, int C, int P, int channel, double* __restrict__ cz) {

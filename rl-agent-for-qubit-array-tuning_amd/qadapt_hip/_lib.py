@@ -25,7 +25,7 @@ EXPORTS = [
     "qd_update_capacitance", "qd_step", "qd_snapshot", "qd_get_state", "qd_set_state", "qd_get_raw",
     "qd_get_occupations", "qd_get_candidates", "qd_get_eigen", "qd_get_search_stats", "qd_get_solver_stats", "qd_get_rng_state", "qd_set_rng_state",
     "qd_time_ground_kernel", "qd_time_candidates_kernel", "qd_time_kernels", "qd_timed_kernel_name", "qd_chunk_envs",
-    "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points",
+    "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex",
 ]
 
 QD_CURVES = {"constant": 0, "polynomial": 1, "exponential": 2, "linear": 3}
@@ -47,6 +47,15 @@ class QdConfig(ctypes.Structure):
         ("delta_max", ctypes.c_double), ("gate_curve_exponent", ctypes.c_double),
         ("plunger_radius", ctypes.c_double), ("outer_plunger_radius", ctypes.c_double),
         ("outer_plunger_reward_max", ctypes.c_double), ("barrier_radius", ctypes.c_double),
+    ]
+
+
+class QdProbeOpts(ctypes.Structure):
+    """qd_probe_opts of include/qdsim.h: the stochastic stages, Philox serial and stream base of a qd_probe_ex call and the
+    device destination of its occupations."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("noise_flags", ctypes.c_int32), ("serial", ctypes.c_uint64),
+        ("stream_base", ctypes.c_int64), ("occ_dst", ctypes.c_void_p),
     ]
 
 
@@ -116,6 +125,8 @@ def lib():
     L.qd_timed_kernel_name.argtypes = [ctypes.c_int]; L.qd_timed_kernel_name.restype = ctypes.c_char_p
     L.qd_chunk_envs.argtypes = [vp]; L.qd_chunk_envs.restype = ctypes.c_int
     L.qd_probe.argtypes = [vp, vp, ctypes.c_int, dp, dp, dp, dp, dp, fp, dp, vp]; L.qd_probe.restype = ctypes.c_int
+    L.qd_probe_ex.argtypes = [vp, vp, ctypes.c_int, dp, dp, dp, dp, dp, fp, dp, ctypes.POINTER(QdProbeOpts), vp]
+    L.qd_probe_ex.restype = ctypes.c_int
     L.qd_probe_compose.argtypes = [vp, dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, dp, vp]
     L.qd_probe_compose.restype = ctypes.c_int
     L.qd_time_select.argtypes = [vp, dp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, dp, ctypes.POINTER(ctypes.c_float), vp]

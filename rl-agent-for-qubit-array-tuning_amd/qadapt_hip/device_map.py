@@ -82,25 +82,27 @@ def _device(env, env_index):
             float(par[L.scal + 2]), par[L.pmin:L.pmin + L.N].copy(), par[L.pmax:L.pmax + L.N].copy())
 
 
-def _render(env, env_index, pair, plan, gt_gates, gt_barriers, half_width, mode):
+def _render(env, env_index, pair, plan, gt_gates, gt_barriers, half_width, mode, noise=None):
     """All tiles of `plan` in one probe (gates pair, pair+1 at the tile centres, the others at their ground truth, the
     barriers at theirs, sensor voltage 0.0 as the scripts' _get_obs calls) and one compose of channel `pair`."""
     nq = plan["n_scans_x"] * plan["n_scans_y"]
     gates = np.tile(gt_gates, (nq, 1))
     gates[:, pair] = plan["centres"][:, 0]
     gates[:, pair + 1] = plan["centres"][:, 1]
-    out = env.probe([env_index], gates, np.tile(gt_barriers, (nq, 1)), window=half_width)
+    kw = {} if noise is None else {"noise": noise}
+    out = env.probe([env_index], gates, np.tile(gt_barriers, (nq, 1)), window=half_width, **kw)
     comp, plohi = env.compose(out["raw"], plan["n_scans_x"], plan["n_scans_y"], channel=pair, mode=mode)
     return out["raw"][:, pair], comp, plohi
 
 
-def map_full_device_range(env, env_index=0, pair=0, v0_min=None, v0_max=None, v1_min=None, v1_max=None):
+def map_full_device_range(env, env_index=0, pair=0, v0_min=None, v0_max=None, v1_min=None, v1_max=None, noise=None):
     """map_full_device_range.py on env `env_index` of a VecQuantumDeviceEnv: its plunger range of gates (pair, pair+1)
     (or the overrides) tiled with the device's own scan window, one probe + one compose, composite normalised by ONE
     0.5 / 99.5 percentile pair (row block j = scan row j: plot with origin='lower').  Tiles are rendered at their saved
     `positions` (see the module docstring for this deviation from the script).  Returns the dict the script pickles
     (`scans` as a (nx*ny, R, R) float64 device tensor, scan (i, j) at i * n_scans_y + j) plus `composite`
-    (ny*R, nx*R) float32 and `plohi` (2,) device tensors and `extent`."""
+    (ny*R, nx*R) float32 and `plohi` (2,) device tensors and `extent`.  noise: handed to `probe` (None: clean scans; True:
+    the env's own stochastic stages, so tiles beyond `full_noise_distance` are white noise as in the reference's maps)."""
     gt_gates, gt_barriers, w, pmin, pmax = _device(env, env_index)
     plunger_min = pmin[pair:pair + 2].copy()
     plunger_max = pmax[pair:pair + 2].copy()
@@ -114,7 +116,7 @@ def map_full_device_range(env, env_index=0, pair=0, v0_min=None, v0_max=None, v1
         plunger_max[1] = v1_max
     obs_window_size = w - (-w)                                   # obs_voltage_max - obs_voltage_min
     plan = tile_plan_full_range(plunger_min, plunger_max, obs_window_size)
-    scans, comp, plohi = _render(env, env_index, pair, plan, gt_gates, gt_barriers, obs_window_size / 2, "global")
+    scans, comp, plohi = _render(env, env_index, pair, plan, gt_gates, gt_barriers, obs_window_size / 2, "global", noise)
     return {"scans": scans, "positions": plan["positions"], "n_scans_x": plan["n_scans_x"], "n_scans_y": plan["n_scans_y"],
             "resolution": env.R, "plunger_min": plunger_min, "plunger_max": plunger_max, "obs_window_size": obs_window_size,
             "step_x": plan["step_x"], "step_y": plan["step_y"], "gt_gates": gt_gates, "gt_barriers": gt_barriers,
@@ -122,15 +124,16 @@ def map_full_device_range(env, env_index=0, pair=0, v0_min=None, v0_max=None, v1
             "extent": [plunger_min[0], plunger_max[0], plunger_min[1], plunger_max[1]]}
 
 
-def map_device_range(env, env_index=0, pair=0, percentile=None, half_range=20.0, window_size=3.0):
+def map_device_range(env, env_index=0, pair=0, percentile=None, half_range=20.0, window_size=3.0, noise=None):
     """map_device_range.py on env `env_index`: +- half_range around the ground truth of gates (pair, pair+1) in
     edge-to-edge scans `window_size` wide, every scan normalised by its own percentiles, row blocks flipped (block
     ny-1-j holds scan row j, as the script stitches them).  percentile: the script's optional cap, applied to the
     composite (one host round trip).  Tiles are rendered at their saved `positions` (module docstring).  Returns the
-    dict the script pickles plus `composite` (ny*R, nx*R) float32 and `plohi` (nx*ny, 2) device tensors."""
+    dict the script pickles plus `composite` (ny*R, nx*R) float32 and `plohi` (nx*ny, 2) device tensors.  noise: handed to
+    `probe`, as in map_full_device_range."""
     gt_gates, gt_barriers, _, _, _ = _device(env, env_index)
     plan = tile_plan_centred(gt_gates[pair], gt_gates[pair + 1], half_range, window_size)
-    scans, comp, plohi = _render(env, env_index, pair, plan, gt_gates, gt_barriers, window_size / 2, "per_scan")
+    scans, comp, plohi = _render(env, env_index, pair, plan, gt_gates, gt_barriers, window_size / 2, "per_scan", noise)
     if percentile is not None:
         p_cap = float(np.percentile(comp.cpu().numpy().astype(np.float64), percentile))
         comp = (comp.clamp(0, p_cap) / p_cap) if p_cap > 0 else comp

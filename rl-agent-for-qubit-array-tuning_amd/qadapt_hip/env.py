@@ -61,7 +61,8 @@ class ArrayFacade:
     """`env.array` of the reference (a QarrayBaseClass) as far as its users outside step() need it: `model.cgd_full`,
     `model.charge_sensor_open` / `model.ground_state_open` (ModelFacade), `barrier_alpha`, `gate_ground_truth`, the scan geometry (`obs_voltage_min`, `obs_voltage_max`, `obs_image_size`,
     `num_dots`, `num_barrier_voltages`) and the stateless `_get_obs` (qarray_base_class.py:171-229), rendered by the
-    backend's probe on the current device without touching the episode.  The window is
+    backend's probe on the current device without touching the episode; `_get_obs(..., noise=True)` runs the stochastic
+    stages the env was created with, as the reference's call does, with fresh noise at every call (default: a clean scan).  The window is
     (obs_voltage_max - obs_voltage_min) / 2 around each gate voltage; it follows the device (`window_delta`) at every
     reset and may be overwritten, as the reference's scripts do, but must stay symmetric: the kernels hold one
     half-width per scan."""
@@ -77,7 +78,7 @@ class ArrayFacade:
         self.obs_channels = int(num_dots) - 1
         self.obs_voltage_min, self.obs_voltage_max = -1.0, 1.0            # qarray_base_class.py:38-39
 
-    def _get_obs(self, gate_voltages, barrier_voltages=None, sensor_voltage=None):
+    def _get_obs(self, gate_voltages, barrier_voltages=None, sensor_voltage=None, noise=False):
         assert (
             len(gate_voltages) == self.num_dots
         ), f"Incorrect gate voltage shape, expected {self.num_dots}, got {len(gate_voltages)}"
@@ -94,7 +95,7 @@ class ArrayFacade:
         out = self._b.probe([0], np.asarray(gate_voltages, np.float64)[None, :],
                             np.asarray(barrier_voltages, np.float64)[None, :],
                             sensor_voltage=None if sensor_voltage is None else float(sensor_voltage),
-                            window=(vmax - vmin) / 2)
+                            window=(vmax - vmin) / 2, **({"noise": True} if noise else {}))
         raw = out["raw"]
         raw = raw.detach().cpu().numpy() if hasattr(raw, "detach") else np.asarray(raw)
         image = np.ascontiguousarray(raw[0].transpose(1, 2, 0))           # (R, R, C) float64, unnormalised

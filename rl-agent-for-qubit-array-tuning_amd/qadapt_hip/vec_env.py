@@ -183,9 +183,11 @@ class VecQuantumDeviceEnv:
         self._rngs = [np.random.Generator(np.random.PCG64(self.seed + self.env_id_offset + e)) for e in range(B)]
         # ---- library handle ---------------------------------------------------
         self._lib = _lib.lib()
+        self.noise_flags = self._noise_flags(noise)   # the stages this env's steps run (probe(noise=True) runs the same)
+        self._probe_serials = 0                       # noisy probes so far: the default serial of the next one
         cfg = make_qd_config(self.config, self.qconfig, N, R, B, env_chunk=env_chunk,
                              flags=(_lib.QD_FLAG_VALIDATE if validate else 0) | (_lib.QD_FLAG_PIXEL_SEARCH if pixel_search else 0),
-                             noise_flags=self._noise_flags(noise), seed=self.seed, env_id_offset=self.env_id_offset)
+                             noise_flags=self.noise_flags, seed=self.seed, env_id_offset=self.env_id_offset)
         self._h = ctypes.c_void_p()
         rc = self._lib.qd_create(ctypes.byref(cfg), self.device.index, ctypes.byref(self._h))
         if rc != 0:                          # a partially built handle carries the error text and must be released
@@ -280,17 +282,27 @@ class VecQuantumDeviceEnv:
             t = torch.from_numpy(a.reshape(-1)).pin_memory().to(self.device, non_blocking=True).reshape(a.shape)
         return t.broadcast_to(shape).contiguous()
 
-    def probe(self, env_ids, gate_voltages, barrier_voltages, sensor_voltage=None, window=None, normalised=False):
-        """Stateless scans (qd_probe): the reference's `array._get_obs(gate_voltages, barrier_voltages, sensor_voltage)`
-        for nq queries in one call, each on the device of env `env_ids[q]` with that env's current virtual gate matrix.
-        Nothing of the episodes changes (state, step counters, Kalman filters, last observation, noise streams), nq may
-        exceed the batch and one env may serve many queries.  Probes are deterministic: no noise stage runs.
+    def probe(self, env_ids, gate_voltages, barrier_voltages, sensor_voltage=None, window=None, normalised=False,
+              noise=None, serial=None, stream_base=None, occupations=False):
+        """Stateless scans (qd_probe / qd_probe_ex): the reference's `array._get_obs(gate_voltages, barrier_voltages,
+        sensor_voltage)` for nq queries in one call, each on the device of env `env_ids[q]` with that env's current
+        virtual gate matrix.  Nothing of the episodes changes (state, step counters, Kalman filters, last observation,
+        noise streams), nq may exceed the batch and one env may serve many queries.
           env_ids           (nq,) ints, or one id for all queries
           gate_voltages     (nq, N) virtual gate voltages; barrier_voltages (nq, N-1)
           sensor_voltage    None (0.0, as the reference's default), a scalar or (nq,)
           window            None (each env's own half-width), a scalar or (nq,) half-widths
+          noise             None / False: a deterministic probe, no noise stage runs.  True: the stages this env was
+                            created with (those of its steps).  Or an iterable of {"sensor", "radial", "latch"}, as the
+                            constructor takes it, whatever the env was created with
+          serial            the observation-number word of the noise streams; None: (1 << 63) | k, where k counts this
+                            object's noisy probes, so every call draws fresh noise and none shares a stream with a step
+          stream_base       query q draws from the streams of global env id stream_base + q; None: env_id_offset
+          occupations       True adds the occupations the signal was formed from (after latching, if it ran)
         numpy or torch inputs.  Returns device tensors {"raw": (nq, C, R, R) float64 unnormalised}, plus, with
-        normalised=True, {"image": (nq, R, R, C) float32 normalised per query, "plohi": (nq, 2) its percentiles}."""
+        normalised=True, {"image": (nq, R, R, C) float32 normalised per query, "plohi": (nq, 2) its percentiles}, plus,
+        with occupations=True, {"occupations": (nq, C, R, R, N) float64; NaN in a channel the radial stage replaced by
+        white noise}."""
         N, C, R = self.N, self.C, self.R
         gv = gate_voltages if isinstance(gate_voltages, torch.Tensor) else np.asarray(gate_voltages, np.float64)
         gv = gv.reshape(-1, N)
@@ -307,9 +319,25 @@ class VecQuantumDeviceEnv:
             out["image"] = torch.empty((nq, R, R, C), dtype=torch.float32, device=self.device)
             out["plohi"] = torch.empty((nq, 2), dtype=torch.float64, device=self.device)
         ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())    # noqa: E731
-        rc = self._lib.qd_probe(self._h, ptr(ids), nq, ptr(gv), ptr(bv), ptr(sv), ptr(wd), ptr(out["raw"]),
-                                ptr(out.get("image")), ptr(out.get("plohi")), self._stream())
-        _lib.check(self._h, rc, "qd_probe")
+        if noise is None and serial is None and stream_base is None and not occupations:
+            rc = self._lib.qd_probe(self._h, ptr(ids), nq, ptr(gv), ptr(bv), ptr(sv), ptr(wd), ptr(out["raw"]),
+                                    ptr(out.get("image")), ptr(out.get("plohi")), self._stream())
+            _lib.check(self._h, rc, "qd_probe")
+            return out
+        flags = self.noise_flags if noise is True else self._noise_flags(noise)
+        if serial is None:
+            serial = (1 << 63) | self._probe_serials
+            if flags:
+                self._probe_serials += 1
+        if occupations:
+            out["occupations"] = torch.empty((nq, C, R, R, N), dtype=torch.float64, device=self.device)
+        opts = _lib.QdProbeOpts(struct_size=ctypes.sizeof(_lib.QdProbeOpts), noise_flags=int(flags),
+                                serial=int(serial) & 0xFFFFFFFFFFFFFFFF,
+                                stream_base=int(self.env_id_offset if stream_base is None else stream_base),
+                                occ_dst=out["occupations"].data_ptr() if occupations else None)
+        rc = self._lib.qd_probe_ex(self._h, ptr(ids), nq, ptr(gv), ptr(bv), ptr(sv), ptr(wd), ptr(out["raw"]),
+                                   ptr(out.get("image")), ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
+        _lib.check(self._h, rc, "qd_probe_ex")
         return out
 
     def compose(self, raw, nx, ny, channel=0, mode="global"):
