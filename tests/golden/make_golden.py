@@ -12,11 +12,14 @@ It loads these reference source files by path and executes them unmodified:
   * src/qarray_latched/DotArrays/GateVoltageComposer.py  
   * src/qadapt/environment/utils/vary_peak_width.py      (variable peak width)
 and stores only INPUTS and OUTPUTS (arrays) as .npz -- no reference source is
-copied.  Everything else on the hot path imports jax/qarray and cannot run
+copied.  updater_traces_f32.npz (--only-updater-f32) is written with fixed zip
+time stamps: running it again gives the same bytes.  Everything else on the hot path imports jax/qarray and cannot run
 here; those rows are pinned by analytic known-answer tests.
 """
 import importlib.util
+import io
 import os
+import zipfile
 
 import numpy as np
 
@@ -94,6 +97,76 @@ def updater_variant_traces():
     np.savez_compressed(os.path.join(HERE, "updater_variants.npz"), **out)
 
 
+def _savez_fixed(path, arrays):
+    """np.savez_compressed with a fixed member order and time stamp: the same arrays give the same bytes on every run
+    (numpy stamps each member with the wall clock)."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+        for name in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(arrays[name]), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            zf.writestr(info, buf.getvalue(), compresslevel=9)
+
+
+F32_STEPS = 8
+F32_GATE = 0.05            # variance_threshold of every case
+
+
+def updater_traces_f32():
+    """Both reference updaters on inputs that ARE float32 numbers (the device takes float32 CNN outputs, so it sees exactly
+    the numbers the reference class saw): n_dots 2..8 x {kalman, direct} x {3 outputs, 2 outputs include_nnn=False}, 8 steps.
+    log-variances from U(-8, 3) cross both ends of the [-6, 2] clamp and the acceptance gate at ln 0.05; about 5 % of the
+    values are multiplied by 40 so that the +-1 mean clamp is hit.  A case is redrawn until it holds an accepted and a
+    rejected update, a clamped mean, a log-variance beyond each clamp end, and no variance within 1e-6 (relative) of the
+    gate: an ulp of exp() then cannot flip a decision."""
+    K = _load(f"{REF}/src/qadapt/capacitance_model/KalmanUpdater.py", "ref_kalman")
+    D = _load(f"{REF}/src/qadapt/capacitance_model/DirectUpdater.py", "ref_direct")
+    out = {}
+    case = 0
+    for n_dots in range(2, 9):
+        for name, cls in (("kalman", K.KalmanCapacitanceUpdater), ("direct", D.DirectCapacitanceUpdater)):
+            for n_out in (3, 2):
+                C = n_dots - 1
+                for attempt in range(10000):
+                    rng = np.random.default_rng([2718, n_dots, name == "direct", n_out, attempt])
+                    values = rng.normal(0.0, 0.1, size=(F32_STEPS, C, n_out))
+                    values[rng.random(values.shape) < 0.05] *= 40.0
+                    values = values.astype(np.float32)
+                    log_vars = rng.uniform(-8.0, 3.0, size=(F32_STEPS, C, n_out)).astype(np.float32)
+                    k = cls(n_dots=n_dots, prior_mean=0.3, prior_variance=0.5, variance_threshold=F32_GATE, process_noise=0.0,
+                            include_nnn=(n_out == 3), prior_mean_nnn=0.15)
+                    means = np.zeros((F32_STEPS, n_dots, n_dots)); varis = np.zeros_like(means); full = np.zeros_like(means)
+                    acc = np.zeros(F32_STEPS, np.int64); rej = np.zeros(F32_STEPS, np.int64)
+                    for t in range(F32_STEPS):
+                        for i in range(C):
+                            outs = [(-float(values[t, i, j]), float(log_vars[t, i, j])) for j in range(n_out)]
+                            k.update_from_scan(left_dot=i, ml_outputs=outs)
+                        means[t] = k.means; varis[t] = k.variances; full[t] = k.get_full_matrix()
+                        acc[t] = k.total_accepted; rej[t] = k.total_rejected
+                    # the outputs the updater reads: with 3 outputs the end channels have no next-nearest neighbour on one side
+                    used = np.ones(values.shape, bool)
+                    if n_out == 3:
+                        used[:, C - 1, 1] = False; used[:, 0, 2] = False
+                    lv = log_vars.astype(np.float64)[used]
+                    var = np.exp(np.clip(lv, -6.0, 2.0))
+                    ok = (acc[-1] > 0 and rej[-1] > 0 and (np.abs(means) == 1.0).any()
+                          and (lv < -6.0).any() and (lv > 2.0).any()
+                          and not (np.abs(var - F32_GATE) < 1e-6 * F32_GATE).any())
+                    if ok:
+                        break
+                else:
+                    raise RuntimeError(f"no draw meets the conditions: {n_dots} {name} {n_out}")
+                out[f"c{case}_kind"] = np.array(name); out[f"c{case}_n_dots"] = np.array(n_dots)
+                out[f"c{case}_values"] = values; out[f"c{case}_log_vars"] = log_vars
+                out[f"c{case}_means"] = means; out[f"c{case}_variances"] = varis; out[f"c{case}_full"] = full
+                out[f"c{case}_accepted"] = acc; out[f"c{case}_rejected"] = rej
+                case += 1
+    out["n_cases"] = np.array(case)
+    _savez_fixed(os.path.join(HERE, "updater_traces_f32.npz"), out)
+
+
 def sweep_grids():
     G = _load(f"{REF}/src/qarray_latched/DotArrays/GateVoltageComposer.py", "ref_gvc")
     out = {}
@@ -144,8 +217,12 @@ if __name__ == "__main__":
     if "--only-updater-variants" in __import__("sys").argv:
         updater_variant_traces()
         raise SystemExit(0)
+    if "--only-updater-f32" in __import__("sys").argv:
+        updater_traces_f32()
+        raise SystemExit(0)
     kalman_traces()
     updater_variant_traces()
+    updater_traces_f32()
     sweep_grids()
     peak_widths()
     print("golden fixtures written to", HERE)

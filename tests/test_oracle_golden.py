@@ -54,3 +54,38 @@ def test_direct_and_nn_mode_updaters_match_reference(golden_dir):
             assert np.array_equal(k.means, g[f"c{c}_means"][t]), (c, t)
             assert np.array_equal(k.vars, g[f"c{c}_variances"][t]), (c, t)
             assert np.array_equal(k.full_matrix(), g[f"c{c}_full"][t]), (c, t)
+
+
+def test_updaters_on_float32_inputs_match_reference(golden_dir):
+    """Both updaters, n_dots 2..8, 3 and 2 outputs, on inputs that are float32 numbers (what the device is fed) and that
+    cross both ends of the log-variance clamp, the acceptance gate and the +-1 mean clamp: traces of the reference
+    classes themselves, with their accepted / rejected counters."""
+    g = np.load(os.path.join(golden_dir, "updater_traces_f32.npz"))
+    assert int(g["n_cases"]) == 7 * 2 * 2
+    seen = set()
+    for c in range(int(g["n_cases"])):
+        n = int(g[f"c{c}_n_dots"]); kind = str(g[f"c{c}_kind"])
+        values = g[f"c{c}_values"]; log_vars = g[f"c{c}_log_vars"]
+        assert values.dtype == np.float32 and log_vars.dtype == np.float32 and values.shape[0] == 8
+        seen.add((n, kind, values.shape[-1]))
+        cls = O.DirectOracle if kind == "direct" else O.KalmanOracle
+        k = cls(n, include_nnn=values.shape[-1] == 3)
+        count = [0, 0]
+        inner = k._update
+
+        def counted(i, j, delta, R, inner=inner, count=count):
+            ok = inner(i, j, delta, R)
+            count[0 if ok else 1] += 1
+            return ok
+        k._update = counted
+        for t in range(values.shape[0]):
+            k.update_from_cnn(values[t], log_vars[t])
+            assert np.array_equal(k.means, g[f"c{c}_means"][t]), (c, t)
+            assert np.array_equal(k.vars, g[f"c{c}_variances"][t]), (c, t)
+            assert np.array_equal(k.full_matrix(), g[f"c{c}_full"][t]), (c, t)
+            assert count == [int(g[f"c{c}_accepted"][t]), int(g[f"c{c}_rejected"][t])], (c, t)
+        # what the fixture is for: every case gates both ways, clamps a mean and has log-variances beyond both clamp ends
+        assert count[0] > 0 and count[1] > 0, c
+        assert (np.abs(g[f"c{c}_means"]) == 1.0).any(), c
+        assert (log_vars < -6).any() and (log_vars > 2).any(), c
+    assert seen == {(n, kind, o) for n in range(2, 9) for kind in ("kalman", "direct") for o in (3, 2)}
