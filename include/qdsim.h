@@ -38,6 +38,10 @@ extern "C" {
                                  grid is fine enough, with an exact per-pixel redo pass; same results, A/B switch) */
 #define QD_FLAG_RETIRED_TILE_FUSED 4  /* was QD_FLAG_TILE_FUSED (round 2: experimental fused tile kernel, 3x slower than the
                                  default pipeline); the kernel is gone and qd_create refuses the flag with QD_ERR_ARG */
+#define QD_FLAG_GS_GERSHGORIN_ZERO 8  /* ground-state stage: discard a hop component only when its Gershgorin lower bound exceeds
+                                 min F = 0 (default: the pixel's lowest 2x2 pair bound (F_i + F_j) / 2 - |H_ij|, with a margin
+                                 of 2^-40 ||H||_inf, which leaves fewer components to solve; same results bit for bit,
+                                 A/B switch; qd_get_solver_stats counts the tasks) */
 
 /* Stochastic stages.  The generators are counter-based Philox streams, so
  * results are reproducible per (rng_seed, global env id, observation number, channel, pixel)

@@ -541,7 +541,7 @@ static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane
                 QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_BOOL(batches < (unsigned)h->cus, SMALL, QD_DISPATCH_N(h->N,
                     qd_k_gs_structure<NN, VAL, (SMALL ? 16 : 4)><<<dim3(batches), dim3(64 * (SMALL ? 16 : 4)), 0, s>>>(env_ids, base + off,
                         rec0 + off, g, h->R, b.params, ln.recs.p, b.state, b.noise_flags, ln.slabs.p, ln.gtiles.p, tilelist, h->gs_batches,
-                        h->kept))));
+                        h->kept, (h->cfg.flags & QD_FLAG_GS_GERSHGORIN_ZERO) ? 1 : 0))));
             }
             QD_HIP(hipGetLastError());
         }

@@ -13,7 +13,8 @@
 //      H_ij = -t_d sqrt(n_from (n_to + 1)) with the occupations of the ROW state (hamiltonian_build.py:125-131),
 //      connected components (hopping conserves the total charge, so H is block diagonal; the padding copies of
 //      |0..0> are always isolated), Gershgorin pruning (a component whose lower bound min(F - sum|H_ij|) exceeds
-//      min F cannot hold the ground state).  Every surviving component of >= 2 states becomes a TASK: its dense
+//      an upper bound of the ground energy cannot hold the ground state; the upper bound: the lowest 2x2 pair
+//      bound of the pixel, qd_gs_pair_bound).  Every surviving component of >= 2 states becomes a TASK: its dense
 //      block is written, lower triangle packed, into the batch's slab and its offset appended to the list of its
 //      size class; the batch's 64-task tiles are appended to the launch-wide tile list of the class.
 //   B  SOLVE (qd_k_gs_solve<class>, one launch per size class with its own register budget), one TASK per lane
@@ -56,6 +57,24 @@ QD_HD unsigned qd_gs_hop(unsigned ci, unsigned cj, unsigned tcq) {
     return t > x ? t - x : 0u;
 }
 
+// Pruning bound of the structure phase.  F: the diagonal relative to the pixel's lowest free energy (min F = 0).
+//   upper bound of the ground energy   ub = min(0, min over the coupled pairs (i, j) of u_ij), u_ij = (F_i + F_j) / 2 - |H_ij|:
+//       the 2x2 principal submatrix of the pair has the lowest eigenvalue m - sqrt(d^2 + c^2) <= m - |c| (m the mean, d half the
+//       difference of its diagonal), and no eigenvalue of a principal submatrix lies below lambda_min(H) (interlacing); the 0 is
+//       the 1x1 submatrix of the lowest state.  No square root: where many components survive the bound 0 (large tc) the
+//       couplings dominate the differences of the diagonal and the full 2x2 eigenvalue prunes no further component.
+//   margin   2^-40 ||H||_inf, ||H||_inf = max_i (F_i + radius_i) over the pixel's K states (shifted frame: F >= 0).
+//   a component of >= 2 states is a task iff its Gershgorin lower bound min(F - radius) <= ub + margin.
+// The margin covers the error bars of the eigen-solvers on the pruned component and on the one that attains ub (<= 2e-14 ||A||
+// each) and the rounding of radius and u_ij (a few eps ||H||_inf): 2^-40 = 9.1e-13 is more than 20 times their sum.  So every
+// component whose COMPUTED eigenvalue could be the lowest of the pixel, or tied for it, is still solved; a task's result does
+// not depend on which other tasks exist; and the select phase sees the same winner, the same tie set and the same vector as
+// with the bound 0.  Isolated states do not go through this test: qd_ground_select takes lambda = 0 for them, which is right
+// iff F <= 0 (a positive margin would admit F > 0).
+QD_HD double qd_gs_pair_bound(double Fi, double Fj, double c) { return __builtin_fma(0.5, Fi + Fj, -__builtin_fabs(c)); }
+QD_HD double qd_gs_prune_margin(double hnorm) { return 0x1p-40 * hnorm; }
+QD_HD bool qd_gs_is_task(double comp_lower, double ub, double margin) { return comp_lower <= ub + margin; }
+
 #if defined(__HIPCC__)
 
 #ifndef QD_NBREG
@@ -78,7 +97,7 @@ struct QdWaveLds {
     double coef[NS][64];            // H_ij of neighbour slot QD_NBREG + s of lane
     unsigned char nidx[NS][64];
     double buf[64];                 // publish buffer for per-component reductions
-    double pv[2][16];               // per half: tc[0..N-2] at offset 9
+    double pv[2][16];               // per half: tc[0..N-2] at offset 9; [0], [1]: upper bound and margin of the pruning test
     short pfl[2][8];                // per half: floor(n_cont)
 };
 struct QdBlockLds {
@@ -161,10 +180,32 @@ __device__ __forceinline__ unsigned qd_half_ballot(bool p) {
     unsigned long long b = __ballot(p);
     return (unsigned)(b >> (threadIdx.x & 32));
 }
+// Minimum over the half-wave, in every lane.  Inside a row of 16 lanes the exchange is done by DPP modifiers (a few cycles each,
+// where a ds_bpermute round trip through the LDS crossbar costs a dependent ~100): lane ^ 1 and lane ^ 2 as quad permutations;
+// then the quads are uniform, and mirroring the 8 lanes (lane i reads 7 - i) hands each quad the other quad's value; then the
+// mirror of the 16.  Only the last step, between the two rows of the half, goes through the crossbar.  All 64 lanes are on
+// (as for qd_half_rot).  A minimum does not depend on the order, so the result is that of the __shfl_xor butterfly.
+#ifndef QD_GS_MIN_DPP
+#define QD_GS_MIN_DPP 1             // 0: the butterfly with __shfl_xor alone (diagnostic)
+#endif
+template <int CTRL>
+__device__ __forceinline__ double qd_dpp_f64(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false),
+                            __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false));
+}
 __device__ __forceinline__ double qd_half_min(double v) {
+#if QD_GS_MIN_DPP
+    v = fmin(v, qd_dpp_f64<0xB1>(v));                      // quad_perm [1, 0, 3, 2]
+    v = fmin(v, qd_dpp_f64<0x4E>(v));                      // quad_perm [2, 3, 0, 1]
+    v = fmin(v, qd_dpp_f64<0x141>(v));                     // row_half_mirror
+    v = fmin(v, qd_dpp_f64<0x140>(v));                     // row_mirror
+    return fmin(v, __shfl_xor(v, 16, 32));
+#else
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 32));
     return v;
+#endif
 }
 // wave-wide maximum, returned through readfirstlane so that the compiler knows it is uniform: loop bounds
 // and slot guards built from it become scalar branches instead of exec-mask juggling
@@ -203,11 +244,12 @@ __device__ __forceinline__ void qd_gs_hop_rounds(unsigned ecode, unsigned tcq, u
 // ---------------------------------------------------------------------------------------------------------------
 // Phase A.  rec: this half's pixel record (states, their free energies from the candidate search, tunnel couplings);
 // ps: the pixel's slot in the batch; live: false for the clamped duplicate beyond the image (nothing is emitted);
-// kept: K, the states of the Hamiltonian (lanes m >= K take no part: their link is QD_LINK_NONE).
+// kept: K, the states of the Hamiltonian (lanes m >= K take no part: their link is QD_LINK_NONE); bound0: prune against
+// min F = 0 alone (QD_FLAG_GS_GERSHGORIN_ZERO, the same for the whole launch).
 // ---------------------------------------------------------------------------------------------------------------
 template <int N, bool VALIDATE>
 __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict__ rec, bool live, int ps, QdWaveLds<N>& W,
-                                                    QdBlockLds& S, const QdSlab& sl, int kept) {
+                                                    QdBlockLds& S, const QdSlab& sl, int kept, bool bound0) {
     const int lane = threadIdx.x & 63;
     const int m = lane & 31;
     const int hb = lane & 32;
@@ -262,10 +304,15 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
     const int cnt = __popc(nbrmask);
     const int maxcnt = qd_wave_max_int(cnt);
     double radius = 0.0;
-    double creg[QD_NBREG]; int jreg[QD_NBREG];
+    double ubl = 0.0;                                      // min(0, my pairs' u_ij): see qd_gs_pair_bound
+    double creg[QD_NBREG];
+    unsigned jpack = 0;                                    // the neighbours of the register slots, 5 bits each
+    static_assert(5 * QD_NBREG <= 32, "jpack: 5 bits per register slot");
 #pragma unroll
-    for (int i = 0; i < QD_NBREG; ++i) { creg[i] = 0.0; jreg[i] = m; }
+    for (int i = 0; i < QD_NBREG; ++i) creg[i] = 0.0;
     {
+        buf[lane] = F;                                     // (a neighbour is a valid state: its F is finite)
+        __builtin_amdgcn_wave_barrier();
         unsigned rem = nbrmask;
         for (int s = 0; s < maxcnt; ++s) {
             const bool has = rem != 0;
@@ -288,12 +335,20 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
                 double sq_ = 0.0;
                 if (prod > 0.0) sq_ = qd_sqrt1(prod);
                 c = -t * sq_;
+                ubl = fmin(ubl, qd_gs_pair_bound(F, buf[hb + j], c));
             }
             if (s < QD_NBREG) {                            // (s is uniform: scalar branches)
 #pragma unroll
-                for (int i = 0; i < QD_NBREG; ++i) if (i == s) { creg[i] = c; jreg[i] = j; }
+                for (int i = 0; i < QD_NBREG; ++i) if (i == s) creg[i] = c;
+                jpack |= (unsigned)j << (5 * s);
             } else { W.coef[s - QD_NBREG][lane] = c; W.nidx[s - QD_NBREG][lane] = (unsigned char)j; }
             radius += fabs(c);
+        }
+        // the pixel's upper bound and margin (qd_gs_pair_bound), parked in LDS over phase 3 like the other pixel-uniform values
+        if (!bound0) {                                     // (uniform for the block)
+            const double ub = qd_half_min(ubl);
+            const double hnorm = -qd_half_min(inK ? -(F + radius) : 0.0);    // (lanes beyond K have F = inf and no part in H)
+            if (m == 0) { W.pv[hh][0] = ub; W.pv[hh][1] = qd_gs_prune_margin(hnorm); }
         }
     }
 
@@ -316,9 +371,12 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
     const int smax = qd_wave_max_int(ssz);
 
     // ---- 4. Gershgorin pruning ---------------------------------------------
-    // upper bound of the pixel's ground energy: min F = 0 (the diagonal is relative to the lowest free energy)
+    // A component whose lower bound min(F - radius) exceeds an upper bound of the pixel's ground energy cannot hold the ground
+    // state.  Components of >= 2 states: the pair bound with its margin (qd_gs_pair_bound); bound0 (QD_FLAG_GS_GERSHGORIN_ZERO,
+    // uniform for the block): min F = 0, as for the isolated states in either case.
     double comp_lower;
     {
+        __builtin_amdgcn_wave_barrier();                   // (the loop of phase 2 read the F of other lanes from buf)
         buf[lane] = F - radius;
         __builtin_amdgcn_wave_barrier();
         double acc = INFINITY;
@@ -329,12 +387,16 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
         __builtin_amdgcn_wave_barrier();
         comp_lower = acc;
     }
-    const bool active = live && comp_lower <= 0.0;
+    bool active = live && comp_lower <= 0.0;
+    if (!bound0 && ssz > 1) active = live && qd_gs_is_task(comp_lower, pvv[0], pvv[1]);
 #if defined(QD_ABLATE) && QD_ABLATE == 3
     const bool solve = false;                              // diagnostic: no tasks
 #else
     const bool solve = active && ssz > 1;
 #endif
+    // trip count of the zero fill below: the largest component that is written (a pruned one writes no block, takes no list
+    // slot and its states are linked to nothing)
+    const int smax_solve = qd_wave_max_int(solve ? ssz : 0);
 
     // ---- 5. tasks: one record per surviving component ------------------------
     unsigned base = 0, gi = 0;
@@ -361,15 +423,16 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
         unsigned nrm = 0;                                  // ranks that carry a coupling
         for (int s = 0; s < maxcnt; ++s) {
             if (s < cnt && solve) {
-                int j = jreg[0]; double c = creg[0];
+                int j; double c = creg[0];
                 if (s >= QD_NBREG) { j = (int)W.nidx[s - QD_NBREG][lane]; c = W.coef[s - QD_NBREG][lane]; }
+                else j = (int)((jpack >> (5 * s)) & 31u);
 #pragma unroll
-                for (int i = 1; i < QD_NBREG; ++i) if (i == s) { j = jreg[i]; c = creg[i]; }
+                for (int i = 1; i < QD_NBREG; ++i) if (i == s) c = creg[i];
                 const int rj = __popc(seg & ((1u << j) - 1u));
                 if (rj < r) { row[rj] = c; nrm |= 1u << rj; }
             }
         }
-        for (int c = 0; c < smax - 1; ++c)
+        for (int c = 0; c < smax_solve - 1; ++c)
             if (solve && c < r && !((nrm >> c) & 1u)) row[c] = 0.0;
         if (solve) row[r] = F;
     }

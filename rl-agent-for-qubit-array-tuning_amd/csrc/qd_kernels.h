@@ -294,7 +294,7 @@ __device__ __forceinline__ void qd_gs_publish_tiles(const QdBlockLds& sB, const 
 }
 
 #ifndef QD_GS_WAVES
-#define QD_GS_WAVES 7            // 72 VGPRs (24 B of scratch per lane) and 7 x 21 KB of LDS per CU (8 dots).  The kernel is latency
+#define QD_GS_WAVES 7            // 72 VGPRs at the most (8 dots: 70, no scratch) and 7 x 21 KB of LDS per CU.  The kernel is latency
                                  // bound (ds_bpermute / LDS chains): measured per env-step 4 waves per SIMD 26.8 us, 5: 22.6, 6: 20.5, 7: 19.6,
                                  // 8 (64 VGPRs, 116 B of scratch): 31.2
 #endif
@@ -305,7 +305,7 @@ __global__ void __launch_bounds__(64 * WPB, WPB == 4 ? QD_GS_WAVES : 4)
 qd_k_gs_structure(const int* __restrict__ env_ids, int env_base, int rec_slot0, QdGsGeom g, int R, const double* __restrict__ params,
                   const QdPixelRec* __restrict__ recs, const double* __restrict__ state, int noise_flags,
                   unsigned char* __restrict__ slabs, unsigned* __restrict__ gtiles, unsigned* __restrict__ tilelist, size_t batches_cap,
-                  int kept) {
+                  int kept, int bound0) {
     const QdLayout L = qd_layout(N);
     __shared__ QdWaveLds<N> sW[WPB];
     __shared__ QdBlockLds sB;
@@ -332,7 +332,7 @@ qd_k_gs_structure(const int* __restrict__ env_ids, int env_base, int rec_slot0, 
         const int p = p0 + ps;
         // both halves of a wave run in lock step: clamp instead of exiting
         const int pc = p < g.P ? p : g.P - 1;
-        qd_ground_structure<N, VALIDATE>(rbase + pc, p < g.P, ps, W, sB, sl, kept);
+        qd_ground_structure<N, VALIDATE>(rbase + pc, p < g.P, ps, W, sB, sl, kept, bound0 != 0);
     }
     __syncthreads();
     qd_gs_publish_tiles(sB, sl, batch, gtiles, tilelist, batches_cap);

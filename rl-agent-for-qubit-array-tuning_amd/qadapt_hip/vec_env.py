@@ -111,8 +111,10 @@ class VecQuantumDeviceEnv:
                  resolution=None, device=None, seed=None, env_id_offset=0, capacitance_model=None,
                  validate=False, env_chunk=0, reset_kalman_on_reset=False, noise=None,
                  vary_peak_width=False, peak_width_alpha=0.01, voltage_capacitance_model=None, pixel_search=False,
-                 num_charge_states=None):
+                 num_charge_states=None, gs_gershgorin_zero=False):
         """pixel_search: a9 by the per-pixel search only (A/B switch; the default runs one search per 8x8 tile).
+        gs_gershgorin_zero: the ground-state stage prunes hop components against the bound 0 alone (A/B switch,
+        QD_FLAG_GS_GERSHGORIN_ZERO; the default prunes against the pixel's lowest pair bound: fewer tasks, same results).
         seed: base seed of the per-env device streams (PCG64(seed + global env id)) and the Philox key of
         the stochastic stages; None draws fresh OS entropy, as the reference's unseeded generators do
         (qarray_base_class.py:773-774, env.py:161).
@@ -186,7 +188,8 @@ class VecQuantumDeviceEnv:
         self.noise_flags = self._noise_flags(noise)   # the stages this env's steps run (probe(noise=True) runs the same)
         self._probe_serials = 0                       # noisy probes so far: the default serial of the next one
         cfg = make_qd_config(self.config, self.qconfig, N, R, B, env_chunk=env_chunk,
-                             flags=(_lib.QD_FLAG_VALIDATE if validate else 0) | (_lib.QD_FLAG_PIXEL_SEARCH if pixel_search else 0),
+                             flags=(_lib.QD_FLAG_VALIDATE if validate else 0) | (_lib.QD_FLAG_PIXEL_SEARCH if pixel_search else 0)
+                             | (_lib.QD_FLAG_GS_GERSHGORIN_ZERO if gs_gershgorin_zero else 0),
                              noise_flags=self.noise_flags, seed=self.seed, env_id_offset=self.env_id_offset)
         self._h = ctypes.c_void_p()
         rc = self._lib.qd_create(ctypes.byref(cfg), self.device.index, ctypes.byref(self._h))

@@ -12,7 +12,8 @@ for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_ANY SQ_WAIT_
            "SQ_THREAD_CYCLES_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INST_CYCLES_VMEM SQ_WAVES" \
            "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  rocprofv3 --pmc $set -d $out/p$i --output-format csv -- python3 scripts/kbench.py "$@" > $out/p$i.log 2>&1 || echo "pass $i failed"
+  # (a pass that fails or runs out of time ends the collection: nothing more is started on the GPU after it)
+  timeout -k 10 420 rocprofv3 --pmc $set -d $out/p$i --output-format csv -- python3 scripts/kbench.py "$@" > $out/p$i.log 2>&1 || { echo "pass $i failed"; exit 1; }
 done
 python3 scripts/pmc_summary.py $out > $out/summary.csv
 grep "qd_k_tile\|qd_k_candidates\|qd_k_gs_" $out/summary.csv

@@ -1,14 +1,18 @@
 """Diagnostic: counters of the ground-state stage's eigen-solver phase (validate mode, `VecQuantumDeviceEnv.solver_stats()`):
 tasks (hop components of >= 2 states that survive the Gershgorin test) per pixel and by size class, Laguerre iterations per
 task and per 64-task wave tile (a tile waits for its slowest lane), lane fill of the tiles -- after reset and in the bench's
-random-action regime.    python scripts/solver_stats.py [envs] [steps]"""
+random-action regime.    python scripts/solver_stats.py [envs] [steps] [zero]
+("zero": a QD_FLAG_GS_GERSHGORIN_ZERO handle, components pruned against the bound 0 alone)"""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "rl-agent-for-qubit-array-tuning_amd"))
 import numpy as np, torch
 from qadapt_hip.vec_env import VecQuantumDeviceEnv, SyntheticCapacitanceModel
 N = 8; B = int(sys.argv[1]) if len(sys.argv) > 1 else 48; K = int(sys.argv[2]) if len(sys.argv) > 2 else 12
-env = VecQuantumDeviceEnv(B, num_dots=N, resolution=64, seed=1234, validate=True, capacitance_model=SyntheticCapacitanceModel(1))
+ZERO = len(sys.argv) > 3 and sys.argv[3] == "zero"
+env = VecQuantumDeviceEnv(B, num_dots=N, resolution=64, seed=1234, validate=True, capacitance_model=SyntheticCapacitanceModel(1),
+                          gs_gershgorin_zero=ZERO)
+print("bound 0 (QD_FLAG_GS_GERSHGORIN_ZERO)" if ZERO else "pair bound (default)")
 env.reset()
 prev = None
 def report(tag):
