@@ -257,7 +257,8 @@ int qd_probe(qd_handle* h, const int32_t* env_of_query_dev, int nq, const double
  * nothing more than qd_probe does.  QD_ERR_ARG, found without touching the device, besides qd_probe's: a struct_size
  * that is not sizeof(qd_probe_opts), a noise_flags bit outside QD_NOISE_SENSOR | QD_NOISE_RADIAL | QD_NOISE_LATCH.
  * A QD_FLAG_VALIDATE handle answers QD_ERR_STATE.  Channel sub-ranges, asymmetric windows and a virtual gate matrix
- * or noise centre per query are not built. */
+ * or noise centre per query are not built for probes; qd_scan2d below renders one image over any two controls and
+ * ranges, with a virtual gate matrix per query. */
 typedef struct qd_probe_opts {
     int32_t  struct_size;   /* = sizeof(qd_probe_opts) */
     int32_t  noise_flags;   /* QD_NOISE_* stages to run on the queries; 0 = none.  Independent of the handle's noise_flags */
@@ -307,6 +308,69 @@ int qd_probe_ex(qd_handle* h, const int32_t* env_of_query_dev, int nq, const dou
 int qd_eval_points(qd_handle* h, const int32_t* group_env_host, const int64_t* group_start_host, int ng,
                    const double* vg_dev, const double* vb_dev, const double* gamma_host,
                    double* signal_dst, double* occ_dst, void* stream);
+
+/* Stateless 2-D scans over ANY two controls, each over its own [lo, hi]: the reference model layer's
+ * do2d_open(x_gate, x_min, x_max, ..., y_gate, ...) and GateVoltageComposer.do2d(..., gate_voltages, add_full_crosstalk)
+ * (GateVoltageComposer.py:170-211) for nq queries in one call -- a non-adjacent plunger pair, a plunger against a barrier,
+ * a sensor-gate sweep, one channel where a caller needs one and not N-1, a scan under a hypothetical virtual gate matrix --
+ * with the measurement stages of a step (sensor noise, latching) and its normalisation.
+ * Controls are indexed in the order of the model's voltage vector: 0..N-1 the plungers, N the sensor gate, N+1..2N-1 the
+ * barriers.  With W[2N] = [gate_v, sensor_v, barrier_v] of the query, pixel (row y, column x) has
+ * W[ax] = linspace(x_lo, x_hi, R)[x] and W[ay] = linspace(y_lo, y_hi, R)[y]: x is the first axis and runs along columns.
+ *   QD_SCAN_VIRTUAL   the model sees VGM W[0:N+1] + origin for the gates and W[N+1:] for the barriers, VGM the env's
+ *                     current virtual gate matrix or the query's
+ *   QD_SCAN_PHYSICAL  the model sees W: no matrix and no origin, as qd_eval_points takes its voltages
+ *   env_of_query_dev [nq]      int32, the env whose device (parameter block, virtual gate matrix) renders query q
+ *   axes_dev         [nq][2]   int32 (ax, ay)
+ *   range_dev        [nq][4]   x_lo, x_hi, y_lo, y_hi; lo > hi sweeps downwards, lo == hi repeats a 1-D sweep
+ *   gate_v_dev       [nq][N], barrier_v_dev [nq][N-1], sensor_v_dev [nq] or NULL (0.0): the controls that are not swept
+ *   raw_dst          [nq][P]    float64 unnormalised signal; may be NULL
+ *   image_dst        [nq][R][R] float32, normalised per query with its own 0.5 / 99.5 percentiles; may be NULL
+ *   plohi_dst        [nq][2]    those percentiles; may be NULL
+ * opts (NULL: virtual frame, deterministic):
+ *   frame         QD_SCAN_VIRTUAL or QD_SCAN_PHYSICAL, for all queries of the call
+ *   noise_flags   QD_NOISE_SENSOR | QD_NOISE_LATCH stages to run.  QD_NOISE_RADIAL is QD_ERR_ARG: the reference defines its
+ *                 centre only for the env's own adjacent-pair observation
+ *   serial, stream_base   as in qd_probe_opts: the caller owns the serial, query q draws from the streams of global env
+ *                 id stream_base + q; the channel word of the Philox counter is 0
+ *   vgm_dev       [nq][N+1][N+1] row-major or NULL: the env's current matrix (virtual frame only)
+ *   gamma_dev     [nq] peak widths, or NULL: with two virtual plungers as axes the rule of a step on those two plungers'
+ *                 base voltages (vary_peak_width handles; the env's constant otherwise), else the env's constant
+ *   occ_dst       [nq][P][N] float64 or NULL: the occupations the signal was formed from (after latching, if it ran)
+ * A query occupies one slot of the scan buffers with ONE channel image.  The two search kernels run with the scan front
+ * end (csrc/qd_pixel.h qd_scan_voltages; the tile search learns the affine model of v' from lane differences and does not
+ * know which controls are swept); structure, solve, select, latching rows, telegraph chains, sensor stage and percentiles
+ * are the kernels of a step or probe.  With ax = c, ay = c + 1, x_lo = fl(v_c - w), x_hi = fl(v_c + w) (likewise y) and the
+ * virtual frame the front end performs the operations of a probe's in the same order: raw equals channel c of qd_probe
+ * with window w bit for bit (image and percentiles too where C = 1), and with noise channel 0 equals qd_probe_ex.
+ * On a QD_FLAG_PIXEL_SEARCH handle raw equals qd_eval_points at the pixels' voltages bit for bit.
+ * Stream-ordered with no host wait after the first call, which allocates the scratch (per query in flight: a parameter
+ * copy, a state block, an axes descriptor, P doubles of signal; P*N doubles of occupations and ceil(P/64) telegraph words
+ * from the first call that needs them) with hipMalloc; qd_destroy frees it.  nq may exceed B; queries run in chunks of
+ * qd_chunk_envs and results do not depend on the chunking.  The call changes nothing that qd_step, qd_observe, qd_probe*,
+ * qd_eval_points or any qd_get_* function can see.
+ * QD_ERR_ARG, found without reading the device: NULL env_of_query_dev, axes_dev, range_dev, gate_v_dev or barrier_v_dev,
+ * nq < 0, a struct_size that is not sizeof(qd_scan_opts), an unknown frame, vgm_dev with the physical frame, a noise bit
+ * outside SENSOR | LATCH.  Axes arrive on the device: an axis outside [0, 2N), ax == ay or an env id outside [0, B) makes
+ * the query inert, its destination slots are left untouched.  QD_ERR_STATE: QD_FLAG_VALIDATE handles and handles in the
+ * full charge-state space, as qd_eval_points refuses them.  Radial noise, more than two swept controls and Rx != Ry are
+ * not built. */
+#define QD_SCAN_VIRTUAL 0
+#define QD_SCAN_PHYSICAL 1
+typedef struct qd_scan_opts {
+    int32_t  struct_size;   /* = sizeof(qd_scan_opts) */
+    int32_t  frame;         /* QD_SCAN_VIRTUAL 0 / QD_SCAN_PHYSICAL 1 */
+    int32_t  noise_flags;   /* QD_NOISE_SENSOR | QD_NOISE_LATCH; 0 = none */
+    int32_t  reserved;
+    uint64_t serial;        /* the observation-number word of the Philox counter */
+    int64_t  stream_base;   /* query q draws from the streams of global env id stream_base + q (mod 2^32) */
+    const double* vgm_dev;  /* [nq][G][G] or NULL: the env's current matrix (virtual frame only) */
+    const double* gamma_dev;/* [nq] or NULL */
+    double*  occ_dst;       /* [nq][P][N] or NULL */
+} qd_scan_opts;
+int qd_scan2d(qd_handle* h, const int32_t* env_of_query_dev, int nq, const int32_t* axes_dev, const double* range_dev,
+              const double* gate_v_dev, const double* barrier_v_dev, const double* sensor_v_dev, double* raw_dst,
+              float* image_dst, double* plohi_dst, const qd_scan_opts* opts, void* stream);
 
 /* Stitches one channel of nx*ny probe signals into one composite image on the device (map_device_range.py:134-170,
  * map_full_device_range.py:168-194).  raw_dev [nx*ny][C][P] as qd_probe wrote it, query index i*ny + j for scan (i, j);

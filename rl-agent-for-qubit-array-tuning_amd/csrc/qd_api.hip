@@ -12,6 +12,7 @@
 #include "qd_probe.h"
 #include "qd_latch.h"
 #include "qd_points.h"
+#include "qd_scan.h"
 #include "qd_scratch.h"
 
 // The owners of a stream and of an event.  With the two memory policies of qd_scratch.h these are the only places that
@@ -137,6 +138,9 @@ struct qd_handle {
     // point evaluation (qd_eval_points): parameter and state copies, sensor constants and occupations of the slots in flight,
     // allocated by the first call
     QdScratchSet points;
+    // axis scans (qd_scan2d): one launch chunk of parameter copies, state blocks (with the axes descriptors), P doubles of signal and
+    // percentiles per query in flight (occupations and telegraph words when asked for), allocated by the first call
+    QdScratchSet scan;
     mutable char err[512];                  // (the launchers take the handle const and still report through it)
 };
 
@@ -510,8 +514,9 @@ static hipError_t qd_launch_solve(const qd_handle* h, const QdLane& ln, hipStrea
 
 // a11-a13 + a15 for the envs at list positions [base, base + cnt): structure -> solve per size class -> select (those of
 // them in `st`), in launches of at most gs_chunk envs (the slabs in flight)
+// C: channel images per env block (h->C, or 1 on the buffers of qd_scan2d)
 static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, const int32_t* env_ids, int base, int cnt,
-                            hipStream_t s, int st) {
+                            hipStream_t s, int st, int C) {
     const int nb = (h->P + h->ppb - 1) / h->ppb;
     unsigned* tilelist = ln.gtiles.p + 16;
     const bool val = qd_validate(h);
@@ -520,8 +525,8 @@ static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane
     const int rec0 = val ? base : 0;
     for (int off = 0; off < cnt; off += h->gs_chunk) {
         const int n = cnt - off < h->gs_chunk ? cnt - off : h->gs_chunk;
-        const QdGsGeom g{n, h->C, h->P, nb};
-        const unsigned batches = (unsigned)((size_t)n * h->C * nb);
+        const QdGsGeom g{n, C, h->P, nb};
+        const unsigned batches = (unsigned)((size_t)n * C * nb);
         if (st & QD_ST_STRUCTURE) {
             QD_HIP(hipMemsetAsync(ln.gtiles.p, 0, sizeof(unsigned) * 16, s));
             if (h->full_m) {
@@ -618,11 +623,31 @@ static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane
 
 // a5-a13 for `cnt` envs starting at list position `base`: those of the stages in `st` that the handle has (qd_stages) --
 // tile search + exact redo pass or the per-pixel search alone, then the ground-state kernels.
+// scan (qd_scan2d): slot k renders ONE image over the axes in its state block copy instead of the env's C channel images.
 static int qd_launch_csd(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, const int32_t* env_ids, int base, int cnt,
-                         hipStream_t s, int st) {
+                         hipStream_t s, int st, bool scan = false) {
     st &= qd_stages(h);
     // validate mode keeps the reference order; K < KC needs it too, the ground-state stage takes the first K
     const int sorted = (qd_validate(h) || h->kept != h->kc) ? 1 : 0;
+    const int C = scan ? 1 : h->C;
+    if (scan) {
+        if (st & QD_ST_TILE) {
+            const int tiles = ((h->R + 7) / 8) * ((h->R + 7) / 8);
+            QD_DISPATCH_TILE(h->N, QD_DISPATCH_KC(h->kc, qd_k_tile<NN, KK, QdFrontScan><<<dim3(tiles, 1, cnt), dim3(64), 0, s>>>(env_ids,
+                             base, h->R, b.params, b.state, ln.recs.p, sorted, 0, h->tstats.p)));
+            QD_HIP(hipGetLastError());
+        }
+        if (st & QD_ST_REDO) {
+            const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
+            const dim3 g1(qd_cand_blocks(h->R), 1, cnt);
+            QD_DISPATCH_BOOL(h->tile_search != 0, TILED, QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
+                qd_k_candidates<NN, TILED, KK, QdFrontScan><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R, b.params, b.state,
+                                                                                                 ln.recs.p, sorted, 0))));
+            QD_HIP(hipGetLastError());
+        }
+        if (st & QD_ST_GROUND) return qd_launch_ground(h, b, ln, env_ids, base, cnt, s, st, C);
+        return QD_OK;
+    }
     if (st & QD_ST_TILE) {
         const int tiles = ((h->R + 7) / 8) * ((h->R + 7) / 8);
         QD_DISPATCH_TILE(h->N, QD_DISPATCH_KC(h->kc, qd_k_tile<NN, KK><<<dim3(tiles, h->C, cnt), dim3(64), 0, s>>>(env_ids, base, h->R,
@@ -637,14 +662,16 @@ static int qd_launch_csd(const qd_handle* h, const QdEnvBufs& b, const QdLane& l
                                                                               b.noise_flags))));
         QD_HIP(hipGetLastError());
     }
-    if (st & QD_ST_GROUND) return qd_launch_ground(h, b, ln, env_ids, base, cnt, s, st);
+    if (st & QD_ST_GROUND) return qd_launch_ground(h, b, ln, env_ids, base, cnt, s, st, C);
     return QD_OK;
 }
 
 // a16 on the signal of `n` envs (their list `ids`, or 0..n-1), in place
-static int qd_launch_sensor(const qd_handle* h, const QdEnvBufs& b, const int32_t* ids, int n, hipStream_t s) {
-    const dim3 g3((h->P + 255) / 256, h->C, n);
-    QD_DISPATCH_N(h->N, qd_k_sensor<NN><<<g3, dim3(256), 0, s>>>(ids, h->R, b.params, b.state, b.zraw, qd_noise_cfg(h, b)));
+// (one_channel: the buffers of qd_scan2d, one image per block)
+static int qd_launch_sensor(const qd_handle* h, const QdEnvBufs& b, const int32_t* ids, int n, hipStream_t s, bool one_channel = false) {
+    const dim3 g3((h->P + 255) / 256, one_channel ? 1 : h->C, n);
+    if (one_channel) { QD_DISPATCH_N(h->N, qd_k_sensor<NN, 1><<<g3, dim3(256), 0, s>>>(ids, h->R, b.params, b.state, b.zraw, qd_noise_cfg(h, b))); }
+    else { QD_DISPATCH_N(h->N, qd_k_sensor<NN><<<g3, dim3(256), 0, s>>>(ids, h->R, b.params, b.state, b.zraw, qd_noise_cfg(h, b))); }
     QD_HIP(hipGetLastError());
     return QD_OK;
 }
@@ -843,6 +870,76 @@ extern "C" int qd_probe(qd_handle* h, const int32_t* env_of_query, int nq, const
     return qd_probe_ex(h, env_of_query, nq, gate_v, barrier_v, sensor_v, window, raw_dst, image_dst, plohi_dst, nullptr, stream);
 }
 
+extern "C" int qd_scan2d(qd_handle* h, const int32_t* env_of_query, int nq, const int32_t* axes, const double* range,
+                         const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst, float* image_dst,
+                         double* plohi_dst, const qd_scan_opts* opts, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    if (nq < 0) return qd_fail(h, QD_ERR_ARG, "qd_scan2d: nq < 0");
+    if (!env_of_query || !axes || !range) return qd_fail(h, QD_ERR_ARG, "qd_scan2d: env_of_query_dev, axes_dev or range_dev is NULL");
+    if (!gate_v || !barrier_v) return qd_fail(h, QD_ERR_ARG, "qd_scan2d: gate_v_dev or barrier_v_dev is NULL");
+    if (opts && opts->struct_size != (int32_t)sizeof(qd_scan_opts))
+        return qd_fail(h, QD_ERR_ARG, "qd_scan2d: opts->struct_size is not sizeof(qd_scan_opts)");
+    if (opts && opts->frame != QD_SCAN_VIRTUAL && opts->frame != QD_SCAN_PHYSICAL)
+        return qd_fail(h, QD_ERR_ARG, "qd_scan2d: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL");
+    if (opts && opts->frame == QD_SCAN_PHYSICAL && opts->vgm_dev)
+        return qd_fail(h, QD_ERR_ARG, "qd_scan2d: vgm_dev has no meaning in the physical frame");
+    if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_LATCH)))
+        return qd_fail(h, QD_ERR_ARG, "qd_scan2d: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
+                                      "centred on the env's own adjacent-pair observation)");
+    if (h->cfg.flags & QD_FLAG_VALIDATE)
+        return qd_fail(h, QD_ERR_STATE, "qd_scan2d: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
+                                        "B envs' last observe and renders no scans; use a handle without the flag");
+    if (h->full_m)
+        return qd_fail(h, QD_ERR_STATE, "qd_scan2d: the full charge-state space synthesises its own voltages "
+                                        "(qd_k_full_structure); a scan front end for it is not built");
+    if (nq == 0) return QD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    QD_ON_DEVICE(h);
+    const int flags = opts ? opts->noise_flags : 0;
+    double* const occ_dst = opts ? opts->occ_dst : nullptr;
+    const bool want_occ = (flags & QD_NOISE_LATCH) || occ_dst, want_tel = (flags & QD_NOISE_SENSOR) != 0;
+    const int pc = h->chunk;                                  // queries in flight = envs per launch chunk (lane 0's scratch)
+    const size_t P = (size_t)h->P;
+    QD_HIP(h->scan.reserve(h->L, P, (size_t)pc, 2, want_occ ? P * h->N : 0, want_tel ? (size_t)h->tel_words : 0));
+    // the hot launchers run on the scan blocks with ONE channel image per slot, without eigenvalues; occupations, telegraph
+    // words and noise only as asked for, keyed by the caller's serial and stream base; nothing of the envs is written
+    QdEnvBufs sb = h->scan.view();
+    sb.occ = want_occ ? h->scan.occ.p : nullptr;
+    sb.noise_flags = flags;
+    if (want_tel) { sb.tel = h->scan.tel.p; sb.tel_words = h->tel_words; }
+    sb.serial = opts ? opts->serial : 0;
+    const QdScanQuery Q{env_of_query, axes, range, gate_v, barrier_v, sensor_v, opts ? opts->vgm_dev : nullptr,
+                        opts ? opts->gamma_dev : nullptr, opts ? opts->frame : QD_SCAN_VIRTUAL};
+    for (int base = 0; base < nq; base += pc) {
+        const int cnt = nq - base < pc ? nq - base : pc;
+        sb.env_off = (uint32_t)((opts ? opts->stream_base : 0) + base);      // slot k of the chunk draws as global env stream_base + base + k
+        qd_k_scan_gather<<<dim3(cnt), dim3(QD_SCAN_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, sb.params, sb.state);
+        QD_HIP(hipGetLastError());
+        if (want_tel) {
+            qd_k_telegraph<<<dim3((cnt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, 1, h->P, h->L.size, h->L.noise, sb.params, sb.tel,
+                                                                      qd_noise_cfg(h, sb));
+            QD_HIP(hipGetLastError());
+        }
+        if (int rc = qd_launch_csd(h, sb, h->lanes[0], nullptr, 0, cnt, s, QD_ST_ALL, true)) return rc;
+        if (flags & QD_NOISE_LATCH) {
+            const long rows = (long)cnt * h->R;
+            QD_DISPATCH_N(h->N, qd_k_latch_rows<NN, 1><<<dim3((unsigned)((rows + QD_LATCH_ROWS_BLOCK - 1) / QD_LATCH_ROWS_BLOCK)),
+                                                         dim3(QD_LATCH_ROWS_BLOCK), 0, s>>>(cnt, h->R, sb.params, sb.state, sb.occ, sb.zraw,
+                                                                                            qd_noise_cfg(h, sb)));
+            QD_HIP(hipGetLastError());
+        }
+        if (int rc = qd_launch_sensor(h, sb, nullptr, cnt, s, true)) return rc;
+        qd_launch_percentile(nullptr, (unsigned)cnt, (long)h->P, sb.zraw, sb.plohi, s);
+        QD_HIP(hipGetLastError());
+        if (raw_dst || image_dst || plohi_dst || occ_dst) {
+            qd_k_scan_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, h->P, sb.zraw, sb.plohi, sb.occ,
+                                                                                raw_dst, image_dst, plohi_dst, occ_dst);
+            QD_HIP(hipGetLastError());
+        }
+    }
+    return QD_OK;
+}
+
 // slots in flight of qd_eval_points: one launch chunk of lane 0's records, at most QD_POINTS_SLOTS
 static int qd_points_slots(const qd_handle* h) { return h->chunk < QD_POINTS_MAX_SLOTS ? h->chunk : QD_POINTS_MAX_SLOTS; }
 
@@ -898,7 +995,7 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
         // qd_get_occupations returns: with K == KC (search order) the records are sorted and the ground-state stage runs again.
         const bool resort = !sorted && occ_dst;
         if (signal_dst || !resort) {
-            if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND)) return rc;
+            if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND, h->C)) return rc;
             if (signal_dst || occ_dst) {
                 QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, qb.params, qb.zraw, qb.occ,
                                                                                                signal_dst, resort ? nullptr : occ_dst));
@@ -909,7 +1006,7 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
             const long nrec = (long)n * CP;
             QD_DISPATCH_KC(h->kc, qd_k_points_sort<KK><<<dim3((unsigned)((nrec + 63) / 64)), dim3(64), 0, s>>>(ln.recs.p, nrec));
             QD_HIP(hipGetLastError());
-            if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND)) return rc;
+            if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND, h->C)) return rc;
             QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, qb.params, qb.zraw, qb.occ,
                                                                                            nullptr, occ_dst));
             QD_HIP(hipGetLastError());

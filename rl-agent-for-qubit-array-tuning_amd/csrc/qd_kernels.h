@@ -175,7 +175,9 @@ __global__ void qd_k_telegraph(const int* __restrict__ env_ids, int n_env, int C
 // REDO: second pass behind the tile search (only the pixels it flagged; their front end comes with the record).
 // KC: size of the kept set (8, 16, 32; the record's slots >= KC are not written).  A handle with K < KC states asks for
 // sort_output and the ground-state stage takes the first K.
-template <int N, bool REDO, int KC>
+// FE: the front end (qd_pixel.h).  QdFrontEnv is the env's observation pattern; QdFrontScan (qd_scan2d) renders ONE image
+// per slot over the two controls of the slot's QdScanAxes, grid = (blocks, 1, slots).
+template <int N, bool REDO, int KC, class FE = QdFrontEnv>
 __global__ void __launch_bounds__(QD_CAND_BLOCK, QD_CAND_WAVES)
 qd_k_candidates(const int* __restrict__ env_ids, int env_base, int R, const double* __restrict__ params,
                 const double* __restrict__ state, QdPixelRec* __restrict__ recs, int sort_output, int noise_flags) {
@@ -205,7 +207,7 @@ qd_k_candidates(const int* __restrict__ env_ids, int env_base, int R, const doub
     uint16_t* sid = (uint16_t*)(se + KC * QD_CAND_BLOCK);     // [KC][BLOCK]
     if (!inside) return;
     if (qd_radial_replaced(spar, sst, L, ch, noise_flags)) return;   // image will be pure noise: nothing to solve
-    QdPixelRec* rec = recs + ((size_t)slot * (N - 1) + ch) * P + p;
+    QdPixelRec* rec = recs + ((size_t)slot * FE::channels(N) + ch) * P + p;
     // second pass behind the tile search (qd_tile.h): only the pixels it left to the exact per-pixel search
     if (only_flagged == 1 && rec->nvalid != QD_T_REDO) return;
     double vd[N], ncont[N], isa;
@@ -216,7 +218,7 @@ qd_k_candidates(const int* __restrict__ env_ids, int env_base, int R, const doub
         isa = rec->E[16];
     } else {
         double v_ext[V], vpp[G], tc[NB];
-        qd_pixel_voltages<N>(spar, sst, ch, R, x, y, v_ext, vpp, tc);
+        FE::template voltages<N>(spar, sst, ch, R, x, y, v_ext, vpp, tc);
         // the sensor stage wants the constant-matrix product: hand it over before v' is rescaled
 #pragma unroll
         for (int i = 0; i < G; ++i) rec->vpp[i] = vpp[i];
@@ -499,7 +501,8 @@ __global__ void qd_k_latch(const int* __restrict__ env_ids, int n_env, int R, co
 // eta = sensor-potential noise (white + telegraph), then radial image noise / replacement.
 // grid = (ceil(P/256), C, n_env)
 // ---------------------------------------------------------------------------
-template <int N>
+// C: channel images per env block (N - 1 in a step or probe; 1 on the buffers of qd_scan2d)
+template <int N, int C = N - 1>
 __global__ void qd_k_sensor(const int* __restrict__ env_ids, int R, const double* __restrict__ params,
                             const double* __restrict__ state, double* __restrict__ zraw, QdNoiseCfg nz) {
     constexpr int G = N + 1;
@@ -512,7 +515,7 @@ __global__ void qd_k_sensor(const int* __restrict__ env_ids, int R, const double
     const double* par = params + (size_t)e * L.size;
     const double* st = state + (size_t)e * L.s_size;
     const uint32_t k1 = nz.env_off + (uint32_t)e;
-    double* zp = zraw + ((size_t)e * (N - 1) + ch) * P + p;
+    double* zp = zraw + ((size_t)e * C + ch) * P + p;
     if (qd_radial_replaced(par, st, L, ch, nz.flags)) {
         // qarray_base_class.py:466-468: np.random.randn(*z.shape)
         const QdPhilox r = qd_philox4x32_10((uint32_t)p, (uint32_t)ch | (QD_RNG_RADIAL << 16), nz.ser_lo, nz.ser_hi, nz.seed, k1);
@@ -529,7 +532,7 @@ __global__ void qd_k_sensor(const int* __restrict__ env_ids, int R, const double
         const QdPhilox r = qd_philox4x32_10((uint32_t)p, (uint32_t)ch | (QD_RNG_WHITE << 16), nz.ser_lo, nz.ser_hi, nz.seed, k1);
         double z0, z1; qd_normal2(r, z0, z1);
         eta = par[L.noise + 0] * z0;
-        const unsigned long long w = nz.tel[((size_t)e * (N - 1) + ch) * nz.tel_words + (p >> 6)];
+        const unsigned long long w = nz.tel[((size_t)e * C + ch) * nz.tel_words + (p >> 6)];
         if ((w >> (p & 63)) & 1ull) eta += par[L.noise + 3];
     }
     double s = 0.0;

@@ -56,11 +56,11 @@ QD_HD void qd_latch_row(const double* par, const QdLayout& L, double* occ_row, d
 // N*8-byte records front to back, as the one thread of qd_k_latch does, and the R-fold parallelism is the gain.
 // Replaced channels (qd_radial_replaced: qd_k_sensor writes pure noise) return at once.  grid = ceil(n_slots C R / 64).
 #define QD_LATCH_ROWS_BLOCK 64
-template <int N>
+// C: channel images per slot (N - 1 on probe buffers; 1 on those of qd_scan2d)
+template <int N, int C = N - 1>
 __global__ void __launch_bounds__(QD_LATCH_ROWS_BLOCK)
 qd_k_latch_rows(int n_slots, int R, const double* __restrict__ params, const double* __restrict__ state,
                 double* __restrict__ occ, double* __restrict__ zraw, QdNoiseCfg nz) {
-    constexpr int C = N - 1;
     const QdLayout L = qd_layout(N);
     const long t = (long)blockIdx.x * QD_LATCH_ROWS_BLOCK + threadIdx.x;
     if (t >= (long)n_slots * C * R) return;

@@ -86,6 +86,87 @@ QD_HD void qd_pixel_voltages(const double* par, const double* st, int ch, int R,
 }
 
 // ---------------------------------------------------------------------------
+// Second front end (qd_scan2d): a 2-D scan over ANY two controls, each over its own [lo, hi].  Controls are indexed in
+// the order of v_ext: 0..N-1 plungers, N the sensor gate, N+1..2N-1 the barriers.  With W[2N] = [gate_v, sensor_v,
+// barrier_v] of the state block, W[ax] = linspace(x_lo, x_hi, R, x) and W[ay] = linspace(y_lo, y_hi, R, y): x is the
+// first axis and runs along columns, as meshgrid_virtual_coupled places dots[0] (GateVoltageComposer.py:170-211).
+//   QD_SCAN_VIRTUAL   v_ext[0:G] = VGM W[0:G] + origin, v_ext[G:] = W[G:]   (do2d with add_full_crosstalk)
+//   QD_SCAN_PHYSICAL  v_ext = W: no matrix, no origin, as qd_eval_points takes its voltages (do2d_open)
+// vpp and tc as in qd_pixel_voltages.  With ax = c, ay = c + 1, x_lo = fl(v_c + (-w)), x_hi = fl(v_c + w) (likewise y)
+// and the virtual frame this performs the operations of qd_pixel_voltages in the same order: same bits.
+// ---------------------------------------------------------------------------
+#define QD_SCAN_VIRTUAL 0
+#define QD_SCAN_PHYSICAL 1
+struct QdScanAxes {
+    double x_lo, x_hi, y_lo, y_hi;
+    int32_t ax, ay, frame, pad;
+};
+
+template <int N>
+QD_HD void qd_scan_voltages(const double* par, const double* st, const QdScanAxes& axes, int R, int x, int y,
+                            double* v_ext, double* vpp, double* tc) {
+    constexpr int G = N + 1, NB = N - 1, V = 2 * N;
+    const QdLayout L = qd_layout(N);
+    const double* vgm = st + L.s_vgm;
+    double W[V];
+#pragma unroll
+    for (int i = 0; i < N; ++i) W[i] = st[L.s_gate_v + i];
+    W[N] = st[L.s_sensor_gt];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) W[G + b] = st[L.s_barrier_v + b];
+    const double sx = qd_linspace(axes.x_lo, axes.x_hi, R, x);
+    const double sy = qd_linspace(axes.y_lo, axes.y_hi, R, y);
+    const int ax = axes.ax, ay = axes.ay;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {            // static indices only (keeps W in registers)
+        if (i == ax) W[i] = sx;
+        if (i == ay) W[i] = sy;
+    }
+    if (axes.frame == QD_SCAN_PHYSICAL) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) v_ext[i] = W[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < G; ++i) { v_ext[i] = qd_dotN<G>(vgm + i * G, W) + par[L.origin + i]; QD_ROW_FENCE(); }
+#pragma unroll
+        for (int b = 0; b < NB; ++b) v_ext[G + b] = W[G + b];
+    }
+#pragma unroll
+    for (int i = 0; i < G; ++i) { vpp[i] = qd_dotN<V>(par + L.cgd + i * V, v_ext); QD_ROW_FENCE(); }
+    const double tc_base = par[L.scal + 0];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        double vb_eff = v_ext[G + b] + qd_dotN<G>(par + L.cbg + b * G, v_ext);
+        tc[b] = tc_base * exp(-par[L.alpha + b] * vb_eff);
+        QD_ROW_FENCE();
+    }
+}
+
+// The front end of a search kernel as a policy: how many channel images a slot holds and where a pixel's voltages come
+// from.  QdFrontEnv is the env's observation pattern (channel ch sweeps virtual plungers ch, ch + 1 over +-window).
+// QdFrontScan is one image per slot over the slot's QdScanAxes, which travels in the slot's own STATE BLOCK COPY in the
+// place of the Kalman means (s_kmean: 2 N^2 >= 8 doubles with the variances; the scan's gather kernel writes it there and
+// no kernel behind a scan reads the Kalman block), so the search kernels keep their arguments.
+struct QdFrontEnv {
+    static constexpr int channels(int N) { return N - 1; }
+    template <int N>
+    static QD_HD void voltages(const double* par, const double* st, int ch, int R, int x, int y, double* v_ext, double* vpp,
+                               double* tc) {
+        qd_pixel_voltages<N>(par, st, ch, R, x, y, v_ext, vpp, tc);
+    }
+};
+static_assert(sizeof(QdScanAxes) == 6 * sizeof(double), "the descriptor overlays 6 doubles of the state block copy");
+QD_HD const QdScanAxes* qd_scan_axes_of(const double* st, const QdLayout& L) { return reinterpret_cast<const QdScanAxes*>(st + L.s_kmean); }
+struct QdFrontScan {
+    static constexpr int channels(int) { return 1; }
+    template <int N>
+    static QD_HD void voltages(const double* par, const double* st, int, int R, int x, int y, double* v_ext, double* vpp,
+                               double* tc) {
+        qd_scan_voltages<N>(par, st, *qd_scan_axes_of(st, qd_layout(N)), R, x, y, v_ext, vpp, tc);
+    }
+};
+
+// ---------------------------------------------------------------------------
 // a8 continuous ground state, with the optional linear voltage-dependent
 // capacitance model (f4; voltage_dependent_capacitance.py:72-88, ground_state.py:53-57):
 //   cdd(V) = cdd_full (1 + alpha mean|v_ext|),  cgd(V) = cgd_full (1 + beta mean|v_ext|)
@@ -179,6 +260,15 @@ QD_HD double qd_peak_width(const double* par, const double* st, const QdLayout& 
     const double g0 = par[L.scal + 1], a = par[L.scal + 3];
     if (a < 0.0) return g0;
     const double vavg = (fabs(st[L.s_gate_v + ch]) + fabs(st[L.s_gate_v + ch + 1])) / 2.0;
+    const double w = g0 - fabs(a * vavg);
+    return fmin(fmax(w, 0.0), 1.0);
+}
+// the same rule for a scan whose two axes are the virtual plungers i and j (qd_scan2d): qd_peak_width's operations with
+// those two base voltages, so i = ch, j = ch + 1 gives its bits
+QD_HD double qd_peak_width_pair(const double* par, const double* st, const QdLayout& L, int i, int j) {
+    const double g0 = par[L.scal + 1], a = par[L.scal + 3];
+    if (a < 0.0) return g0;
+    const double vavg = (fabs(st[L.s_gate_v + i]) + fabs(st[L.s_gate_v + j])) / 2.0;
     const double w = g0 - fabs(a * vavg);
     return fmin(fmax(w, 0.0), 1.0);
 }

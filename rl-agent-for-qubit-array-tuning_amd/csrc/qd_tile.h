@@ -131,7 +131,10 @@ __device__ __forceinline__ void qd_tile_hand_over(QdPixelRec* rec, const double*
 // states in S; [8 + reason]: tiles redone by reason (1 ranges, 2 seeds, 3 frontier overflow, 4 too few leaves, 5 |S|)
 // ---------------------------------------------------------------------------------------------
 // Writes one QdPixelRec per pixel for the ground-state kernels (qd_k_gs_*): the KC lowest states (slots >= KC untouched).
-template <int N, int KC>
+// FE: the front end (qd_pixel.h).  QdFrontEnv is the env's observation pattern; QdFrontScan (qd_scan2d) renders ONE image
+// per slot over the two controls of the slot's QdScanAxes, grid = (tiles, 1, slots).  The search learns the affine model
+// of v' from lane differences and does not know which controls are swept.
+template <int N, int KC, class FE = QdFrontEnv>
 __global__ void __launch_bounds__(64)
 qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __restrict__ params,
           const double* __restrict__ state, QdPixelRec* __restrict__ recs, int sort_output, int noise_flags,
@@ -153,7 +156,7 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
     const double* spar = params + (size_t)e * L.size;
     const double* sst = state + (size_t)e * L.s_size;
     if (qd_radial_replaced(spar, sst, L, ch, noise_flags)) return;        // image will be pure noise: nothing to solve
-    QdPixelRec* rec = recs + ((size_t)slot * (N - 1) + ch) * P + p;
+    QdPixelRec* rec = recs + ((size_t)slot * FE::channels(N) + ch) * P + p;
     const double* A = spar + L.cdd_inv;                                   // row-major, lda = G
     const double* U = spar + L.ufac;
 
@@ -162,7 +165,7 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
     double vpp[G], tc[NB];
     {
         double v_ext[V];
-        qd_pixel_voltages<N>(spar, sst, ch, R, x, y, v_ext, vpp, tc);
+        FE::template voltages<N>(spar, sst, ch, R, x, y, v_ext, vpp, tc);
         if (inside) {
 #pragma unroll
             for (int i = 0; i < G; ++i) rec->vpp[i] = vpp[i];

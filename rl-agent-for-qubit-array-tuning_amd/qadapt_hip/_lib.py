@@ -18,6 +18,7 @@ QD_NOISE_RADIAL = 2
 QD_NOISE_LATCH = 4
 QD_MAP_GLOBAL, QD_MAP_PER_SCAN = 0, 1
 QD_POINTS_SLOTS = 64
+QD_SCAN_VIRTUAL, QD_SCAN_PHYSICAL = 0, 1
 QD_ERR_ARG, QD_ERR_HIP, QD_ERR_STATE = 1, 2, 3
 
 EXPORTS = [
@@ -28,6 +29,8 @@ EXPORTS = [
     "qd_time_ground_kernel", "qd_time_candidates_kernel", "qd_time_kernels", "qd_timed_kernel_name", "qd_chunk_envs",
     "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex",
 ]
+# exported too, kept apart: names with a digit, which a scan of qdsim.h for `qd_[a-z_]+(` does not find
+EXPORTS_WITH_DIGITS = ["qd_scan2d"]
 
 QD_CURVES = {"constant": 0, "polynomial": 1, "exponential": 2, "linear": 3}
 QD_UPDATE_KALMAN, QD_UPDATE_DIRECT = 0, 1
@@ -57,6 +60,16 @@ class QdProbeOpts(ctypes.Structure):
     _fields_ = [
         ("struct_size", ctypes.c_int32), ("noise_flags", ctypes.c_int32), ("serial", ctypes.c_uint64),
         ("stream_base", ctypes.c_int64), ("occ_dst", ctypes.c_void_p),
+    ]
+
+
+class QdScanOpts(ctypes.Structure):
+    """qd_scan_opts of include/qdsim.h: frame, stochastic stages, Philox serial and stream base of a qd_scan2d call, the
+    per-query virtual gate matrices and peak widths, and the device destination of its occupations."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("frame", ctypes.c_int32), ("noise_flags", ctypes.c_int32),
+        ("reserved", ctypes.c_int32), ("serial", ctypes.c_uint64), ("stream_base", ctypes.c_int64),
+        ("vgm_dev", ctypes.c_void_p), ("gamma_dev", ctypes.c_void_p), ("occ_dst", ctypes.c_void_p),
     ]
 
 
@@ -135,6 +148,8 @@ def lib():
     L.qd_eval_points.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, dp, dp, ctypes.POINTER(ctypes.c_double),
                                  dp, dp, vp]
     L.qd_eval_points.restype = ctypes.c_int
+    L.qd_scan2d.argtypes = [vp, vp, ctypes.c_int, vp, dp, dp, dp, dp, dp, fp, dp, ctypes.POINTER(QdScanOpts), vp]
+    L.qd_scan2d.restype = ctypes.c_int
     _LIB = L
     return L
 

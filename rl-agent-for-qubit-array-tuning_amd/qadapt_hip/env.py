@@ -60,7 +60,8 @@ class ModelFacade:
 class ArrayFacade:
     """`env.array` of the reference (a QarrayBaseClass) as far as its users outside step() need it: `model.cgd_full`,
     `model.charge_sensor_open` / `model.ground_state_open` (ModelFacade), `barrier_alpha`, `gate_ground_truth`, the scan geometry (`obs_voltage_min`, `obs_voltage_max`, `obs_image_size`,
-    `num_dots`, `num_barrier_voltages`) and the stateless `_get_obs` (qarray_base_class.py:171-229), rendered by the
+    `num_dots`, `num_barrier_voltages`), the stateless single image `_get_charge_sensor_data` and `scan2d` over any two
+    controls (the backend's scan2d), and the stateless `_get_obs` (qarray_base_class.py:171-229), rendered by the
     backend's probe on the current device without touching the episode; `_get_obs(..., noise=True)` runs the stochastic
     stages the env was created with, as the reference's call does, with fresh noise at every call (default: a clean scan).  The window is
     (obs_voltage_max - obs_voltage_min) / 2 around each gate voltage; it follows the device (`window_delta`) at every
@@ -103,6 +104,36 @@ class ArrayFacade:
         if image.shape != expected:
             raise ValueError(f"Image observation shape {image.shape} does not match expected {expected}")
         return {"image": image, "obs_gate_voltages": gate_voltages, "obs_barrier_voltages": barrier_voltages}
+
+    def _get_charge_sensor_data(self, gate1, gate2, gate_voltages, barrier_voltages=None, sensor_voltage=None):
+        """One (R, R) float64 image over the virtual gates `gate1` (columns) and `gate2` (rows), 1-indexed, each over the
+        env's window around its voltage (qarray_base_class.py:95-168).  The reference asserts an adjacent pair; any two
+        different gates in 1..N+1 are accepted (N+1 is the sensor gate)."""
+        assert (
+            len(gate_voltages) == self.num_dots
+        ), f"Incorrect gate voltage shape, expected {self.num_dots}, got {len(gate_voltages)}"
+        assert barrier_voltages is not None, "Barrier voltages must be provided for models with barriers"
+        assert (
+            len(barrier_voltages) == self.num_dots - 1
+        ), f"Incorrect barrier voltage shape, expected {self.num_dots - 1}, got {len(barrier_voltages)}"
+        G = self.num_dots + 1
+        gate1, gate2 = int(gate1), int(gate2)
+        if not (1 <= gate1 <= G and 1 <= gate2 <= G) or gate1 == gate2:
+            raise ValueError(f"gate1 and gate2 must be two different gates in 1..{G}, got {gate1} and {gate2}")
+        base = list(np.asarray(gate_voltages, np.float64)) + [0.0 if sensor_voltage is None else float(sensor_voltage)]
+        vmin, vmax = float(self.obs_voltage_min), float(self.obs_voltage_max)
+        ranges = [(base[g - 1] + vmin, base[g - 1] + vmax) for g in (gate1, gate2)]
+        out = self.scan2d(gate1 - 1, gate2 - 1, ranges[0], ranges[1], gate_voltages, barrier_voltages,
+                          sensor_voltage=sensor_voltage)
+        return out["raw"]
+
+    def scan2d(self, x, y, x_range, y_range, gate_voltages, barrier_voltages, sensor_voltage=None, **kw):
+        """The backend's scan2d for this env: one query, numpy results without the query axis ("raw" (R, R), ...)."""
+        out = self._b.scan2d([0], x, y, x_range, y_range, np.asarray(gate_voltages, np.float64)[None, :],
+                             np.asarray(barrier_voltages, np.float64)[None, :],
+                             sensor_voltage=None if sensor_voltage is None else float(sensor_voltage), **kw)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return {k: host(v)[0] for k, v in out.items()}
 
 
 class QuantumDeviceEnv:

@@ -106,6 +106,45 @@ def make_qd_config(config, qconfig, num_dots, resolution, batch, *, env_chunk=0,
                          barrier_radius=float(rew.get("barrier_radius", 0.0)))
 
 
+def scan_control_index(name, N, frame="virtual"):
+    """Index of one swept control of scan2d in the order of the model's voltage vector: 0..N-1 the plungers, N the sensor
+    gate, N+1..2N-1 the barriers.  `name` is such an index, or a name, 1-indexed as the reference's GateVoltageComposer
+    names its gates: "vP1".."vPN" in the virtual frame ("P1".."PN" in the physical frame), "S", "B1".."B{N-1}"."""
+    if isinstance(name, (int, np.integer)):
+        i = int(name)
+        if not 0 <= i < 2 * N:
+            raise ValueError(f"control index {i} outside [0, {2 * N})")
+        return i
+    if not isinstance(name, str):
+        raise TypeError(f"a control is an index or a name, got {type(name).__name__}")
+    if name == "S":
+        return N
+    plunger = "vP" if frame == "virtual" else "P"
+    other = "P" if frame == "virtual" else "vP"
+    for prefix, base, count in ((plunger, 0, N), ("B", N + 1, N - 1)):
+        if name.startswith(prefix) and name[len(prefix):].isdigit():
+            k = int(name[len(prefix):])
+            if not 1 <= k <= count:
+                raise ValueError(f"{name!r}: {prefix}1..{prefix}{count} exist for {N} dots")
+            return base + k - 1
+    if name.startswith(other) and name[len(other):].isdigit():
+        raise ValueError(f"{name!r} is a plunger of the {'physical' if frame == 'virtual' else 'virtual'} frame; "
+                         f"the {frame} frame names its plungers {plunger}1..{plunger}{N}")
+    raise ValueError(f"unknown control {name!r}: expected {plunger}1..{plunger}{N}, S or B1..B{N - 1}")
+
+
+def scan_control_indices(x, N, frame, nq):
+    """(nq,) int32 control indices from one index / name for all queries or a sequence of nq of them."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    if isinstance(x, (str, int, np.integer)):
+        return np.full(nq, scan_control_index(x, N, frame), np.int32)
+    idx = np.array([scan_control_index(v, N, frame) for v in list(x)], np.int32)
+    if idx.shape != (nq,):
+        raise ValueError(f"{len(idx)} controls for {nq} queries")
+    return idx
+
+
 class VecQuantumDeviceEnv:
     def __init__(self, num_envs, num_dots=None, config_path=None, qarray_config_path=None,
                  resolution=None, device=None, seed=None, env_id_offset=0, capacitance_model=None,
@@ -359,6 +398,81 @@ class VecQuantumDeviceEnv:
                                         plohi.data_ptr(), self._stream())
         _lib.check(self._h, rc, "qd_probe_compose")
         return comp, plohi
+
+    # ------------------------------------------------------------------ axis scans
+    def scan2d(self, env_ids, x, y, x_range, y_range, gate_voltages, barrier_voltages, sensor_voltage=None,
+               frame="virtual", vgm=None, gamma=None, normalised=False, occupations=False, noise=None, serial=None,
+               stream_base=None):
+        """Stateless 2-D scans over any two controls (qd_scan2d): the reference model layer's `do2d_open(x_gate, x_min,
+        x_max, ..., y_gate, ...)` / `GateVoltageComposer.do2d(..., gate_voltages, add_full_crosstalk=True)` for nq queries in
+        one call, each on the device of env `env_ids[q]`.  Nothing of the episodes changes.
+          env_ids           (nq,) ints, or one id for all queries
+          x, y              the swept controls, one for all queries or (nq,): indices in the order of the model's voltage
+                            vector (0..N-1 plungers, N the sensor gate, N+1..2N-1 barriers) or names, 1-indexed as the
+                            composer's: "vP1".."vPN" ("P1".."PN" in the physical frame), "S", "B1".."B{N-1}".  x runs along
+                            columns, y along rows
+          x_range, y_range  (lo, hi) for all queries or (nq, 2); lo > hi sweeps downwards, lo == hi repeats a 1-D sweep
+          gate_voltages     (nq, N), barrier_voltages (nq, N-1), sensor_voltage None (0.0) / scalar / (nq,): the controls
+                            that are not swept
+          frame             "virtual": the gates go through the virtual gate matrix (the env's current one, or `vgm`
+                            (nq, N+1, N+1)) and origin; "physical": voltages as the model takes them, as eval_points
+          gamma             None, a scalar or (nq,) peak widths.  None: with two virtual plungers as axes the rule of a
+                            step (vary_peak_width) on those plungers' base voltages, else the env's constant
+          noise             None / False: deterministic.  True: the sensor and latching stages this env was created with.
+                            Or an iterable of {"sensor", "latch"}; the radial stage is not defined for axis scans
+          serial, stream_base   as in probe()
+        Returns device tensors {"raw": (nq, R, R) float64}, plus, with normalised=True, {"image": (nq, R, R) float32
+        normalised per query, "plohi": (nq, 2)}, plus, with occupations=True, {"occupations": (nq, R, R, N) float64}."""
+        N, C, R = self.N, self.C, self.R
+        if frame not in ("virtual", "physical"):
+            raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
+        if vgm is not None and frame == "physical":
+            raise ValueError("vgm has no meaning in the physical frame")
+        gv = gate_voltages if isinstance(gate_voltages, torch.Tensor) else np.asarray(gate_voltages, np.float64)
+        gv = gv.reshape(-1, N)
+        nq = int(gv.shape[0])
+        axes = np.stack([scan_control_indices(x, N, frame, nq), scan_control_indices(y, N, frame, nq)], axis=1)
+        if np.any(axes[:, 0] == axes[:, 1]):
+            raise ValueError("x and y must be two different controls")
+        rng = np.concatenate([np.broadcast_to(np.asarray(x_range, np.float64), (nq, 2)),
+                              np.broadcast_to(np.asarray(y_range, np.float64), (nq, 2))], axis=1)
+        if noise is True:
+            flags = self.noise_flags & ~_lib.QD_NOISE_RADIAL
+        else:
+            if noise and "radial" in tuple(noise):
+                raise ValueError("radial noise is centred on the env's own adjacent-pair observation: not defined for axis scans")
+            flags = self._noise_flags(noise)
+        gv = self._to_dev(gv, torch.float64, (nq, N))
+        bv = barrier_voltages if isinstance(barrier_voltages, torch.Tensor) else np.asarray(barrier_voltages, np.float64)
+        bv = self._to_dev(bv.reshape(-1, C), torch.float64, (nq, C))
+        ids = env_ids if isinstance(env_ids, torch.Tensor) else np.asarray(env_ids, np.int32)
+        ids = self._to_dev(ids.reshape(-1), torch.int32, (nq,))
+        ax = self._to_dev(axes.astype(np.int32), torch.int32, (nq, 2))
+        rg = self._to_dev(rng, torch.float64, (nq, 4))
+        sv = None if sensor_voltage is None else self._to_dev(sensor_voltage, torch.float64, (nq,))
+        vm = None if vgm is None else self._to_dev(vgm, torch.float64, (nq, N + 1, N + 1))
+        gm = None if gamma is None else self._to_dev(gamma, torch.float64, (nq,))
+        out = {"raw": torch.empty((nq, R, R), dtype=torch.float64, device=self.device)}
+        if normalised:
+            out["image"] = torch.empty((nq, R, R), dtype=torch.float32, device=self.device)
+            out["plohi"] = torch.empty((nq, 2), dtype=torch.float64, device=self.device)
+        if occupations:
+            out["occupations"] = torch.empty((nq, R, R, N), dtype=torch.float64, device=self.device)
+        if serial is None:
+            serial = (1 << 63) | self._probe_serials
+            if flags:
+                self._probe_serials += 1
+        addr = lambda t: None if t is None else t.data_ptr()                    # noqa: E731
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())    # noqa: E731
+        opts = _lib.QdScanOpts(struct_size=ctypes.sizeof(_lib.QdScanOpts),
+                               frame=_lib.QD_SCAN_PHYSICAL if frame == "physical" else _lib.QD_SCAN_VIRTUAL,
+                               noise_flags=int(flags), reserved=0, serial=int(serial) & 0xFFFFFFFFFFFFFFFF,
+                               stream_base=int(self.env_id_offset if stream_base is None else stream_base),
+                               vgm_dev=addr(vm), gamma_dev=addr(gm), occ_dst=addr(out.get("occupations")))
+        rc = self._lib.qd_scan2d(self._h, ptr(ids), nq, ptr(ax), ptr(rg), ptr(gv), ptr(bv), ptr(sv), ptr(out["raw"]),
+                                 ptr(out.get("image")), ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
+        _lib.check(self._h, rc, "qd_scan2d")
+        return out
 
     # ------------------------------------------------------------------ point evaluation
     def eval_points(self, env_ids, vg, vb, gamma=None, outputs=("signal", "occupations")):
