@@ -70,9 +70,13 @@ struct QdStageRing {
 
 // The per-env device buffers the hot launchers work on, handed to them as an argument: qd_env_bufs() is the view of the
 // handle's own envs, a QdScratchSet gives one of its blocks starting from a zeroed object, so whatever a probe does not
-// set reaches the kernels as nullptr / 0 and never as the envs' pointer.
+// set reaches the kernels as nullptr / 0 and never as the envs' pointer.  The view also says what shape its blocks have,
+// and every launcher reads grid, front end and channel template argument from there.
+enum QdFront { QD_FRONT_ENV, QD_FRONT_SCAN };   // who fills the records: QdFrontEnv / QdFrontScan (qd_pixel.h)
 struct QdEnvBufs {
     double *params, *state, *zraw, *plohi, *occ, *eig;
+    int channels;                           // channel images per block: h->C, or 1 on the buffers of qd_scan2d
+    QdFront front;
     int noise_flags;
     unsigned long long* tel; int tel_words;
     unsigned long long serial;              // number of the observation being rendered (Philox counter word)
@@ -97,9 +101,10 @@ struct QdScratchSet {
         return e;
     }
     // without noise, eigenvalues or telegraph words
-    QdEnvBufs view() const {
+    QdEnvBufs view(int channels, QdFront front = QD_FRONT_ENV) const {
         QdEnvBufs b{};
         b.params = params.p; b.state = state.p; b.zraw = z.p; b.plohi = plohi.p; b.occ = occ.p;
+        b.channels = channels; b.front = front;
         return b;
     }
 };
@@ -149,6 +154,7 @@ static bool qd_validate(const qd_handle* h) { return (h->cfg.flags & QD_FLAG_VAL
 static QdEnvBufs qd_env_bufs(const qd_handle* h) {
     QdEnvBufs b{};
     b.params = h->params.p; b.state = h->state.p; b.zraw = h->zraw.p; b.plohi = h->plohi.p; b.occ = h->occ.p; b.eig = h->eig.p;
+    b.channels = h->C; b.front = QD_FRONT_ENV;
     b.noise_flags = h->cfg.noise_flags;
     b.tel = h->tel.p; b.tel_words = h->tel_words;
     b.serial = h->obs_serial;
@@ -210,6 +216,10 @@ struct QdEventPair {
 // a boolean template argument: NAME_ is a constexpr bool inside the statement
 #define QD_DISPATCH_BOOL(COND_, NAME_, ...)                                       \
     { if (COND_) { constexpr bool NAME_ = true; __VA_ARGS__; } else { constexpr bool NAME_ = false; __VA_ARGS__; } }
+
+// the front end of a buffer view's records: FE is the search kernels' policy type inside the statement
+#define QD_DISPATCH_FRONT(FRONT_, ...)                                            \
+    { if ((FRONT_) == QD_FRONT_SCAN) { using FE = QdFrontScan; __VA_ARGS__; } else { using FE = QdFrontEnv; __VA_ARGS__; } }
 
 extern "C" int qd_param_block_doubles(int n) { return (n < 2 || n > QD_MAXN) ? -1 : qd_layout(n).size; }
 extern "C" int qd_state_block_doubles(int n) { return (n < 2 || n > QD_MAXN) ? -1 : qd_layout(n).s_size; }
@@ -514,10 +524,9 @@ static hipError_t qd_launch_solve(const qd_handle* h, const QdLane& ln, hipStrea
 
 // a11-a13 + a15 for the envs at list positions [base, base + cnt): structure -> solve per size class -> select (those of
 // them in `st`), in launches of at most gs_chunk envs (the slabs in flight)
-// C: channel images per env block (h->C, or 1 on the buffers of qd_scan2d)
 static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, const int32_t* env_ids, int base, int cnt,
-                            hipStream_t s, int st, int C) {
-    const int nb = (h->P + h->ppb - 1) / h->ppb;
+                            hipStream_t s, int st) {
+    const int nb = (h->P + h->ppb - 1) / h->ppb, C = b.channels;
     unsigned* tilelist = ln.gtiles.p + 16;
     const bool val = qd_validate(h);
     QdWide wide = h->wide; wide.buf = ln.wide.p;
@@ -621,57 +630,47 @@ static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane
         default: return qd_fail(h, QD_ERR_ARG, "tile kernels need n_dot in 4..8");      \
     }
 
+// validate mode keeps the records' kept states in the reference order; K < KC needs it too, the ground-state stage takes the first K
+static int qd_sorted_records(const qd_handle* h) { return (qd_validate(h) || h->kept != h->kc) ? 1 : 0; }
+
+// a5/a8-a10 by the per-pixel search on `cnt` blocks of `b`.  tiled: the exact redo pass, only on the pixels whose record
+// asks for it (behind the tile search, or behind a front end that filled the records itself); else every pixel.
+// (in both search kernels noise_flags reaches qd_radial_replaced alone, false without the radial bit, which qd_scan2d refuses)
+static int qd_launch_candidates(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, const int32_t* env_ids, int base, int cnt,
+                                hipStream_t s, bool tiled) {
+    const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
+    const dim3 grid(qd_cand_blocks(h->R), b.channels, cnt);
+    QD_DISPATCH_FRONT(b.front, QD_DISPATCH_BOOL(tiled, TILED, QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
+        qd_k_candidates<NN, TILED, KK, FE><<<grid, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R, b.params, b.state, ln.recs.p,
+                                                                                  qd_sorted_records(h), b.noise_flags)))));
+    QD_HIP(hipGetLastError());
+    return QD_OK;
+}
+
 // a5-a13 for `cnt` envs starting at list position `base`: those of the stages in `st` that the handle has (qd_stages) --
-// tile search + exact redo pass or the per-pixel search alone, then the ground-state kernels.
-// scan (qd_scan2d): slot k renders ONE image over the axes in its state block copy instead of the env's C channel images.
+// tile search + exact redo pass or the per-pixel search alone, then the ground-state kernels.  On the blocks of a scan
+// (b.front) slot k renders ONE image over the axes in its state block copy instead of the env's C channel images.
 static int qd_launch_csd(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, const int32_t* env_ids, int base, int cnt,
-                         hipStream_t s, int st, bool scan = false) {
+                         hipStream_t s, int st) {
     st &= qd_stages(h);
-    // validate mode keeps the reference order; K < KC needs it too, the ground-state stage takes the first K
-    const int sorted = (qd_validate(h) || h->kept != h->kc) ? 1 : 0;
-    const int C = scan ? 1 : h->C;
-    if (scan) {
-        if (st & QD_ST_TILE) {
-            const int tiles = ((h->R + 7) / 8) * ((h->R + 7) / 8);
-            QD_DISPATCH_TILE(h->N, QD_DISPATCH_KC(h->kc, qd_k_tile<NN, KK, QdFrontScan><<<dim3(tiles, 1, cnt), dim3(64), 0, s>>>(env_ids,
-                             base, h->R, b.params, b.state, ln.recs.p, sorted, 0, h->tstats.p)));
-            QD_HIP(hipGetLastError());
-        }
-        if (st & QD_ST_REDO) {
-            const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
-            const dim3 g1(qd_cand_blocks(h->R), 1, cnt);
-            QD_DISPATCH_BOOL(h->tile_search != 0, TILED, QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
-                qd_k_candidates<NN, TILED, KK, QdFrontScan><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R, b.params, b.state,
-                                                                                                 ln.recs.p, sorted, 0))));
-            QD_HIP(hipGetLastError());
-        }
-        if (st & QD_ST_GROUND) return qd_launch_ground(h, b, ln, env_ids, base, cnt, s, st, C);
-        return QD_OK;
-    }
     if (st & QD_ST_TILE) {
         const int tiles = ((h->R + 7) / 8) * ((h->R + 7) / 8);
-        QD_DISPATCH_TILE(h->N, QD_DISPATCH_KC(h->kc, qd_k_tile<NN, KK><<<dim3(tiles, h->C, cnt), dim3(64), 0, s>>>(env_ids, base, h->R,
-                         b.params, b.state, ln.recs.p, sorted, b.noise_flags, h->tstats.p)));
+        QD_DISPATCH_FRONT(b.front, QD_DISPATCH_TILE(h->N, QD_DISPATCH_KC(h->kc,
+            qd_k_tile<NN, KK, FE><<<dim3(tiles, b.channels, cnt), dim3(64), 0, s>>>(env_ids, base, h->R, b.params, b.state, ln.recs.p,
+                                                                                    qd_sorted_records(h), b.noise_flags, h->tstats.p))));
         QD_HIP(hipGetLastError());
     }
-    if (st & QD_ST_REDO) {
-        const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
-        const dim3 g1(qd_cand_blocks(h->R), h->C, cnt);
-        QD_DISPATCH_BOOL(h->tile_search != 0, TILED, QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
-            qd_k_candidates<NN, TILED, KK><<<g1, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R, b.params, b.state, ln.recs.p, sorted,
-                                                                              b.noise_flags))));
-        QD_HIP(hipGetLastError());
-    }
-    if (st & QD_ST_GROUND) return qd_launch_ground(h, b, ln, env_ids, base, cnt, s, st, C);
+    if (st & QD_ST_REDO)
+        if (int rc = qd_launch_candidates(h, b, ln, env_ids, base, cnt, s, h->tile_search != 0)) return rc;
+    if (st & QD_ST_GROUND) return qd_launch_ground(h, b, ln, env_ids, base, cnt, s, st);
     return QD_OK;
 }
 
 // a16 on the signal of `n` envs (their list `ids`, or 0..n-1), in place
-// (one_channel: the buffers of qd_scan2d, one image per block)
-static int qd_launch_sensor(const qd_handle* h, const QdEnvBufs& b, const int32_t* ids, int n, hipStream_t s, bool one_channel = false) {
-    const dim3 g3((h->P + 255) / 256, one_channel ? 1 : h->C, n);
-    if (one_channel) { QD_DISPATCH_N(h->N, qd_k_sensor<NN, 1><<<g3, dim3(256), 0, s>>>(ids, h->R, b.params, b.state, b.zraw, qd_noise_cfg(h, b))); }
-    else { QD_DISPATCH_N(h->N, qd_k_sensor<NN><<<g3, dim3(256), 0, s>>>(ids, h->R, b.params, b.state, b.zraw, qd_noise_cfg(h, b))); }
+static int qd_launch_sensor(const qd_handle* h, const QdEnvBufs& b, const int32_t* ids, int n, hipStream_t s) {
+    const dim3 g3((h->P + 255) / 256, b.channels, n);
+    QD_DISPATCH_BOOL(b.channels == 1, ONE, QD_DISPATCH_N(h->N,
+        qd_k_sensor<NN, (ONE ? 1 : NN - 1)><<<g3, dim3(256), 0, s>>>(ids, h->R, b.params, b.state, b.zraw, qd_noise_cfg(h, b))));
     QD_HIP(hipGetLastError());
     return QD_OK;
 }
@@ -792,6 +791,67 @@ extern "C" int qd_snapshot(qd_handle* h, const int32_t* env_ids, int n, float* g
     return QD_OK;
 }
 
+// The option values qd_probe_opts and qd_scan_opts share.
+struct QdQueryOpts {
+    int noise_flags; unsigned long long serial; long long stream_base;
+    bool occ;                               // the caller takes the occupations
+};
+
+// The stateless queries (qd_probe_ex, qd_scan2d): `nq` of them in launch chunks of h->chunk slots on the blocks of `set`,
+// each slot `channels` images filled by `front`.  Per chunk: gather(base, cnt, bufs) copies the envs' blocks into the slots
+// and applies the queries; then the stages of an observation in qd_observe's order -- telegraph words, search and ground
+// state, latching, sensor, percentiles -- on the slots alone, without eigenvalues; occupations, telegraph words and noise
+// only as asked for, keyed by the caller's serial and stream base; write(base, cnt, bufs) hands the results out.  Both
+// only launch, the runner checks.  Nothing of the envs is written.
+template <class Gather, class Write>
+static int qd_run_queries(qd_handle* h, QdScratchSet& set, int channels, QdFront front, const QdQueryOpts& o, int nq, hipStream_t s,
+                          Gather gather, Write write) {
+    const bool want_occ = (o.noise_flags & QD_NOISE_LATCH) || o.occ, want_tel = (o.noise_flags & QD_NOISE_SENSOR) != 0;
+    const int pc = h->chunk;                                  // queries in flight = envs per launch chunk (lane 0's scratch)
+    const size_t CP = (size_t)channels * h->P;
+    QD_HIP(set.reserve(h->L, CP, (size_t)pc, 2, want_occ ? CP * h->N : 0, want_tel ? (size_t)channels * h->tel_words : 0));
+    QdEnvBufs b = set.view(channels, front);
+    b.occ = want_occ ? set.occ.p : nullptr;
+    b.noise_flags = o.noise_flags;
+    if (want_tel) { b.tel = set.tel.p; b.tel_words = h->tel_words; }
+    b.serial = o.serial;
+    for (int base = 0; base < nq; base += pc) {
+        const int cnt = nq - base < pc ? nq - base : pc;
+        b.env_off = (uint32_t)(o.stream_base + base);        // slot k of the chunk draws as global env stream_base + base + k
+        gather(base, cnt, b);
+        QD_HIP(hipGetLastError());
+        if (want_tel) {
+            const int nt = cnt * channels;
+            qd_k_telegraph<<<dim3((nt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, channels, h->P, h->L.size, h->L.noise, b.params, b.tel,
+                                                                     qd_noise_cfg(h, b));
+            QD_HIP(hipGetLastError());
+        }
+        if (int rc = qd_launch_csd(h, b, h->lanes[0], nullptr, 0, cnt, s, QD_ST_ALL)) return rc;
+        if (o.noise_flags & QD_NOISE_LATCH) {
+#ifdef QD_PROBE_SERIAL_LATCH        // (measurement only, DESIGN.md 7: probes take the one-thread walk of qd_observe on their buffers)
+            if (front == QD_FRONT_ENV) {
+                QD_DISPATCH_N(h->N, qd_k_latch<NN><<<dim3((cnt * channels + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, h->R, b.params, b.state,
+                                                                                                       b.occ, b.zraw, qd_noise_cfg(h, b)));
+            } else
+#endif
+            {
+                const long rows = (long)cnt * channels * h->R;
+                const dim3 grid((unsigned)((rows + QD_LATCH_ROWS_BLOCK - 1) / QD_LATCH_ROWS_BLOCK));
+                QD_DISPATCH_BOOL(channels == 1, ONE, QD_DISPATCH_N(h->N,
+                    qd_k_latch_rows<NN, (ONE ? 1 : NN - 1)><<<grid, dim3(QD_LATCH_ROWS_BLOCK), 0, s>>>(cnt, h->R, b.params, b.state, b.occ,
+                                                                                                       b.zraw, qd_noise_cfg(h, b))));
+            }
+            QD_HIP(hipGetLastError());
+        }
+        if (int rc = qd_launch_sensor(h, b, nullptr, cnt, s)) return rc;
+        qd_launch_percentile(nullptr, (unsigned)cnt, (long)channels * h->P, b.zraw, b.plohi, s);
+        QD_HIP(hipGetLastError());
+        write(base, cnt, b);
+        QD_HIP(hipGetLastError());
+    }
+    return QD_OK;
+}
+
 extern "C" int qd_probe_ex(qd_handle* h, const int32_t* env_of_query, int nq, const double* gate_v, const double* barrier_v,
                            const double* sensor_v, const double* window, double* raw_dst, float* image_dst, double* plohi_dst,
                            const qd_probe_opts* opts, void* stream) {
@@ -809,59 +869,21 @@ extern "C" int qd_probe_ex(qd_handle* h, const int32_t* env_of_query, int nq, co
     if (nq == 0) return QD_OK;
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
-    const int flags = opts ? opts->noise_flags : 0;
+    const QdQueryOpts o = opts ? QdQueryOpts{opts->noise_flags, opts->serial, opts->stream_base, opts->occ_dst != nullptr} : QdQueryOpts{};
     double* const occ_dst = opts ? opts->occ_dst : nullptr;
-    const bool want_occ = (flags & QD_NOISE_LATCH) || occ_dst, want_tel = (flags & QD_NOISE_SENSOR) != 0;
-    const int pc = h->chunk;                                  // queries in flight = envs per launch chunk (lane 0's scratch)
-    const size_t CP = (size_t)h->C * h->P;
-    QD_HIP(h->probe.reserve(h->L, CP, (size_t)pc, 2, want_occ ? CP * h->N : 0, want_tel ? (size_t)h->C * h->tel_words : 0));
-    // the hot launchers run on the probe blocks, without eigenvalues; occupations, telegraph words and noise only as asked
-    // for, keyed by the caller's serial and stream base; nothing of the envs is written
-    QdEnvBufs pb = h->probe.view();
-    pb.occ = want_occ ? h->probe.occ.p : nullptr;
-    pb.noise_flags = flags;
-    if (want_tel) { pb.tel = h->probe.tel.p; pb.tel_words = h->tel_words; }
-    pb.serial = opts ? opts->serial : 0;
     const QdProbeQuery Q{env_of_query, gate_v, barrier_v, sensor_v, window};
-    for (int base = 0; base < nq; base += pc) {
-        const int cnt = nq - base < pc ? nq - base : pc;
-        pb.env_off = (uint32_t)((opts ? opts->stream_base : 0) + base);      // slot k of the chunk draws as global env stream_base + base + k
-        qd_k_probe_gather<<<dim3(cnt), dim3(QD_PROBE_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, pb.params, pb.state);
-        QD_HIP(hipGetLastError());
-        if (want_tel) {
-            const int nt = cnt * h->C;
-            qd_k_telegraph<<<dim3((nt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, h->C, h->P, h->L.size, h->L.noise, pb.params, pb.tel,
-                                                                     qd_noise_cfg(h, pb));
-            QD_HIP(hipGetLastError());
-        }
-        if (int rc = qd_launch_csd(h, pb, h->lanes[0], nullptr, 0, cnt, s, QD_ST_ALL)) return rc;
-        if (flags & QD_NOISE_LATCH) {
-#ifdef QD_PROBE_SERIAL_LATCH        // (measurement only, DESIGN.md 7: the one-thread walk of qd_observe on the probe buffers)
-            QD_DISPATCH_N(h->N, qd_k_latch<NN><<<dim3((cnt * h->C + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, h->R, pb.params, pb.state,
-                                                                                               pb.occ, pb.zraw, qd_noise_cfg(h, pb)));
-#else
-            const long rows = (long)cnt * h->C * h->R;
-            QD_DISPATCH_N(h->N, qd_k_latch_rows<NN><<<dim3((unsigned)((rows + QD_LATCH_ROWS_BLOCK - 1) / QD_LATCH_ROWS_BLOCK)),
-                                                      dim3(QD_LATCH_ROWS_BLOCK), 0, s>>>(cnt, h->R, pb.params, pb.state, pb.occ, pb.zraw,
-                                                                                         qd_noise_cfg(h, pb)));
-#endif
-            QD_HIP(hipGetLastError());
-        }
-        if (int rc = qd_launch_sensor(h, pb, nullptr, cnt, s)) return rc;
-        qd_launch_percentile(nullptr, (unsigned)cnt, (long)h->C * h->P, pb.zraw, pb.plohi, s);
-        QD_HIP(hipGetLastError());
-        if (raw_dst || image_dst || plohi_dst) {
-            qd_k_probe_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(env_of_query, base, h->B, h->C, h->P, pb.zraw, pb.plohi,
-                                                                                 raw_dst, image_dst, plohi_dst);
-            QD_HIP(hipGetLastError());
-        }
-        if (occ_dst) {
-            qd_k_probe_write_occ<<<dim3((h->P * h->N + 255) / 256, h->C, cnt), dim3(256), 0, s>>>(env_of_query, base, h->B, h->N, h->P,
-                                                                                                  pb.params, pb.state, flags, pb.occ, occ_dst);
-            QD_HIP(hipGetLastError());
-        }
-    }
-    return QD_OK;
+    return qd_run_queries(h, h->probe, h->C, QD_FRONT_ENV, o, nq, s,
+        [&](int base, int cnt, const QdEnvBufs& pb) {
+            qd_k_probe_gather<<<dim3(cnt), dim3(QD_PROBE_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, pb.params, pb.state);
+        },
+        [&](int base, int cnt, const QdEnvBufs& pb) {
+            if (raw_dst || image_dst || plohi_dst)
+                qd_k_probe_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(env_of_query, base, h->B, h->C, h->P, pb.zraw, pb.plohi,
+                                                                                     raw_dst, image_dst, plohi_dst);
+            if (occ_dst)
+                qd_k_probe_write_occ<<<dim3((h->P * h->N + 255) / 256, h->C, cnt), dim3(256), 0, s>>>(env_of_query, base, h->B, h->N, h->P,
+                                                                                                      pb.params, pb.state, o.noise_flags, pb.occ, occ_dst);
+        });
 }
 
 extern "C" int qd_probe(qd_handle* h, const int32_t* env_of_query, int nq, const double* gate_v, const double* barrier_v,
@@ -895,49 +917,20 @@ extern "C" int qd_scan2d(qd_handle* h, const int32_t* env_of_query, int nq, cons
     if (nq == 0) return QD_OK;
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
-    const int flags = opts ? opts->noise_flags : 0;
+    const QdQueryOpts o = opts ? QdQueryOpts{opts->noise_flags, opts->serial, opts->stream_base, opts->occ_dst != nullptr} : QdQueryOpts{};
     double* const occ_dst = opts ? opts->occ_dst : nullptr;
-    const bool want_occ = (flags & QD_NOISE_LATCH) || occ_dst, want_tel = (flags & QD_NOISE_SENSOR) != 0;
-    const int pc = h->chunk;                                  // queries in flight = envs per launch chunk (lane 0's scratch)
-    const size_t P = (size_t)h->P;
-    QD_HIP(h->scan.reserve(h->L, P, (size_t)pc, 2, want_occ ? P * h->N : 0, want_tel ? (size_t)h->tel_words : 0));
-    // the hot launchers run on the scan blocks with ONE channel image per slot, without eigenvalues; occupations, telegraph
-    // words and noise only as asked for, keyed by the caller's serial and stream base; nothing of the envs is written
-    QdEnvBufs sb = h->scan.view();
-    sb.occ = want_occ ? h->scan.occ.p : nullptr;
-    sb.noise_flags = flags;
-    if (want_tel) { sb.tel = h->scan.tel.p; sb.tel_words = h->tel_words; }
-    sb.serial = opts ? opts->serial : 0;
     const QdScanQuery Q{env_of_query, axes, range, gate_v, barrier_v, sensor_v, opts ? opts->vgm_dev : nullptr,
                         opts ? opts->gamma_dev : nullptr, opts ? opts->frame : QD_SCAN_VIRTUAL};
-    for (int base = 0; base < nq; base += pc) {
-        const int cnt = nq - base < pc ? nq - base : pc;
-        sb.env_off = (uint32_t)((opts ? opts->stream_base : 0) + base);      // slot k of the chunk draws as global env stream_base + base + k
-        qd_k_scan_gather<<<dim3(cnt), dim3(QD_SCAN_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, sb.params, sb.state);
-        QD_HIP(hipGetLastError());
-        if (want_tel) {
-            qd_k_telegraph<<<dim3((cnt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, 1, h->P, h->L.size, h->L.noise, sb.params, sb.tel,
-                                                                      qd_noise_cfg(h, sb));
-            QD_HIP(hipGetLastError());
-        }
-        if (int rc = qd_launch_csd(h, sb, h->lanes[0], nullptr, 0, cnt, s, QD_ST_ALL, true)) return rc;
-        if (flags & QD_NOISE_LATCH) {
-            const long rows = (long)cnt * h->R;
-            QD_DISPATCH_N(h->N, qd_k_latch_rows<NN, 1><<<dim3((unsigned)((rows + QD_LATCH_ROWS_BLOCK - 1) / QD_LATCH_ROWS_BLOCK)),
-                                                         dim3(QD_LATCH_ROWS_BLOCK), 0, s>>>(cnt, h->R, sb.params, sb.state, sb.occ, sb.zraw,
-                                                                                            qd_noise_cfg(h, sb)));
-            QD_HIP(hipGetLastError());
-        }
-        if (int rc = qd_launch_sensor(h, sb, nullptr, cnt, s, true)) return rc;
-        qd_launch_percentile(nullptr, (unsigned)cnt, (long)h->P, sb.zraw, sb.plohi, s);
-        QD_HIP(hipGetLastError());
-        if (raw_dst || image_dst || plohi_dst || occ_dst) {
-            qd_k_scan_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, h->P, sb.zraw, sb.plohi, sb.occ,
-                                                                                raw_dst, image_dst, plohi_dst, occ_dst);
-            QD_HIP(hipGetLastError());
-        }
-    }
-    return QD_OK;
+    // ONE channel image per slot, over the axes that the gather kernel leaves in the slot's state block copy
+    return qd_run_queries(h, h->scan, 1, QD_FRONT_SCAN, o, nq, s,
+        [&](int base, int cnt, const QdEnvBufs& sb) {
+            qd_k_scan_gather<<<dim3(cnt), dim3(QD_SCAN_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, sb.params, sb.state);
+        },
+        [&](int base, int cnt, const QdEnvBufs& sb) {
+            if (raw_dst || image_dst || plohi_dst || occ_dst)
+                qd_k_scan_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, h->P, sb.zraw, sb.plohi, sb.occ,
+                                                                                    raw_dst, image_dst, plohi_dst, occ_dst);
+        });
 }
 
 // slots in flight of qd_eval_points: one launch chunk of lane 0's records, at most QD_POINTS_SLOTS
@@ -968,9 +961,8 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
     const long long CP = (long long)h->C * h->P;
     QD_HIP(h->points.reserve(h->L, (size_t)CP, (size_t)ps, 0, (size_t)CP * h->N));
     // the ground-state launcher runs on the point buffers, without noise or eigenvalues; nothing of the envs is written
-    const QdEnvBufs qb = h->points.view();
+    const QdEnvBufs qb = h->points.view(h->C);
     const QdLane& ln = h->lanes[0];
-    const int sorted = h->kept != h->kc ? 1 : 0;              // as qd_launch_csd: K < KC takes the first K of the ordered list
     QdPointSlots T;
     memset(&T, 0, sizeof(T));
     T.own_gamma = gamma ? 0 : 1;
@@ -983,19 +975,15 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
         QD_HIP(hipGetLastError());
         QD_DISPATCH_N(h->N, qd_k_points_front<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, vg, vb, qb.params, ln.recs.p));
         QD_HIP(hipGetLastError());
-        // (launched directly: qd_launch_csd would pick the non-redo instantiation on handles without a tile search and
-        // overwrite the front end)
-        const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
-        QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
-            qd_k_candidates<NN, true, KK><<<dim3(qd_cand_blocks(h->R), h->C, n), dim3(QD_CAND_BLOCK), shm, s>>>(nullptr, 0, h->R,
-                qb.params, qb.state, ln.recs.p, sorted, 0)));
-        QD_HIP(hipGetLastError());
+        // (the redo instantiation, and not through qd_launch_csd: on handles without a tile search that would pick the
+        // whole per-pixel search and overwrite the front end)
+        if (int rc = qd_launch_candidates(h, qb, ln, nullptr, 0, n, s, true)) return rc;
         // The signal comes from the list as the search left it, which is what qd_observe and qd_probe solve: the probe's bits.
         // The occupations come from the list in the reference order, which is what a validate handle solves and
         // qd_get_occupations returns: with K == KC (search order) the records are sorted and the ground-state stage runs again.
-        const bool resort = !sorted && occ_dst;
+        const bool resort = !qd_sorted_records(h) && occ_dst;
         if (signal_dst || !resort) {
-            if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND, h->C)) return rc;
+            if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND)) return rc;
             if (signal_dst || occ_dst) {
                 QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, qb.params, qb.zraw, qb.occ,
                                                                                                signal_dst, resort ? nullptr : occ_dst));
@@ -1006,7 +994,7 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
             const long nrec = (long)n * CP;
             QD_DISPATCH_KC(h->kc, qd_k_points_sort<KK><<<dim3((unsigned)((nrec + 63) / 64)), dim3(64), 0, s>>>(ln.recs.p, nrec));
             QD_HIP(hipGetLastError());
-            if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND, h->C)) return rc;
+            if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND)) return rc;
             QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, qb.params, qb.zraw, qb.occ,
                                                                                            nullptr, occ_dst));
             QD_HIP(hipGetLastError());

@@ -145,6 +145,11 @@ def scan_control_indices(x, N, frame, nq):
     return idx
 
 
+def _ptr(t):
+    """A device tensor's address as a pointer argument; None stays NULL."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
 class VecQuantumDeviceEnv:
     def __init__(self, num_envs, num_dots=None, config_path=None, qarray_config_path=None,
                  resolution=None, device=None, seed=None, env_id_offset=0, capacitance_model=None,
@@ -324,6 +329,36 @@ class VecQuantumDeviceEnv:
             t = torch.from_numpy(a.reshape(-1)).pin_memory().to(self.device, non_blocking=True).reshape(a.shape)
         return t.broadcast_to(shape).contiguous()
 
+    def _query_inputs(self, env_ids, gate_voltages, barrier_voltages, sensor_voltage):
+        """What probe() and scan2d() take per query, on the device: (nq, env ids, gate, barrier, sensor voltages or None)."""
+        def arr(x, dtype):
+            return x if isinstance(x, torch.Tensor) else np.asarray(x, dtype)
+        N, C = self.N, self.C
+        gv = arr(gate_voltages, np.float64).reshape(-1, N)
+        nq = int(gv.shape[0])
+        return (nq, self._to_dev(arr(env_ids, np.int32).reshape(-1), torch.int32, (nq,)), self._to_dev(gv, torch.float64, (nq, N)),
+                self._to_dev(arr(barrier_voltages, np.float64).reshape(-1, C), torch.float64, (nq, C)),
+                None if sensor_voltage is None else self._to_dev(sensor_voltage, torch.float64, (nq,)))
+
+    def _query_outputs(self, nq, channels, normalised, occupations):
+        """The result tensors of nq queries of `channels` = (C,) or () channel images each."""
+        R, f64 = self.R, {"dtype": torch.float64, "device": self.device}
+        out = {"raw": torch.empty((nq, *channels, R, R), **f64)}
+        if normalised:
+            out["image"] = torch.empty((nq, R, R, *channels), dtype=torch.float32, device=self.device)
+            out["plohi"] = torch.empty((nq, 2), **f64)
+        if occupations:
+            out["occupations"] = torch.empty((nq, *channels, R, R, self.N), **f64)
+        return out
+
+    def _query_serial(self, serial, flags):
+        """The serial word of a probe or scan: the caller's, or (1 << 63) | k, k counting this object's noisy queries."""
+        if serial is None:
+            serial = (1 << 63) | self._probe_serials
+            if flags:
+                self._probe_serials += 1
+        return int(serial) & 0xFFFFFFFFFFFFFFFF
+
     def probe(self, env_ids, gate_voltages, barrier_voltages, sensor_voltage=None, window=None, normalised=False,
               noise=None, serial=None, stream_base=None, occupations=False):
         """Stateless scans (qd_probe / qd_probe_ex): the reference's `array._get_obs(gate_voltages, barrier_voltages,
@@ -345,40 +380,21 @@ class VecQuantumDeviceEnv:
         normalised=True, {"image": (nq, R, R, C) float32 normalised per query, "plohi": (nq, 2) its percentiles}, plus,
         with occupations=True, {"occupations": (nq, C, R, R, N) float64; NaN in a channel the radial stage replaced by
         white noise}."""
-        N, C, R = self.N, self.C, self.R
-        gv = gate_voltages if isinstance(gate_voltages, torch.Tensor) else np.asarray(gate_voltages, np.float64)
-        gv = gv.reshape(-1, N)
-        nq = int(gv.shape[0])
-        gv = self._to_dev(gv, torch.float64, (nq, N))
-        bv = barrier_voltages if isinstance(barrier_voltages, torch.Tensor) else np.asarray(barrier_voltages, np.float64)
-        bv = self._to_dev(bv.reshape(-1, C), torch.float64, (nq, C))
-        ids = env_ids if isinstance(env_ids, torch.Tensor) else np.asarray(env_ids, np.int32)
-        ids = self._to_dev(ids.reshape(-1), torch.int32, (nq,))
-        sv = None if sensor_voltage is None else self._to_dev(sensor_voltage, torch.float64, (nq,))
+        nq, ids, gv, bv, sv = self._query_inputs(env_ids, gate_voltages, barrier_voltages, sensor_voltage)
         wd = None if window is None else self._to_dev(window, torch.float64, (nq,))
-        out = {"raw": torch.empty((nq, C, R, R), dtype=torch.float64, device=self.device)}
-        if normalised:
-            out["image"] = torch.empty((nq, R, R, C), dtype=torch.float32, device=self.device)
-            out["plohi"] = torch.empty((nq, 2), dtype=torch.float64, device=self.device)
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())    # noqa: E731
+        out = self._query_outputs(nq, (self.C,), normalised, occupations)
         if noise is None and serial is None and stream_base is None and not occupations:
-            rc = self._lib.qd_probe(self._h, ptr(ids), nq, ptr(gv), ptr(bv), ptr(sv), ptr(wd), ptr(out["raw"]),
-                                    ptr(out.get("image")), ptr(out.get("plohi")), self._stream())
+            rc = self._lib.qd_probe(self._h, _ptr(ids), nq, _ptr(gv), _ptr(bv), _ptr(sv), _ptr(wd), _ptr(out["raw"]),
+                                    _ptr(out.get("image")), _ptr(out.get("plohi")), self._stream())
             _lib.check(self._h, rc, "qd_probe")
             return out
         flags = self.noise_flags if noise is True else self._noise_flags(noise)
-        if serial is None:
-            serial = (1 << 63) | self._probe_serials
-            if flags:
-                self._probe_serials += 1
-        if occupations:
-            out["occupations"] = torch.empty((nq, C, R, R, N), dtype=torch.float64, device=self.device)
         opts = _lib.QdProbeOpts(struct_size=ctypes.sizeof(_lib.QdProbeOpts), noise_flags=int(flags),
-                                serial=int(serial) & 0xFFFFFFFFFFFFFFFF,
+                                serial=self._query_serial(serial, flags),
                                 stream_base=int(self.env_id_offset if stream_base is None else stream_base),
                                 occ_dst=out["occupations"].data_ptr() if occupations else None)
-        rc = self._lib.qd_probe_ex(self._h, ptr(ids), nq, ptr(gv), ptr(bv), ptr(sv), ptr(wd), ptr(out["raw"]),
-                                   ptr(out.get("image")), ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
+        rc = self._lib.qd_probe_ex(self._h, _ptr(ids), nq, _ptr(gv), _ptr(bv), _ptr(sv), _ptr(wd), _ptr(out["raw"]),
+                                   _ptr(out.get("image")), _ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
         _lib.check(self._h, rc, "qd_probe_ex")
         return out
 
@@ -423,14 +439,12 @@ class VecQuantumDeviceEnv:
           serial, stream_base   as in probe()
         Returns device tensors {"raw": (nq, R, R) float64}, plus, with normalised=True, {"image": (nq, R, R) float32
         normalised per query, "plohi": (nq, 2)}, plus, with occupations=True, {"occupations": (nq, R, R, N) float64}."""
-        N, C, R = self.N, self.C, self.R
+        N = self.N
         if frame not in ("virtual", "physical"):
             raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
         if vgm is not None and frame == "physical":
             raise ValueError("vgm has no meaning in the physical frame")
-        gv = gate_voltages if isinstance(gate_voltages, torch.Tensor) else np.asarray(gate_voltages, np.float64)
-        gv = gv.reshape(-1, N)
-        nq = int(gv.shape[0])
+        nq, ids, gv, bv, sv = self._query_inputs(env_ids, gate_voltages, barrier_voltages, sensor_voltage)
         axes = np.stack([scan_control_indices(x, N, frame, nq), scan_control_indices(y, N, frame, nq)], axis=1)
         if np.any(axes[:, 0] == axes[:, 1]):
             raise ValueError("x and y must be two different controls")
@@ -442,35 +456,19 @@ class VecQuantumDeviceEnv:
             if noise and "radial" in tuple(noise):
                 raise ValueError("radial noise is centred on the env's own adjacent-pair observation: not defined for axis scans")
             flags = self._noise_flags(noise)
-        gv = self._to_dev(gv, torch.float64, (nq, N))
-        bv = barrier_voltages if isinstance(barrier_voltages, torch.Tensor) else np.asarray(barrier_voltages, np.float64)
-        bv = self._to_dev(bv.reshape(-1, C), torch.float64, (nq, C))
-        ids = env_ids if isinstance(env_ids, torch.Tensor) else np.asarray(env_ids, np.int32)
-        ids = self._to_dev(ids.reshape(-1), torch.int32, (nq,))
         ax = self._to_dev(axes.astype(np.int32), torch.int32, (nq, 2))
         rg = self._to_dev(rng, torch.float64, (nq, 4))
-        sv = None if sensor_voltage is None else self._to_dev(sensor_voltage, torch.float64, (nq,))
         vm = None if vgm is None else self._to_dev(vgm, torch.float64, (nq, N + 1, N + 1))
         gm = None if gamma is None else self._to_dev(gamma, torch.float64, (nq,))
-        out = {"raw": torch.empty((nq, R, R), dtype=torch.float64, device=self.device)}
-        if normalised:
-            out["image"] = torch.empty((nq, R, R), dtype=torch.float32, device=self.device)
-            out["plohi"] = torch.empty((nq, 2), dtype=torch.float64, device=self.device)
-        if occupations:
-            out["occupations"] = torch.empty((nq, R, R, N), dtype=torch.float64, device=self.device)
-        if serial is None:
-            serial = (1 << 63) | self._probe_serials
-            if flags:
-                self._probe_serials += 1
+        out = self._query_outputs(nq, (), normalised, occupations)
         addr = lambda t: None if t is None else t.data_ptr()                    # noqa: E731
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())    # noqa: E731
         opts = _lib.QdScanOpts(struct_size=ctypes.sizeof(_lib.QdScanOpts),
                                frame=_lib.QD_SCAN_PHYSICAL if frame == "physical" else _lib.QD_SCAN_VIRTUAL,
-                               noise_flags=int(flags), reserved=0, serial=int(serial) & 0xFFFFFFFFFFFFFFFF,
+                               noise_flags=int(flags), reserved=0, serial=self._query_serial(serial, flags),
                                stream_base=int(self.env_id_offset if stream_base is None else stream_base),
                                vgm_dev=addr(vm), gamma_dev=addr(gm), occ_dst=addr(out.get("occupations")))
-        rc = self._lib.qd_scan2d(self._h, ptr(ids), nq, ptr(ax), ptr(rg), ptr(gv), ptr(bv), ptr(sv), ptr(out["raw"]),
-                                 ptr(out.get("image")), ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
+        rc = self._lib.qd_scan2d(self._h, _ptr(ids), nq, _ptr(ax), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv), _ptr(out["raw"]),
+                                 _ptr(out.get("image")), _ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
         _lib.check(self._h, rc, "qd_scan2d")
         return out
 
