@@ -372,6 +372,58 @@ int qd_scan2d(qd_handle* h, const int32_t* env_of_query_dev, int nq, const int32
               const double* gate_v_dev, const double* barrier_v_dev, const double* sensor_v_dev, double* raw_dst,
               float* image_dst, double* plohi_dst, const qd_scan_opts* opts, void* stream);
 
+/* Stateless 2-D scans along two DIRECTION VECTORS over the 2N controls: the axes a double-dot experiment is plotted in --
+ * detuning e{i}_{j} (+1 on plunger i, -1 on plunger j) against the on-site axis U{i}_{j} (1/sqrt(2) on both), as the
+ * reference's GateVoltageComposer builds them (GateVoltageComposer.py:35-84) -- a plunger with a compensating barrier, a
+ * sweep along a ground-truth direction, and qd_scan2d itself as the special case of two unit vectors; with the measurement
+ * stages of a step (sensor noise, latching), the tile search and the normalisation, none of which a grid sent through
+ * qd_eval_points gets.
+ * Controls are indexed as in qd_scan2d.  With W0[2N] = [gate_v, sensor_v, barrier_v] of the query (the BASE POINT: unlike
+ * the composer's crosstalk-free do2d, the controls that are not swept keep the query's voltages and the origin is added
+ * once), sx = linspace(x_lo, x_hi, R)[x] and sy = linspace(y_lo, y_hi, R)[y], pixel (row y, column x) has
+ *   W[i] = fma(sy, dy[i], fma(sx, dx[i], W0[i]))      i = 0..2N-1
+ * and the model sees W through the frame as in qd_scan2d (QD_SCAN_VIRTUAL: VGM W[0:N+1] + origin and W[N+1:];
+ * QD_SCAN_PHYSICAL: W).  With dx = e_ax, dy = e_ay and W0[ax] = W0[ay] = 0 every result has the bits of qd_scan2d(ax, ay)
+ * (with gamma_dev given: see below).
+ *   env_of_query_dev [nq]          int32, the env whose device renders query q
+ *   dir_dev          [nq][2][2N]   dx then dy of query q.  A zero vector is legal: it repeats a 1-D sweep.  Non-finite
+ *                                  coefficients are NOT looked for: they give non-finite voltages and an undefined image
+ *   range_dev        [nq][4]       x_lo, x_hi, y_lo, y_hi of the two scalars sx, sy; lo > hi sweeps downwards
+ *   gate_v_dev       [nq][N], barrier_v_dev [nq][N-1], sensor_v_dev [nq] or NULL (0.0): the base point
+ *   raw_dst, image_dst, plohi_dst  as in qd_scan2d; each may be NULL
+ * opts (NULL: virtual frame, deterministic): the fields of qd_scan_opts with the same meaning, except
+ *   gamma_dev     [nq] peak widths, or NULL: the env's constant coulomb_peak_width.  The vary_peak_width rule of a step is
+ *                 a function of the swept plunger PAIR; an affine axis has no pair, so the rule is not applied
+ * A query occupies one slot of the scan buffers (those of qd_scan2d) with ONE channel image; the two search kernels run with
+ * the affine front end (csrc/qd_pixel.h qd_affine_voltages), everything behind them is the kernels of a step or probe.
+ * On a QD_FLAG_PIXEL_SEARCH handle raw equals qd_eval_points at the pixels' voltages bit for bit.
+ * Stream-ordered with no host wait after the first call, which allocates the scratch with hipMalloc (per query in flight:
+ * what qd_scan2d keeps -- a parameter copy, a state block, P doubles of signal, 2 of percentiles; P*N doubles of occupations
+ * and ceil(P/64) telegraph words from the first call that needs them -- shared with qd_scan2d, and one descriptor of
+ * 4 + 4*8 doubles and the frame, 296 bytes); qd_destroy frees it.  Calls of qd_scan2d and qd_scan_affine on one handle
+ * belong on one stream.  nq may exceed B; queries run in chunks of qd_chunk_envs and results do not depend on the chunking.
+ * The call changes nothing that qd_step, qd_observe, qd_probe*, qd_scan2d, qd_eval_points or any qd_get_* function can see.
+ * QD_ERR_ARG, found without reading the device: NULL env_of_query_dev, dir_dev, range_dev, gate_v_dev or barrier_v_dev,
+ * nq < 0, a struct_size that is not sizeof(qd_scan_affine_opts), an unknown frame, vgm_dev with the physical frame, a noise
+ * bit outside SENSOR | LATCH (the radial stage is centred on the env's own adjacent-pair observation).  An env id outside
+ * [0, B) makes the query inert, its destination slots are left untouched.  QD_ERR_STATE: QD_FLAG_VALIDATE handles and
+ * handles in the full charge-state space, as qd_scan2d refuses them.  Radial noise, more than two axes and Rx != Ry are
+ * not built. */
+typedef struct qd_scan_affine_opts {
+    int32_t  struct_size;   /* = sizeof(qd_scan_affine_opts) */
+    int32_t  frame;         /* QD_SCAN_VIRTUAL 0 / QD_SCAN_PHYSICAL 1 */
+    int32_t  noise_flags;   /* QD_NOISE_SENSOR | QD_NOISE_LATCH; 0 = none */
+    int32_t  reserved;
+    uint64_t serial;        /* the observation-number word of the Philox counter */
+    int64_t  stream_base;   /* query q draws from the streams of global env id stream_base + q (mod 2^32) */
+    const double* vgm_dev;  /* [nq][G][G] or NULL: the env's current matrix (virtual frame only) */
+    const double* gamma_dev;/* [nq] or NULL: the env's constant peak width */
+    double*  occ_dst;       /* [nq][P][N] or NULL */
+} qd_scan_affine_opts;
+int qd_scan_affine(qd_handle* h, const int32_t* env_of_query_dev, int nq, const double* dir_dev, const double* range_dev,
+                   const double* gate_v_dev, const double* barrier_v_dev, const double* sensor_v_dev, double* raw_dst,
+                   float* image_dst, double* plohi_dst, const qd_scan_affine_opts* opts, void* stream);
+
 /* Stitches one channel of nx*ny probe signals into one composite image on the device (map_device_range.py:134-170,
  * map_full_device_range.py:168-194).  raw_dev [nx*ny][C][P] as qd_probe wrote it, query index i*ny + j for scan (i, j);
  * composite_dst [ny*R][nx*R] float32; both DEVICE memory, stream-ordered, no host wait.

@@ -13,6 +13,7 @@
 #include "qd_latch.h"
 #include "qd_points.h"
 #include "qd_scan.h"
+#include "qd_affine.h"
 #include "qd_scratch.h"
 
 // The owners of a stream and of an event.  With the two memory policies of qd_scratch.h these are the only places that
@@ -72,7 +73,7 @@ struct QdStageRing {
 // handle's own envs, a QdScratchSet gives one of its blocks starting from a zeroed object, so whatever a probe does not
 // set reaches the kernels as nullptr / 0 and never as the envs' pointer.  The view also says what shape its blocks have,
 // and every launcher reads grid, front end and channel template argument from there.
-enum QdFront { QD_FRONT_ENV, QD_FRONT_SCAN };   // who fills the records: QdFrontEnv / QdFrontScan (qd_pixel.h)
+enum QdFront { QD_FRONT_ENV, QD_FRONT_SCAN, QD_FRONT_AFFINE };   // who fills the records: QdFrontEnv / QdFrontScan / QdFrontAffine (qd_pixel.h)
 struct QdEnvBufs {
     double *params, *state, *zraw, *plohi, *occ, *eig;
     int channels;                           // channel images per block: h->C, or 1 on the buffers of qd_scan2d
@@ -146,6 +147,9 @@ struct qd_handle {
     // axis scans (qd_scan2d): one launch chunk of parameter copies, state blocks (with the axes descriptors), P doubles of signal and
     // percentiles per query in flight (occupations and telegraph words when asked for), allocated by the first call
     QdScratchSet scan;
+    // affine scans (qd_scan_affine) render on the slots of `scan`; one descriptor (ranges, two direction vectors, frame) per
+    // query in flight, whose address the slot's state block copy carries, allocated by the first call
+    QdDev<QdAffineAxes> affine_axes;
     mutable char err[512];                  // (the launchers take the handle const and still report through it)
 };
 
@@ -219,7 +223,9 @@ struct QdEventPair {
 
 // the front end of a buffer view's records: FE is the search kernels' policy type inside the statement
 #define QD_DISPATCH_FRONT(FRONT_, ...)                                            \
-    { if ((FRONT_) == QD_FRONT_SCAN) { using FE = QdFrontScan; __VA_ARGS__; } else { using FE = QdFrontEnv; __VA_ARGS__; } }
+    { if ((FRONT_) == QD_FRONT_SCAN) { using FE = QdFrontScan; __VA_ARGS__; }                                    \
+      else if ((FRONT_) == QD_FRONT_AFFINE) { using FE = QdFrontAffine; __VA_ARGS__; }                             \
+      else { using FE = QdFrontEnv; __VA_ARGS__; } }
 
 extern "C" int qd_param_block_doubles(int n) { return (n < 2 || n > QD_MAXN) ? -1 : qd_layout(n).size; }
 extern "C" int qd_state_block_doubles(int n) { return (n < 2 || n > QD_MAXN) ? -1 : qd_layout(n).s_size; }
@@ -635,7 +641,8 @@ static int qd_sorted_records(const qd_handle* h) { return (qd_validate(h) || h->
 
 // a5/a8-a10 by the per-pixel search on `cnt` blocks of `b`.  tiled: the exact redo pass, only on the pixels whose record
 // asks for it (behind the tile search, or behind a front end that filled the records itself); else every pixel.
-// (in both search kernels noise_flags reaches qd_radial_replaced alone, false without the radial bit, which qd_scan2d refuses)
+// (in both search kernels noise_flags reaches qd_radial_replaced alone, false without the radial bit, which qd_scan2d and
+// qd_scan_affine refuse)
 static int qd_launch_candidates(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, const int32_t* env_ids, int base, int cnt,
                                 hipStream_t s, bool tiled) {
     const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
@@ -797,7 +804,7 @@ struct QdQueryOpts {
     bool occ;                               // the caller takes the occupations
 };
 
-// The stateless queries (qd_probe_ex, qd_scan2d): `nq` of them in launch chunks of h->chunk slots on the blocks of `set`,
+// The stateless queries (qd_probe_ex, qd_scan2d, qd_scan_affine): `nq` of them in launch chunks of h->chunk slots on the blocks of `set`,
 // each slot `channels` images filled by `front`.  Per chunk: gather(base, cnt, bufs) copies the envs' blocks into the slots
 // and applies the queries; then the stages of an observation in qd_observe's order -- telegraph words, search and ground
 // state, latching, sensor, percentiles -- on the slots alone, without eigenvalues; occupations, telegraph words and noise
@@ -930,6 +937,50 @@ extern "C" int qd_scan2d(qd_handle* h, const int32_t* env_of_query, int nq, cons
             if (raw_dst || image_dst || plohi_dst || occ_dst)
                 qd_k_scan_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, h->P, sb.zraw, sb.plohi, sb.occ,
                                                                                     raw_dst, image_dst, plohi_dst, occ_dst);
+        });
+}
+
+extern "C" int qd_scan_affine(qd_handle* h, const int32_t* env_of_query, int nq, const double* dir, const double* range,
+                              const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst,
+                              float* image_dst, double* plohi_dst, const qd_scan_affine_opts* opts, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    if (nq < 0) return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: nq < 0");
+    if (!env_of_query || !dir || !range) return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: env_of_query_dev, dir_dev or range_dev is NULL");
+    if (!gate_v || !barrier_v) return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: gate_v_dev or barrier_v_dev is NULL");
+    if (opts && opts->struct_size != (int32_t)sizeof(qd_scan_affine_opts))
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: opts->struct_size is not sizeof(qd_scan_affine_opts)");
+    if (opts && opts->frame != QD_SCAN_VIRTUAL && opts->frame != QD_SCAN_PHYSICAL)
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL");
+    if (opts && opts->frame == QD_SCAN_PHYSICAL && opts->vgm_dev)
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: vgm_dev has no meaning in the physical frame");
+    if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_LATCH)))
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
+                                      "centred on the env's own adjacent-pair observation)");
+    if (h->cfg.flags & QD_FLAG_VALIDATE)
+        return qd_fail(h, QD_ERR_STATE, "qd_scan_affine: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
+                                        "B envs' last observe and renders no scans; use a handle without the flag");
+    if (h->full_m)
+        return qd_fail(h, QD_ERR_STATE, "qd_scan_affine: the full charge-state space synthesises its own voltages "
+                                        "(qd_k_full_structure); a scan front end for it is not built");
+    if (nq == 0) return QD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    QD_ON_DEVICE(h);
+    const QdQueryOpts o = opts ? QdQueryOpts{opts->noise_flags, opts->serial, opts->stream_base, opts->occ_dst != nullptr} : QdQueryOpts{};
+    double* const occ_dst = opts ? opts->occ_dst : nullptr;
+    const QdAffineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, opts ? opts->vgm_dev : nullptr,
+                          opts ? opts->gamma_dev : nullptr, opts ? opts->frame : QD_SCAN_VIRTUAL};
+    // one descriptor per query in flight (qd_run_queries: h->chunk slots), beside the slots of the scan buffers
+    QD_HIP(h->affine_axes.reserve((size_t)h->chunk));
+    QdAffineAxes* const axes = h->affine_axes.p;
+    return qd_run_queries(h, h->scan, 1, QD_FRONT_AFFINE, o, nq, s,
+        [&](int base, int cnt, const QdEnvBufs& sb) {
+            qd_k_affine_gather<<<dim3(cnt), dim3(QD_AFFINE_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, sb.params, sb.state,
+                                                                           axes);
+        },
+        [&](int base, int cnt, const QdEnvBufs& sb) {
+            if (raw_dst || image_dst || plohi_dst || occ_dst)
+                qd_k_affine_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, h->P, sb.zraw, sb.plohi, sb.occ,
+                                                                                      raw_dst, image_dst, plohi_dst, occ_dst);
         });
 }
 

@@ -167,6 +167,81 @@ struct QdFrontScan {
 };
 
 // ---------------------------------------------------------------------------
+// Third front end (qd_scan_affine): a 2-D scan whose two axes are DIRECTION VECTORS over the 2N controls (detuning e{i}_{j},
+// the on-site axis U{i}_{j}, a plunger with a compensating barrier, any mixed-control axis: GateVoltageComposer.py:35-84).
+// With W0[2N] = [gate_v, sensor_v, barrier_v] of the state block, sx = linspace(x_lo, x_hi, R, x), sy = linspace(y_lo, y_hi,
+// R, y) (x along columns) and the directions dx, dy of the descriptor
+//   W[i] = fma(sy, dy[i], fma(sx, dx[i], W0[i]))        i = 0..2N-1
+// then the frame, vpp and tc as the tail of qd_scan_voltages: same operations, order and fences.  With dx = e_ax, dy = e_ay
+// and W0[ax] = W0[ay] = 0 the two fmas are exact (fma(sx, 1, 0) = sx, fma(sy, 0, sx) = sx, fma(sy, 0, fma(sx, 0, w)) = w),
+// so the bits are those of qd_scan_voltages(ax, ay).  The descriptor (4 + 4N doubles and the frame) does not fit in the
+// Kalman block of a 2-dot state block (8 doubles): it lives in a buffer of its own and the slot's state block copy carries
+// its ADDRESS in the place of the Kalman means.  An address read from memory is a flat pointer, and loads through one are
+// vector loads; the descriptor is uniform over a block and constant while a search kernel runs (the gather kernel before it
+// wrote it), so on the device the address is taken as one into the constant address space and the ranges and directions
+// arrive through scalar loads like the parameter block.
+// ---------------------------------------------------------------------------
+struct QdAffineAxes {
+    double x_lo, x_hi, y_lo, y_hi;
+    double dx[2 * QD_MAXN], dy[2 * QD_MAXN];                     // the first 2N of each
+    int32_t frame, pad;
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) QdAffineAxes* QdAffineAxesPtr;
+#else
+typedef const QdAffineAxes* QdAffineAxesPtr;
+#endif
+
+template <int N>
+QD_HD void qd_affine_voltages(const double* par, const double* st, QdAffineAxesPtr axes, int R, int x, int y,
+                              double* v_ext, double* vpp, double* tc) {
+    constexpr int G = N + 1, NB = N - 1, V = 2 * N;
+    const QdLayout L = qd_layout(N);
+    const double* vgm = st + L.s_vgm;
+    const double sx = qd_linspace(axes->x_lo, axes->x_hi, R, x);
+    const double sy = qd_linspace(axes->y_lo, axes->y_hi, R, y);
+    double W[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const double w0 = i < N ? st[L.s_gate_v + i] : (i == N ? st[L.s_sensor_gt] : st[L.s_barrier_v + (i - G)]);
+        W[i] = fma(sy, axes->dy[i], fma(sx, axes->dx[i], w0));
+    }
+    if (axes->frame == QD_SCAN_PHYSICAL) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) v_ext[i] = W[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < G; ++i) { v_ext[i] = qd_dotN<G>(vgm + i * G, W) + par[L.origin + i]; QD_ROW_FENCE(); }
+#pragma unroll
+        for (int b = 0; b < NB; ++b) v_ext[G + b] = W[G + b];
+    }
+#pragma unroll
+    for (int i = 0; i < G; ++i) { vpp[i] = qd_dotN<V>(par + L.cgd + i * V, v_ext); QD_ROW_FENCE(); }
+    const double tc_base = par[L.scal + 0];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        double vb_eff = v_ext[G + b] + qd_dotN<G>(par + L.cbg + b * G, v_ext);
+        tc[b] = tc_base * exp(-par[L.alpha + b] * vb_eff);
+        QD_ROW_FENCE();
+    }
+}
+
+// one image per slot over the slot's QdAffineAxes, whose address travels in the slot's state block copy (s_kmean)
+static_assert(sizeof(const QdAffineAxes*) == sizeof(double), "the descriptor's address overlays one double of the state block copy");
+QD_HD QdAffineAxesPtr qd_affine_axes_of(const double* st, const QdLayout& L) {
+    return (QdAffineAxesPtr)(*reinterpret_cast<const uintptr_t*>(st + L.s_kmean));
+}
+struct QdFrontAffine {
+    static constexpr int channels(int) { return 1; }
+    template <int N>
+    static QD_HD void voltages(const double* par, const double* st, int, int R, int x, int y, double* v_ext, double* vpp,
+                               double* tc) {
+        qd_affine_voltages<N>(par, st, qd_affine_axes_of(st, qd_layout(N)), R, x, y, v_ext, vpp, tc);
+    }
+};
+
+// ---------------------------------------------------------------------------
 // a8 continuous ground state, with the optional linear voltage-dependent
 // capacitance model (f4; voltage_dependent_capacitance.py:72-88, ground_state.py:53-57):
 //   cdd(V) = cdd_full (1 + alpha mean|v_ext|),  cgd(V) = cgd_full (1 + beta mean|v_ext|)

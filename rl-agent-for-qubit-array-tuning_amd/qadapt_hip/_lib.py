@@ -27,7 +27,7 @@ EXPORTS = [
     "qd_update_capacitance", "qd_step", "qd_snapshot", "qd_get_state", "qd_set_state", "qd_get_raw",
     "qd_get_occupations", "qd_get_candidates", "qd_get_eigen", "qd_get_search_stats", "qd_get_solver_stats", "qd_get_rng_state", "qd_set_rng_state",
     "qd_time_ground_kernel", "qd_time_candidates_kernel", "qd_time_kernels", "qd_timed_kernel_name", "qd_chunk_envs",
-    "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex",
+    "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex", "qd_scan_affine",
 ]
 # exported too, kept apart: names with a digit, which a scan of qdsim.h for `qd_[a-z_]+(` does not find
 EXPORTS_WITH_DIGITS = ["qd_scan2d"]
@@ -71,6 +71,11 @@ class QdScanOpts(ctypes.Structure):
         ("reserved", ctypes.c_int32), ("serial", ctypes.c_uint64), ("stream_base", ctypes.c_int64),
         ("vgm_dev", ctypes.c_void_p), ("gamma_dev", ctypes.c_void_p), ("occ_dst", ctypes.c_void_p),
     ]
+
+
+class QdScanAffineOpts(ctypes.Structure):
+    """qd_scan_affine_opts of include/qdsim.h: the fields of qd_scan_opts for a qd_scan_affine call."""
+    _fields_ = list(QdScanOpts._fields_)
 
 
 class QdError(RuntimeError):
@@ -150,6 +155,8 @@ def lib():
     L.qd_eval_points.restype = ctypes.c_int
     L.qd_scan2d.argtypes = [vp, vp, ctypes.c_int, vp, dp, dp, dp, dp, dp, fp, dp, ctypes.POINTER(QdScanOpts), vp]
     L.qd_scan2d.restype = ctypes.c_int
+    L.qd_scan_affine.argtypes = [vp, vp, ctypes.c_int, dp, dp, dp, dp, dp, dp, fp, dp, ctypes.POINTER(QdScanAffineOpts), vp]
+    L.qd_scan_affine.restype = ctypes.c_int
     _LIB = L
     return L
 

@@ -135,6 +135,15 @@ class ArrayFacade:
         host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
         return {k: host(v)[0] for k, v in out.items()}
 
+    def scan_affine(self, x, y, x_range, y_range, gate_voltages, barrier_voltages, sensor_voltage=None, **kw):
+        """The backend's scan_affine for this env (axes such as "e1_2" and "U1_2", a {control: coefficient} dict or a (2N,)
+        vector): one query, numpy results without the query axis ("raw" (R, R), ...)."""
+        out = self._b.scan_affine([0], x, y, x_range, y_range, np.asarray(gate_voltages, np.float64)[None, :],
+                                  np.asarray(barrier_voltages, np.float64)[None, :],
+                                  sensor_voltage=None if sensor_voltage is None else float(sensor_voltage), **kw)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return {k: host(v)[0] for k, v in out.items()}
+
 
 class QuantumDeviceEnv:
     metadata = {"render_modes": []}

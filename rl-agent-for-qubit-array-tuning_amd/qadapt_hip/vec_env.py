@@ -15,6 +15,7 @@ an input provider here: pass `capacitance_model=callable`, or
 from __future__ import annotations
 
 import ctypes
+import re
 
 import numpy as np
 import torch
@@ -143,6 +144,66 @@ def scan_control_indices(x, N, frame, nq):
     if idx.shape != (nq,):
         raise ValueError(f"{len(idx)} controls for {nq} queries")
     return idx
+
+
+_COMBINATION_AXIS = re.compile(r"^([eU])(\d+)_(\d+)$")
+
+
+def scan_axis_vector(axis, N, frame="virtual"):
+    """(2N,) float64 direction of one axis of scan_affine over the controls in the order of the model's voltage vector
+    (0..N-1 the plungers, N the sensor gate, N+1..2N-1 the barriers).  `axis` is
+      a control index or name, as scan_control_index takes them: the unit vector of that control;
+      "e{i}_{j}": detuning, +1 on plunger i and -1 on plunger j; "U{i}_{j}": the on-site axis, 1/sqrt(2) on both plungers --
+          1-indexed and unnormalised exactly as the reference's GateVoltageComposer builds them (v_i - v_j and
+          (v_i + v_j) / sqrt(2), GateVoltageComposer.py:66-82); the plungers are virtual or physical by `frame`;
+      a {control: coefficient} dict, its controls indices or names (coefficients of a control named twice add up);
+      a (2N,) sequence of numbers: the vector itself."""
+    if isinstance(axis, str):
+        m = _COMBINATION_AXIS.match(axis)
+        if m:
+            i, j = int(m.group(2)), int(m.group(3))
+            if not (1 <= i <= N and 1 <= j <= N):
+                raise ValueError(f"{axis!r}: the dots of a combination axis are 1..{N} for {N} dots")
+            if i == j:
+                raise ValueError(f"{axis!r}: a combination axis needs two different dots")
+            v = np.zeros(2 * N)
+            if m.group(1) == "e":
+                v[i - 1], v[j - 1] = 1.0, -1.0
+            else:
+                v[i - 1] = v[j - 1] = 1.0 / np.sqrt(2.0)
+            return v
+    if isinstance(axis, (str, int, np.integer)):
+        v = np.zeros(2 * N)
+        v[scan_control_index(axis, N, frame)] = 1.0
+        return v
+    if isinstance(axis, dict):
+        v = np.zeros(2 * N)
+        for name, c in axis.items():
+            v[scan_control_index(name, N, frame)] += float(c)
+        return v
+    if isinstance(axis, torch.Tensor):
+        axis = axis.detach().cpu().numpy()
+    v = np.asarray(axis, np.float64)
+    if v.shape != (2 * N,):
+        raise ValueError(f"an axis vector has one coefficient per control, shape ({2 * N},); got {v.shape}")
+    return v.copy()
+
+
+def scan_axis_vectors(axis, N, frame, nq):
+    """(nq, 2N) float64 directions: one axis for all queries (anything scan_axis_vector takes), an (nq, 2N) array, or a
+    list of nq axes that are not all plain numbers (names, dicts, vectors)."""
+    if isinstance(axis, torch.Tensor):
+        axis = axis.detach().cpu().numpy()
+    if isinstance(axis, (list, tuple)) and not all(isinstance(a, (int, float, np.integer, np.floating)) for a in axis):
+        rows = [scan_axis_vector(a, N, frame) for a in axis]
+        if len(rows) != nq:
+            raise ValueError(f"{len(rows)} axes for {nq} queries")
+        return np.stack(rows)
+    if isinstance(axis, np.ndarray) and axis.ndim == 2:
+        if axis.shape != (nq, 2 * N):
+            raise ValueError(f"per-query axis vectors have shape ({nq}, {2 * N}); got {axis.shape}")
+        return np.ascontiguousarray(axis, np.float64)
+    return np.tile(scan_axis_vector(axis, N, frame), (nq, 1))
 
 
 def _ptr(t):
@@ -470,6 +531,60 @@ class VecQuantumDeviceEnv:
         rc = self._lib.qd_scan2d(self._h, _ptr(ids), nq, _ptr(ax), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv), _ptr(out["raw"]),
                                  _ptr(out.get("image")), _ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
         _lib.check(self._h, rc, "qd_scan2d")
+        return out
+
+    def scan_affine(self, env_ids, x, y, x_range, y_range, gate_voltages, barrier_voltages, sensor_voltage=None,
+                    frame="virtual", vgm=None, gamma=None, normalised=False, occupations=False, noise=None, serial=None,
+                    stream_base=None):
+        """Stateless 2-D scans along two direction vectors over the controls (qd_scan_affine): detuning against the on-site
+        axis, a plunger with a compensating barrier, any mixed-control axis, for nq queries in one call, each on the device
+        of env `env_ids[q]`.  With W0 = [gate_voltages, sensor_voltage, barrier_voltages] of the query, pixel (row r, column
+        c) sits at W0 + linspace(*x_range, R)[c] * dx + linspace(*y_range, R)[r] * dy.  Nothing of the episodes changes.
+          x, y              the two axes, one for all queries or one per query (scan_axis_vector, scan_axis_vectors): a control
+                            index or name as scan2d takes them; "e{i}_{j}" (detuning: +1 on plunger i, -1 on plunger j) or
+                            "U{i}_{j}" (on-site: 1/sqrt(2) on both), 1-indexed and unnormalised exactly as the reference's
+                            GateVoltageComposer builds them, plungers virtual or physical by `frame`; a {control: coefficient}
+                            dict; a (2N,) vector, or (nq, 2N) for one per query.  A zero vector repeats a 1-D sweep.
+                            Coefficients are not checked for NaN or infinity
+          x_range, y_range  (lo, hi) of the scalar that multiplies the axis, for all queries or (nq, 2)
+          gate_voltages, barrier_voltages, sensor_voltage   the BASE POINT of the scan.  Unlike the composer's crosstalk-free
+                            `do2d(x_gate, ..., y_gate, ...)`, which holds every control that is not swept at 0 and adds its
+                            origin once per "vP" axis, sqrt(2) times per "U" axis and never per "e" axis, the controls that
+                            are not swept keep these voltages (a swept one starts from its own) and the origin is added once
+          frame, vgm, normalised, occupations, noise, serial, stream_base   as in scan2d
+          gamma             None (each env's constant coulomb_peak_width), a scalar or (nq,) peak widths.  The vary_peak_width
+                            rule of a step is a function of the swept plunger pair and is not applied: an axis has no pair
+        With unit vectors for x and y and 0 at those two controls of the base point this is scan2d (bit for bit, given the
+        same gamma).  Returns what scan2d returns."""
+        N = self.N
+        if frame not in ("virtual", "physical"):
+            raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
+        if vgm is not None and frame == "physical":
+            raise ValueError("vgm has no meaning in the physical frame")
+        nq, ids, gv, bv, sv = self._query_inputs(env_ids, gate_voltages, barrier_voltages, sensor_voltage)
+        dirs = np.stack([scan_axis_vectors(x, N, frame, nq), scan_axis_vectors(y, N, frame, nq)], axis=1)
+        rng = np.concatenate([np.broadcast_to(np.asarray(x_range, np.float64), (nq, 2)),
+                              np.broadcast_to(np.asarray(y_range, np.float64), (nq, 2))], axis=1)
+        if noise is True:
+            flags = self.noise_flags & ~_lib.QD_NOISE_RADIAL
+        else:
+            if noise and "radial" in tuple(noise):
+                raise ValueError("radial noise is centred on the env's own adjacent-pair observation: not defined for axis scans")
+            flags = self._noise_flags(noise)
+        dr = self._to_dev(dirs, torch.float64, (nq, 2, 2 * N))
+        rg = self._to_dev(rng, torch.float64, (nq, 4))
+        vm = None if vgm is None else self._to_dev(vgm, torch.float64, (nq, N + 1, N + 1))
+        gm = None if gamma is None else self._to_dev(gamma, torch.float64, (nq,))
+        out = self._query_outputs(nq, (), normalised, occupations)
+        addr = lambda t: None if t is None else t.data_ptr()                    # noqa: E731
+        opts = _lib.QdScanAffineOpts(struct_size=ctypes.sizeof(_lib.QdScanAffineOpts),
+                                     frame=_lib.QD_SCAN_PHYSICAL if frame == "physical" else _lib.QD_SCAN_VIRTUAL,
+                                     noise_flags=int(flags), reserved=0, serial=self._query_serial(serial, flags),
+                                     stream_base=int(self.env_id_offset if stream_base is None else stream_base),
+                                     vgm_dev=addr(vm), gamma_dev=addr(gm), occ_dst=addr(out.get("occupations")))
+        rc = self._lib.qd_scan_affine(self._h, _ptr(ids), nq, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv), _ptr(out["raw"]),
+                                      _ptr(out.get("image")), _ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
+        _lib.check(self._h, rc, "qd_scan_affine")
         return out
 
     # ------------------------------------------------------------------ point evaluation
