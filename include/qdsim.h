@@ -424,6 +424,71 @@ int qd_scan_affine(qd_handle* h, const int32_t* env_of_query_dev, int nq, const 
                    const double* gate_v_dev, const double* barrier_v_dev, const double* sensor_v_dev, double* raw_dst,
                    float* image_dst, double* plohi_dst, const qd_scan_affine_opts* opts, void* stream);
 
+/* Stateless dense 1-D sweeps along one DIRECTION VECTOR over the 2N controls: the reference model layer's
+ * do1d_open(gate, min, max, points) over GateVoltageComposer.do1d (GateVoltageComposer.py:35-84, 213-222) for P{i}, vP{i},
+ * e{i}_{j}, U{i}_{j} or any mixed-control direction, nq lines of n_points points in one call, with the measurement stages of a
+ * step (sensor noise, latching ALONG the sweep) and a normalisation per line.  A line sent through qd_eval_points occupies a
+ * whole slot of C*P records and is deterministic only; qd_scan_affine with a zero dy renders the same line R times.
+ * Controls are indexed as in qd_scan2d.  With W0[2N] = [gate_v, sensor_v, barrier_v] of the query (the BASE POINT, as in
+ * qd_scan_affine) and s = linspace(lo, hi, n_points)[t], point t has
+ *   W[i] = fma(s, d[i], W0[i])      i = 0..2N-1
+ * and the model sees W through the frame as in qd_scan2d.  The front end (csrc/qd_line.h qd_line_voltages) performs the
+ * operations of qd_scan_affine's in the same order: with dx = d, dy = 0 and R = n_points, row 0 of that scan has the bits of
+ * the line on a QD_FLAG_PIXEL_SEARCH handle, with noise too under the same serial and stream base (row 0 of an image and a
+ * line share the point indices, the start of the telegraph chain and the latching walk).  raw equals qd_eval_points at the
+ * points' voltages bit for bit.
+ *   env_of_query_dev [nq]       int32, the env whose device renders query q
+ *   n_points                    points per line, 1..P of the handle, the same for all queries of the call
+ *   dir_dev          [nq][2N]   the direction d of query q.  The zero vector is legal: it repeats the base point.
+ *                               Non-finite coefficients are NOT looked for
+ *   range_dev        [nq][2]    lo, hi of the scalar s; lo > hi sweeps downwards, lo == hi repeats a point
+ *   gate_v_dev       [nq][N], barrier_v_dev [nq][N-1], sensor_v_dev [nq] or NULL (0.0): the base point
+ *   raw_dst          [nq][n]    float64 unnormalised signal; may be NULL
+ *   image_dst        [nq][n]    float32, normalised per line with its own 0.5 / 99.5 percentiles (all zero for a constant
+ *                               line); may be NULL
+ *   plohi_dst        [nq][2]    those percentiles; may be NULL
+ * opts (NULL: virtual frame, deterministic): the fields of qd_scan_affine_opts with the same meaning, except
+ *   occ_dst       [nq][n][N] float64 or NULL: the occupations the signal was formed from (after latching, if it ran)
+ *   noise_flags   QD_NOISE_LATCH walks the line as ONE row of n points: the held state starts at point 0 and is never reset
+ *                 (an image resets it at every row start), the Philox counter of point t is t.  QD_NOISE_SENSOR: the
+ *                 telegraph chain starts at point 0, white noise is keyed by the point index; the channel word is 0
+ * A query occupies one slot of its OWN size: Rl x Rl records with Rl = ceil(sqrt(n)), record p = point p, the Rl*Rl - n tail
+ * records inert (all zero: no search, no eigen task).  With n <= P, Rl <= R.  Per launch: gather, telegraph chain, the line
+ * front kernel (records in the hand-over form of the tile search), the redo instantiation of the per-pixel search, the
+ * ground-state kernels, the latching walk, the sensor stage, a pack of the n leading values of each slot into a dense row,
+ * the percentile kernel, the write -- the kernels of a step with the slot geometry as data, and five small kernels of the
+ * line's own (csrc/qd_line.h).  Slots in flight per launch: what lane 0's record buffer (qd_chunk_envs * C * P records) and
+ * slabs hold, floor(qd_chunk_envs * C * P / Rl^2) and floor(slab capacity / ceil(Rl^2 / 256)), at most QD_LINE_SLOTS.
+ * Stream-ordered with no host wait after the first call, which allocates the scratch with hipMalloc (per slot in flight: a
+ * parameter copy, a state block, Rl^2 + n doubles of signal, 2 of percentiles, one descriptor of 2 + 2*8 doubles and the
+ * frame, 152 bytes; Rl^2*N doubles of occupations and ceil(Rl^2/64) telegraph words from the first call that needs them --
+ * 11.3 KB per 64-point line at 8 dots with everything, 46 MB for 4096 of them); a later call with more slots or longer lines grows it (hipFree waits
+ * for the device); qd_destroy frees it.  Calls of qd_scan1d belong on the stream qd_scan2d and qd_scan_affine use on that
+ * handle.  nq may exceed B, many queries may name one env, and results do not depend on how queries fall into launches.
+ * The call changes nothing that qd_step, qd_observe, qd_probe*, qd_scan2d, qd_scan_affine, qd_eval_points or any qd_get_*
+ * function can see.
+ * QD_ERR_ARG, found without reading the device: NULL env_of_query_dev, dir_dev, range_dev, gate_v_dev or barrier_v_dev,
+ * nq < 0, n_points outside 1..P, a struct_size that is not sizeof(qd_scan1d_opts), an unknown frame, vgm_dev with the
+ * physical frame, a noise bit outside SENSOR | LATCH (the radial stage is centred on the env's own adjacent-pair
+ * observation).  An env id outside [0, B) makes the query inert, its destination slots are left untouched.  QD_ERR_STATE:
+ * QD_FLAG_VALIDATE handles and handles in the full charge-state space, as qd_scan2d refuses them.  nq == 0 does nothing.
+ * Radial noise, lines longer than P, different lengths within one call and eigenvalues per point are not built. */
+#define QD_LINE_SLOTS 4096
+typedef struct qd_scan1d_opts {
+    int32_t  struct_size;   /* = sizeof(qd_scan1d_opts) */
+    int32_t  frame;         /* QD_SCAN_VIRTUAL 0 / QD_SCAN_PHYSICAL 1 */
+    int32_t  noise_flags;   /* QD_NOISE_SENSOR | QD_NOISE_LATCH; 0 = none */
+    int32_t  reserved;
+    uint64_t serial;        /* the observation-number word of the Philox counter */
+    int64_t  stream_base;   /* query q draws from the streams of global env id stream_base + q (mod 2^32) */
+    const double* vgm_dev;  /* [nq][G][G] or NULL: the env's current matrix (virtual frame only) */
+    const double* gamma_dev;/* [nq] or NULL: the env's constant peak width */
+    double*  occ_dst;       /* [nq][n][N] or NULL */
+} qd_scan1d_opts;
+int qd_scan1d(qd_handle* h, const int32_t* env_of_query_dev, int nq, int n_points, const double* dir_dev,
+              const double* range_dev, const double* gate_v_dev, const double* barrier_v_dev, const double* sensor_v_dev,
+              double* raw_dst, float* image_dst, double* plohi_dst, const qd_scan1d_opts* opts, void* stream);
+
 /* Stitches one channel of nx*ny probe signals into one composite image on the device (map_device_range.py:134-170,
  * map_full_device_range.py:168-194).  raw_dev [nx*ny][C][P] as qd_probe wrote it, query index i*ny + j for scan (i, j);
  * composite_dst [ny*R][nx*R] float32; both DEVICE memory, stream-ordered, no host wait.

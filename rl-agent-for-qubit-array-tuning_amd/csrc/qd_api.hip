@@ -14,6 +14,7 @@
 #include "qd_points.h"
 #include "qd_scan.h"
 #include "qd_affine.h"
+#include "qd_line.h"
 #include "qd_scratch.h"
 
 // The owners of a stream and of an event.  With the two memory policies of qd_scratch.h these are the only places that
@@ -73,10 +74,13 @@ struct QdStageRing {
 // handle's own envs, a QdScratchSet gives one of its blocks starting from a zeroed object, so whatever a probe does not
 // set reaches the kernels as nullptr / 0 and never as the envs' pointer.  The view also says what shape its blocks have,
 // and every launcher reads grid, front end and channel template argument from there.
-enum QdFront { QD_FRONT_ENV, QD_FRONT_SCAN, QD_FRONT_AFFINE };   // who fills the records: QdFrontEnv / QdFrontScan / QdFrontAffine (qd_pixel.h)
+// who fills the records: QdFrontEnv / QdFrontScan / QdFrontAffine (qd_pixel.h) inside the search kernels, or, QD_FRONT_LINE, a
+// front kernel of its own before them (qd_k_line_front), behind which only the redo instantiation of the search runs
+enum QdFront { QD_FRONT_ENV, QD_FRONT_SCAN, QD_FRONT_AFFINE, QD_FRONT_LINE };
 struct QdEnvBufs {
     double *params, *state, *zraw, *plohi, *occ, *eig;
     int channels;                           // channel images per block: h->C, or 1 on the buffers of qd_scan2d
+    int R, P;                               // side and pixel count of one channel image: h->R and h->P, or those of a line's slot (qd_scan1d)
     QdFront front;
     int noise_flags;
     unsigned long long* tel; int tel_words;
@@ -102,10 +106,10 @@ struct QdScratchSet {
         return e;
     }
     // without noise, eigenvalues or telegraph words
-    QdEnvBufs view(int channels, QdFront front = QD_FRONT_ENV) const {
+    QdEnvBufs view(int channels, int R, QdFront front = QD_FRONT_ENV) const {
         QdEnvBufs b{};
         b.params = params.p; b.state = state.p; b.zraw = z.p; b.plohi = plohi.p; b.occ = occ.p;
-        b.channels = channels; b.front = front;
+        b.channels = channels; b.R = R; b.P = R * R; b.front = front;
         return b;
     }
 };
@@ -150,6 +154,12 @@ struct qd_handle {
     // affine scans (qd_scan_affine) render on the slots of `scan`; one descriptor (ranges, two direction vectors, frame) per
     // query in flight, whose address the slot's state block copy carries, allocated by the first call
     QdDev<QdAffineAxes> affine_axes;
+    // lines (qd_scan1d): slots of ceil(sqrt(n))^2 records each -- parameter copies, state blocks, signals, percentiles
+    // (occupations and telegraph words when asked for), one descriptor and a dense row of n signals per line in flight,
+    // allocated by the first call and grown by a call that needs more
+    QdScratchSet line;
+    QdDev<QdLineAxes> line_axes;
+    QdDev<double> line_dense;
     mutable char err[512];                  // (the launchers take the handle const and still report through it)
 };
 
@@ -158,7 +168,7 @@ static bool qd_validate(const qd_handle* h) { return (h->cfg.flags & QD_FLAG_VAL
 static QdEnvBufs qd_env_bufs(const qd_handle* h) {
     QdEnvBufs b{};
     b.params = h->params.p; b.state = h->state.p; b.zraw = h->zraw.p; b.plohi = h->plohi.p; b.occ = h->occ.p; b.eig = h->eig.p;
-    b.channels = h->C; b.front = QD_FRONT_ENV;
+    b.channels = h->C; b.R = h->R; b.P = h->P; b.front = QD_FRONT_ENV;
     b.noise_flags = h->cfg.noise_flags;
     b.tel = h->tel.p; b.tel_words = h->tel_words;
     b.serial = h->obs_serial;
@@ -221,10 +231,12 @@ struct QdEventPair {
 #define QD_DISPATCH_BOOL(COND_, NAME_, ...)                                       \
     { if (COND_) { constexpr bool NAME_ = true; __VA_ARGS__; } else { constexpr bool NAME_ = false; __VA_ARGS__; } }
 
-// the front end of a buffer view's records: FE is the search kernels' policy type inside the statement
+// the front end of a buffer view's records: FE is the search kernels' policy type inside the statement.  (A line's records
+// are filled before the search: its redo pass never asks FE for voltages, only for the ONE channel image per slot, and so
+// runs the instantiation of the affine scans.)
 #define QD_DISPATCH_FRONT(FRONT_, ...)                                            \
     { if ((FRONT_) == QD_FRONT_SCAN) { using FE = QdFrontScan; __VA_ARGS__; }                                    \
-      else if ((FRONT_) == QD_FRONT_AFFINE) { using FE = QdFrontAffine; __VA_ARGS__; }                             \
+      else if ((FRONT_) == QD_FRONT_AFFINE || (FRONT_) == QD_FRONT_LINE) { using FE = QdFrontAffine; __VA_ARGS__; } \
       else { using FE = QdFrontEnv; __VA_ARGS__; } }
 
 extern "C" int qd_param_block_doubles(int n) { return (n < 2 || n > QD_MAXN) ? -1 : qd_layout(n).size; }
@@ -532,15 +544,17 @@ static hipError_t qd_launch_solve(const qd_handle* h, const QdLane& ln, hipStrea
 // them in `st`), in launches of at most gs_chunk envs (the slabs in flight)
 static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, const int32_t* env_ids, int base, int cnt,
                             hipStream_t s, int st) {
-    const int nb = (h->P + h->ppb - 1) / h->ppb, C = b.channels;
+    const int nb = (b.P + h->ppb - 1) / h->ppb, C = b.channels;
+    // blocks per launch: what the slabs hold (the handle's own geometry: gs_chunk)
+    const int per = (int)(h->gs_batches / ((size_t)C * nb));
     unsigned* tilelist = ln.gtiles.p + 16;
     const bool val = qd_validate(h);
     QdWide wide = h->wide; wide.buf = ln.wide.p;
     // records: product mode keeps one launch chunk (slot = position in the chunk), validate mode all envs (position in the list)
     const int rec0 = val ? base : 0;
-    for (int off = 0; off < cnt; off += h->gs_chunk) {
-        const int n = cnt - off < h->gs_chunk ? cnt - off : h->gs_chunk;
-        const QdGsGeom g{n, C, h->P, nb};
+    for (int off = 0; off < cnt; off += per) {
+        const int n = cnt - off < per ? cnt - off : per;
+        const QdGsGeom g{n, C, b.P, nb};
         const unsigned batches = (unsigned)((size_t)n * C * nb);
         if (st & QD_ST_STRUCTURE) {
             QD_HIP(hipMemsetAsync(ln.gtiles.p, 0, sizeof(unsigned) * 16, s));
@@ -553,14 +567,14 @@ static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane
                 else { constexpr int SPL = 8; constexpr bool WIDE = true; __VA_ARGS__; }
                 QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_FULL(QD_DISPATCH_N(h->N,
                     qd_k_full_structure<NN, VAL, SPL, WIDE><<<dim3(batches), dim3(64 * QdFullWpb<SPL>::v), 0, s>>>(env_ids, base + off,
-                        rec0 + off, g, h->ppb, h->R, b.params, b.state, b.noise_flags, h->ftab.p, ln.recs.p, ln.slabs.p, ln.gtiles.p, tilelist,
+                        rec0 + off, g, h->ppb, b.R, b.params, b.state, b.noise_flags, h->ftab.p, ln.recs.p, ln.slabs.p, ln.gtiles.p, tilelist,
                         h->gs_batches, wide))));
 #undef QD_DISPATCH_FULL
             } else {
                 // (small launches: 16 waves per batch instead of 4, see the kernel)
                 QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_BOOL(batches < (unsigned)h->cus, SMALL, QD_DISPATCH_N(h->N,
                     qd_k_gs_structure<NN, VAL, (SMALL ? 16 : 4)><<<dim3(batches), dim3(64 * (SMALL ? 16 : 4)), 0, s>>>(env_ids, base + off,
-                        rec0 + off, g, h->R, b.params, ln.recs.p, b.state, b.noise_flags, ln.slabs.p, ln.gtiles.p, tilelist, h->gs_batches,
+                        rec0 + off, g, b.R, b.params, ln.recs.p, b.state, b.noise_flags, ln.slabs.p, ln.gtiles.p, tilelist, h->gs_batches,
                         h->kept, (h->cfg.flags & QD_FLAG_GS_GERSHGORIN_ZERO) ? 1 : 0))));
             }
             QD_HIP(hipGetLastError());
@@ -616,7 +630,7 @@ static int qd_launch_ground(const qd_handle* h, const QdEnvBufs& b, const QdLane
                         b.params, ln.recs.p, b.zraw, b.occ, b.state, b.noise_flags, b.eig, h->ftab.p, ln.slabs.p, wide))));
             } else {
                 QD_DISPATCH_BOOL(val, VAL, QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
-                    qd_k_gs_select<NN, VAL, KK><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids, base + off, rec0 + off, g, h->R,
+                    qd_k_gs_select<NN, VAL, KK><<<dim3(batches), dim3(QD_GS_BLOCK), 0, s>>>(env_ids, base + off, rec0 + off, g, b.R,
                         b.params, ln.recs.p, b.zraw, b.occ, b.state, b.noise_flags, b.eig, ln.slabs.p))));
             }
             QD_HIP(hipGetLastError());
@@ -646,9 +660,10 @@ static int qd_sorted_records(const qd_handle* h) { return (qd_validate(h) || h->
 static int qd_launch_candidates(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, const int32_t* env_ids, int base, int cnt,
                                 hipStream_t s, bool tiled) {
     const size_t shm = (size_t)h->kc * QD_CAND_BLOCK * (sizeof(double) + sizeof(uint16_t));
-    const dim3 grid(qd_cand_blocks(h->R), b.channels, cnt);
+    if (b.front == QD_FRONT_LINE && !tiled) return qd_fail(h, QD_ERR_STATE, "a line's records have no front end inside the search");
+    const dim3 grid(qd_cand_blocks(b.R), b.channels, cnt);
     QD_DISPATCH_FRONT(b.front, QD_DISPATCH_BOOL(tiled, TILED, QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
-        qd_k_candidates<NN, TILED, KK, FE><<<grid, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, h->R, b.params, b.state, ln.recs.p,
+        qd_k_candidates<NN, TILED, KK, FE><<<grid, dim3(QD_CAND_BLOCK), shm, s>>>(env_ids, base, b.R, b.params, b.state, ln.recs.p,
                                                                                   qd_sorted_records(h), b.noise_flags)))));
     QD_HIP(hipGetLastError());
     return QD_OK;
@@ -661,9 +676,9 @@ static int qd_launch_csd(const qd_handle* h, const QdEnvBufs& b, const QdLane& l
                          hipStream_t s, int st) {
     st &= qd_stages(h);
     if (st & QD_ST_TILE) {
-        const int tiles = ((h->R + 7) / 8) * ((h->R + 7) / 8);
+        const int tiles = ((b.R + 7) / 8) * ((b.R + 7) / 8);
         QD_DISPATCH_FRONT(b.front, QD_DISPATCH_TILE(h->N, QD_DISPATCH_KC(h->kc,
-            qd_k_tile<NN, KK, FE><<<dim3(tiles, b.channels, cnt), dim3(64), 0, s>>>(env_ids, base, h->R, b.params, b.state, ln.recs.p,
+            qd_k_tile<NN, KK, FE><<<dim3(tiles, b.channels, cnt), dim3(64), 0, s>>>(env_ids, base, b.R, b.params, b.state, ln.recs.p,
                                                                                     qd_sorted_records(h), b.noise_flags, h->tstats.p))));
         QD_HIP(hipGetLastError());
     }
@@ -675,9 +690,9 @@ static int qd_launch_csd(const qd_handle* h, const QdEnvBufs& b, const QdLane& l
 
 // a16 on the signal of `n` envs (their list `ids`, or 0..n-1), in place
 static int qd_launch_sensor(const qd_handle* h, const QdEnvBufs& b, const int32_t* ids, int n, hipStream_t s) {
-    const dim3 g3((h->P + 255) / 256, b.channels, n);
+    const dim3 g3((b.P + 255) / 256, b.channels, n);
     QD_DISPATCH_BOOL(b.channels == 1, ONE, QD_DISPATCH_N(h->N,
-        qd_k_sensor<NN, (ONE ? 1 : NN - 1)><<<g3, dim3(256), 0, s>>>(ids, h->R, b.params, b.state, b.zraw, qd_noise_cfg(h, b))));
+        qd_k_sensor<NN, (ONE ? 1 : NN - 1)><<<g3, dim3(256), 0, s>>>(ids, b.R, b.params, b.state, b.zraw, qd_noise_cfg(h, b))));
     QD_HIP(hipGetLastError());
     return QD_OK;
 }
@@ -815,9 +830,9 @@ static int qd_run_queries(qd_handle* h, QdScratchSet& set, int channels, QdFront
                           Gather gather, Write write) {
     const bool want_occ = (o.noise_flags & QD_NOISE_LATCH) || o.occ, want_tel = (o.noise_flags & QD_NOISE_SENSOR) != 0;
     const int pc = h->chunk;                                  // queries in flight = envs per launch chunk (lane 0's scratch)
-    const size_t CP = (size_t)channels * h->P;
+    const size_t CP = (size_t)channels * h->P;                // (slots of the handle's own image size: b.R, b.P below)
     QD_HIP(set.reserve(h->L, CP, (size_t)pc, 2, want_occ ? CP * h->N : 0, want_tel ? (size_t)channels * h->tel_words : 0));
-    QdEnvBufs b = set.view(channels, front);
+    QdEnvBufs b = set.view(channels, h->R, front);
     b.occ = want_occ ? set.occ.p : nullptr;
     b.noise_flags = o.noise_flags;
     if (want_tel) { b.tel = set.tel.p; b.tel_words = h->tel_words; }
@@ -829,7 +844,7 @@ static int qd_run_queries(qd_handle* h, QdScratchSet& set, int channels, QdFront
         QD_HIP(hipGetLastError());
         if (want_tel) {
             const int nt = cnt * channels;
-            qd_k_telegraph<<<dim3((nt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, channels, h->P, h->L.size, h->L.noise, b.params, b.tel,
+            qd_k_telegraph<<<dim3((nt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, channels, b.P, h->L.size, h->L.noise, b.params, b.tel,
                                                                      qd_noise_cfg(h, b));
             QD_HIP(hipGetLastError());
         }
@@ -842,16 +857,16 @@ static int qd_run_queries(qd_handle* h, QdScratchSet& set, int channels, QdFront
             } else
 #endif
             {
-                const long rows = (long)cnt * channels * h->R;
+                const long rows = (long)cnt * channels * b.R;
                 const dim3 grid((unsigned)((rows + QD_LATCH_ROWS_BLOCK - 1) / QD_LATCH_ROWS_BLOCK));
                 QD_DISPATCH_BOOL(channels == 1, ONE, QD_DISPATCH_N(h->N,
-                    qd_k_latch_rows<NN, (ONE ? 1 : NN - 1)><<<grid, dim3(QD_LATCH_ROWS_BLOCK), 0, s>>>(cnt, h->R, b.params, b.state, b.occ,
+                    qd_k_latch_rows<NN, (ONE ? 1 : NN - 1)><<<grid, dim3(QD_LATCH_ROWS_BLOCK), 0, s>>>(cnt, b.R, b.params, b.state, b.occ,
                                                                                                        b.zraw, qd_noise_cfg(h, b))));
             }
             QD_HIP(hipGetLastError());
         }
         if (int rc = qd_launch_sensor(h, b, nullptr, cnt, s)) return rc;
-        qd_launch_percentile(nullptr, (unsigned)cnt, (long)channels * h->P, b.zraw, b.plohi, s);
+        qd_launch_percentile(nullptr, (unsigned)cnt, (long)channels * b.P, b.zraw, b.plohi, s);
         QD_HIP(hipGetLastError());
         write(base, cnt, b);
         QD_HIP(hipGetLastError());
@@ -984,6 +999,100 @@ extern "C" int qd_scan_affine(qd_handle* h, const int32_t* env_of_query, int nq,
         });
 }
 
+// slots in flight of qd_scan1d for lines of n points: what lane 0's record buffer (chunk * C * P records) and its slabs
+// (gs_batches) hold in slots of the line's own size, at most QD_LINE_SLOTS.  With n <= P both hold one slot at the least.
+static int qd_line_slots(const qd_handle* h, int n) {
+    const int side = qd_line_side(n);
+    const size_t sp = (size_t)side * side;
+    size_t slots = (size_t)h->chunk * h->C * h->P / sp;
+    const size_t by_slabs = h->gs_batches / (size_t)qd_line_batches(n, h->ppb);
+    if (by_slabs < slots) slots = by_slabs;
+    return (int)(slots < QD_LINE_MAX_SLOTS ? slots : QD_LINE_MAX_SLOTS);
+}
+
+extern "C" int qd_scan1d(qd_handle* h, const int32_t* env_of_query, int nq, int n_points, const double* dir, const double* range,
+                         const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst, float* image_dst,
+                         double* plohi_dst, const qd_scan1d_opts* opts, void* stream) {
+    static_assert(QD_LINE_MAX_SLOTS == QD_LINE_SLOTS, "qdsim.h states the bound");
+    if (!h) return QD_ERR_ARG;
+    if (nq < 0) return qd_fail(h, QD_ERR_ARG, "qd_scan1d: nq < 0");
+    if (!env_of_query || !dir || !range) return qd_fail(h, QD_ERR_ARG, "qd_scan1d: env_of_query_dev, dir_dev or range_dev is NULL");
+    if (!gate_v || !barrier_v) return qd_fail(h, QD_ERR_ARG, "qd_scan1d: gate_v_dev or barrier_v_dev is NULL");
+    if (n_points < 1 || n_points > h->P) return qd_fail(h, QD_ERR_ARG, "qd_scan1d: n_points must be in 1..P (P = resolution^2 of the handle)");
+    if (opts && opts->struct_size != (int32_t)sizeof(qd_scan1d_opts))
+        return qd_fail(h, QD_ERR_ARG, "qd_scan1d: opts->struct_size is not sizeof(qd_scan1d_opts)");
+    if (opts && opts->frame != QD_SCAN_VIRTUAL && opts->frame != QD_SCAN_PHYSICAL)
+        return qd_fail(h, QD_ERR_ARG, "qd_scan1d: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL");
+    if (opts && opts->frame == QD_SCAN_PHYSICAL && opts->vgm_dev)
+        return qd_fail(h, QD_ERR_ARG, "qd_scan1d: vgm_dev has no meaning in the physical frame");
+    if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_LATCH)))
+        return qd_fail(h, QD_ERR_ARG, "qd_scan1d: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
+                                      "centred on the env's own adjacent-pair observation)");
+    if (h->cfg.flags & QD_FLAG_VALIDATE)
+        return qd_fail(h, QD_ERR_STATE, "qd_scan1d: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
+                                        "B envs' last observe and renders no lines; use a handle without the flag");
+    if (h->full_m)
+        return qd_fail(h, QD_ERR_STATE, "qd_scan1d: the full charge-state space synthesises its own voltages "
+                                        "(qd_k_full_structure); a line front end for it is not built");
+    if (nq == 0) return QD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    QD_ON_DEVICE(h);
+    const int noise_flags = opts ? opts->noise_flags : 0;
+    const unsigned long long serial = opts ? opts->serial : 0;
+    const long long stream_base = opts ? opts->stream_base : 0;
+    double* const occ_dst = opts ? opts->occ_dst : nullptr;
+    const bool want_occ = (noise_flags & QD_NOISE_LATCH) || occ_dst, want_tel = (noise_flags & QD_NOISE_SENSOR) != 0;
+    const QdLineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, opts ? opts->vgm_dev : nullptr,
+                        opts ? opts->gamma_dev : nullptr, opts ? opts->frame : QD_SCAN_VIRTUAL};
+    // the slot of a line: side x side records, record p = point p, the tail inert
+    const int n = n_points, side = qd_line_side(n), SP = side * side, tel_words = (SP + 63) / 64;
+    const int cap = qd_line_slots(h, n), pc = nq < cap ? nq : cap;
+    QD_HIP(h->line.reserve(h->L, (size_t)SP, (size_t)pc, 2, want_occ ? (size_t)SP * h->N : 0, want_tel ? (size_t)tel_words : 0));
+    QD_HIP(h->line_axes.reserve((size_t)pc));
+    QD_HIP(h->line_dense.reserve((size_t)pc * n));
+    QdEnvBufs b = h->line.view(1, side, QD_FRONT_LINE);
+    b.occ = want_occ ? h->line.occ.p : nullptr;
+    b.noise_flags = noise_flags;
+    if (want_tel) { b.tel = h->line.tel.p; b.tel_words = tel_words; }
+    b.serial = serial;
+    const QdLane& ln = h->lanes[0];
+    QdLineAxes* const axes = h->line_axes.p;
+    double* const dense = h->line_dense.p;
+    // per launch, the stages of an observation in qd_observe's order on the slots alone; nothing of the envs is written
+    for (int base = 0; base < nq; base += pc) {
+        const int cnt = nq - base < pc ? nq - base : pc;
+        b.env_off = (uint32_t)(stream_base + base);          // slot k of the launch draws as global env stream_base + base + k
+        qd_k_line_gather<<<dim3(cnt), dim3(QD_LINE_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, b.params, b.state, axes);
+        QD_HIP(hipGetLastError());
+        if (want_tel) {
+            // (a chain of SP states per slot; the sensor stage reads the first n bits)
+            qd_k_telegraph<<<dim3((cnt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, 1, SP, h->L.size, h->L.noise, b.params, b.tel,
+                                                                      qd_noise_cfg(h, b));
+            QD_HIP(hipGetLastError());
+        }
+        QD_DISPATCH_N(h->N, qd_k_line_front<NN><<<dim3((SP + QD_LINE_BLOCK - 1) / QD_LINE_BLOCK, cnt), dim3(QD_LINE_BLOCK), 0, s>>>(
+                                n, SP, b.params, b.state, axes, ln.recs.p));
+        QD_HIP(hipGetLastError());
+        if (int rc = qd_launch_candidates(h, b, ln, nullptr, 0, cnt, s, true)) return rc;
+        if (int rc = qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND)) return rc;
+        if (noise_flags & QD_NOISE_LATCH) {
+            QD_DISPATCH_N(h->N, qd_k_latch_lines<NN><<<dim3((cnt + 63) / 64), dim3(64), 0, s>>>(cnt, n, SP, b.params, b.occ, b.zraw,
+                                                                                              qd_noise_cfg(h, b)));
+            QD_HIP(hipGetLastError());
+        }
+        if (int rc = qd_launch_sensor(h, b, nullptr, cnt, s)) return rc;
+        qd_k_line_pack<<<dim3((n + 255) / 256, cnt), dim3(256), 0, s>>>(n, SP, b.zraw, dense);
+        qd_launch_percentile(nullptr, (unsigned)cnt, (long)n, dense, b.plohi, s);
+        QD_HIP(hipGetLastError());
+        if (raw_dst || image_dst || plohi_dst || occ_dst) {
+            qd_k_line_write<<<dim3((n + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, n, SP, dense, b.plohi, b.occ, raw_dst,
+                                                                             image_dst, plohi_dst, occ_dst);
+            QD_HIP(hipGetLastError());
+        }
+    }
+    return QD_OK;
+}
+
 // slots in flight of qd_eval_points: one launch chunk of lane 0's records, at most QD_POINTS_SLOTS
 static int qd_points_slots(const qd_handle* h) { return h->chunk < QD_POINTS_MAX_SLOTS ? h->chunk : QD_POINTS_MAX_SLOTS; }
 
@@ -1012,7 +1121,7 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
     const long long CP = (long long)h->C * h->P;
     QD_HIP(h->points.reserve(h->L, (size_t)CP, (size_t)ps, 0, (size_t)CP * h->N));
     // the ground-state launcher runs on the point buffers, without noise or eigenvalues; nothing of the envs is written
-    const QdEnvBufs qb = h->points.view(h->C);
+    const QdEnvBufs qb = h->points.view(h->C, h->R);
     const QdLane& ln = h->lanes[0];
     QdPointSlots T;
     memset(&T, 0, sizeof(T));

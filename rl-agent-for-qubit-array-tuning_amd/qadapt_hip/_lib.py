@@ -18,6 +18,7 @@ QD_NOISE_RADIAL = 2
 QD_NOISE_LATCH = 4
 QD_MAP_GLOBAL, QD_MAP_PER_SCAN = 0, 1
 QD_POINTS_SLOTS = 64
+QD_LINE_SLOTS = 4096
 QD_SCAN_VIRTUAL, QD_SCAN_PHYSICAL = 0, 1
 QD_ERR_ARG, QD_ERR_HIP, QD_ERR_STATE = 1, 2, 3
 
@@ -30,7 +31,7 @@ EXPORTS = [
     "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex", "qd_scan_affine",
 ]
 # exported too, kept apart: names with a digit, which a scan of qdsim.h for `qd_[a-z_]+(` does not find
-EXPORTS_WITH_DIGITS = ["qd_scan2d"]
+EXPORTS_WITH_DIGITS = ["qd_scan2d", "qd_scan1d"]
 
 QD_CURVES = {"constant": 0, "polynomial": 1, "exponential": 2, "linear": 3}
 QD_UPDATE_KALMAN, QD_UPDATE_DIRECT = 0, 1
@@ -75,6 +76,11 @@ class QdScanOpts(ctypes.Structure):
 
 class QdScanAffineOpts(ctypes.Structure):
     """qd_scan_affine_opts of include/qdsim.h: the fields of qd_scan_opts for a qd_scan_affine call."""
+    _fields_ = list(QdScanOpts._fields_)
+
+
+class QdScan1dOpts(ctypes.Structure):
+    """qd_scan1d_opts of include/qdsim.h: the fields of qd_scan_opts for a qd_scan1d call (occ_dst is [nq][n][N])."""
     _fields_ = list(QdScanOpts._fields_)
 
 
@@ -157,6 +163,8 @@ def lib():
     L.qd_scan2d.restype = ctypes.c_int
     L.qd_scan_affine.argtypes = [vp, vp, ctypes.c_int, dp, dp, dp, dp, dp, dp, fp, dp, ctypes.POINTER(QdScanAffineOpts), vp]
     L.qd_scan_affine.restype = ctypes.c_int
+    L.qd_scan1d.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, dp, fp, dp, ctypes.POINTER(QdScan1dOpts), vp]
+    L.qd_scan1d.restype = ctypes.c_int
     _LIB = L
     return L
 

@@ -56,6 +56,38 @@ class ModelFacade:
         """n_open (..., N) float64."""
         return self._points(vg, vb, ("occupations",))[1]
 
+    def do1d_open(self, gate, min, max, points):
+        """The reference's `do1d_open(gate, min, max, points)` (TunnelCoupledChargeSensed.py:192-205 over
+        GateVoltageComposer.do1d): a noise-free sweep of `points` points of one gate over [min, max] on the env's current
+        device, every other gate, the sensor gate and the barriers at 0 -- the base point is zero, as the composer builds it.
+        Returns (signal (points, 1), n_open (points, N)) float64, as charge_sensor_open does.  `gate` follows the composer's
+        grammar: an int g or "P{g}" (1-indexed; g = N+1 is the sensor gate) sweeps that PHYSICAL gate; "vP{i}", "e{i}_{j}"
+        (v_i - v_j) and "U{i}_{j}" ((v_i + v_j) / sqrt(2)) sweep in the VIRTUAL frame through the env's current virtual gate
+        matrix.  The composer's grid carries the virtual gate origin once on a "vP" sweep, sqrt(2) times on a "U" sweep, and
+        never on an "e" or a physical sweep (each _do1d_virtual term brings it along).  The facade renders through the
+        backend's scan1d, whose virtual frame adds the origin exactly ONCE: "vP", "P" and int sweeps are the composer's grid,
+        an "e" sweep sits one origin above it and a "U" sweep sqrt(2) - 1 origins below it; with a zero origin all agree."""
+        N = self.n_dot
+        if isinstance(gate, (int, np.integer)) and not isinstance(gate, bool):
+            g = int(gate)
+            if not 1 <= g <= N + 1:
+                raise ValueError(f"gate must be in the range 1 to {N + 1}")
+            axis, frame = g - 1, "physical"
+        elif isinstance(gate, str) and gate[:1] == "P" and gate[1:].isdigit():
+            g = int(gate[1:])
+            if not 1 <= g <= N + 1:
+                raise ValueError(f"{gate!r}: P1..P{N + 1} exist for {N} dots (P{N + 1} is the sensor gate)")
+            axis, frame = g - 1, "physical"
+        elif isinstance(gate, str) and (gate[:2] == "vP" or gate[:1] in ("e", "U")):
+            axis, frame = gate, "virtual"
+        else:
+            raise ValueError(f"Invalid gate {gate!r} must be in the form P[int], vP[int], e[int]_[int], U[int]_[int]")
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        out = self._b.scan1d([0], axis, (float(min), float(max)), int(points), np.zeros((1, N)), np.zeros((1, N - 1)), 0.0,
+                             frame=frame, gamma=gamma, occupations=True)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return (host(out["raw"]).astype(np.float64)[0][:, None], host(out["occupations"]).astype(np.float64)[0])
+
 
 class ArrayFacade:
     """`env.array` of the reference (a QarrayBaseClass) as far as its users outside step() need it: `model.cgd_full`,
@@ -141,6 +173,16 @@ class ArrayFacade:
         out = self._b.scan_affine([0], x, y, x_range, y_range, np.asarray(gate_voltages, np.float64)[None, :],
                                   np.asarray(barrier_voltages, np.float64)[None, :],
                                   sensor_voltage=None if sensor_voltage is None else float(sensor_voltage), **kw)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return {k: host(v)[0] for k, v in out.items()}
+
+    def scan1d(self, axis, s_range, n_points, gate_voltages, barrier_voltages, sensor_voltage=None, **kw):
+        """The backend's scan1d for this env (a dense sweep of n_points points along a control, "e1_2", "U1_2", a {control:
+        coefficient} dict or a (2N,) vector): one query, numpy results without the query axis ("raw" (n,), "image" (n,),
+        "plohi" (2,), "occupations" (n, N))."""
+        out = self._b.scan1d([0], axis, s_range, n_points, np.asarray(gate_voltages, np.float64)[None, :],
+                             np.asarray(barrier_voltages, np.float64)[None, :],
+                             sensor_voltage=None if sensor_voltage is None else float(sensor_voltage), **kw)
         host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
         return {k: host(v)[0] for k, v in out.items()}
 

@@ -401,15 +401,17 @@ class VecQuantumDeviceEnv:
                 self._to_dev(arr(barrier_voltages, np.float64).reshape(-1, C), torch.float64, (nq, C)),
                 None if sensor_voltage is None else self._to_dev(sensor_voltage, torch.float64, (nq,)))
 
-    def _query_outputs(self, nq, channels, normalised, occupations):
-        """The result tensors of nq queries of `channels` = (C,) or () channel images each."""
-        R, f64 = self.R, {"dtype": torch.float64, "device": self.device}
-        out = {"raw": torch.empty((nq, *channels, R, R), **f64)}
+    def _query_outputs(self, nq, channels, normalised, occupations, shape=None):
+        """The result tensors of nq queries of `channels` = (C,) or () channel images each; `shape`: what one image is, (R, R)
+        unless given ((n,) for the lines of scan1d)."""
+        f64 = {"dtype": torch.float64, "device": self.device}
+        shape = (self.R, self.R) if shape is None else tuple(shape)
+        out = {"raw": torch.empty((nq, *channels, *shape), **f64)}
         if normalised:
-            out["image"] = torch.empty((nq, R, R, *channels), dtype=torch.float32, device=self.device)
+            out["image"] = torch.empty((nq, *shape, *channels), dtype=torch.float32, device=self.device)
             out["plohi"] = torch.empty((nq, 2), **f64)
         if occupations:
-            out["occupations"] = torch.empty((nq, *channels, R, R, self.N), **f64)
+            out["occupations"] = torch.empty((nq, *channels, *shape, self.N), **f64)
         return out
 
     def _query_serial(self, serial, flags):
@@ -585,6 +587,61 @@ class VecQuantumDeviceEnv:
         rc = self._lib.qd_scan_affine(self._h, _ptr(ids), nq, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv), _ptr(out["raw"]),
                                       _ptr(out.get("image")), _ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
         _lib.check(self._h, rc, "qd_scan_affine")
+        return out
+
+    def scan1d(self, env_ids, axis, s_range, n_points, gate_voltages, barrier_voltages, sensor_voltage=None, *,
+               frame="virtual", vgm=None, gamma=None, noise=(), serial=None, stream_base=None, occupations=False):
+        """Stateless dense 1-D sweeps along one control or direction vector (qd_scan1d): the reference model layer's
+        `do1d_open(gate, min, max, points)` over `GateVoltageComposer.do1d`, for nq queries in one call, each on the device of
+        env `env_ids[q]`.  With W0 = [gate_voltages, sensor_voltage, barrier_voltages] of the query, point t sits at
+        W0 + linspace(*s_range, n_points)[t] * d.  A line runs in a slot of its own size (ceil(sqrt(n))^2 records), not in one
+        of an image.  Nothing of the episodes changes.
+          axis              the direction d, one for all queries or one per query (scan_axis_vector, scan_axis_vectors): a
+                            control index or name, "e{i}_{j}", "U{i}_{j}", a {control: coefficient} dict, a (2N,) vector, or
+                            (nq, 2N).  The zero vector repeats the base point.  Coefficients are not checked for NaN or infinity
+          s_range           (lo, hi) of the scalar that multiplies d, for all queries or (nq, 2); lo > hi sweeps downwards,
+                            lo == hi repeats a point
+          n_points          points per line, 1 .. R*R of this env, the same for all queries of a call
+          gate_voltages, barrier_voltages, sensor_voltage   the BASE POINT, as in scan_affine
+          frame, vgm, serial, stream_base   as in scan2d
+          gamma             None (each env's constant coulomb_peak_width), a scalar or (nq,) peak widths
+          noise             () / None / False: deterministic.  True: the sensor and latching stages this env was created with.
+                            Or an iterable of {"sensor", "latch"}.  Latching walks the line as ONE row: the held state starts
+                            at point 0 and is never reset; the telegraph chain starts at point 0
+          occupations       True adds the occupations the signal was formed from (after latching, if it ran)
+        Returns device tensors {"raw": (nq, n) float64, "image": (nq, n) float32 normalised per line with its own 0.5 / 99.5
+        percentiles, "plohi": (nq, 2)}, plus, with occupations=True, {"occupations": (nq, n, N) float64}."""
+        N = self.N
+        if frame not in ("virtual", "physical"):
+            raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
+        if vgm is not None and frame == "physical":
+            raise ValueError("vgm has no meaning in the physical frame")
+        n = int(n_points)
+        if not 1 <= n <= self.R * self.R:
+            raise ValueError(f"n_points must be in 1..{self.R * self.R} (R*R of this env), got {n_points}")
+        nq, ids, gv, bv, sv = self._query_inputs(env_ids, gate_voltages, barrier_voltages, sensor_voltage)
+        dirs = scan_axis_vectors(axis, N, frame, nq)
+        rng = np.array(np.broadcast_to(np.asarray(s_range, np.float64), (nq, 2)))
+        if noise is True:
+            flags = self.noise_flags & ~_lib.QD_NOISE_RADIAL
+        else:
+            if noise and "radial" in tuple(noise):
+                raise ValueError("radial noise is centred on the env's own adjacent-pair observation: not defined for lines")
+            flags = self._noise_flags(noise)
+        dr = self._to_dev(dirs, torch.float64, (nq, 2 * N))
+        rg = self._to_dev(rng, torch.float64, (nq, 2))
+        vm = None if vgm is None else self._to_dev(vgm, torch.float64, (nq, N + 1, N + 1))
+        gm = None if gamma is None else self._to_dev(gamma, torch.float64, (nq,))
+        out = self._query_outputs(nq, (), True, occupations, shape=(n,))
+        addr = lambda t: None if t is None else t.data_ptr()                    # noqa: E731
+        opts = _lib.QdScan1dOpts(struct_size=ctypes.sizeof(_lib.QdScan1dOpts),
+                                 frame=_lib.QD_SCAN_PHYSICAL if frame == "physical" else _lib.QD_SCAN_VIRTUAL,
+                                 noise_flags=int(flags), reserved=0, serial=self._query_serial(serial, flags),
+                                 stream_base=int(self.env_id_offset if stream_base is None else stream_base),
+                                 vgm_dev=addr(vm), gamma_dev=addr(gm), occ_dst=addr(out.get("occupations")))
+        rc = self._lib.qd_scan1d(self._h, _ptr(ids), nq, n, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv), _ptr(out["raw"]),
+                                 _ptr(out["image"]), _ptr(out["plohi"]), ctypes.byref(opts), self._stream())
+        _lib.check(self._h, rc, "qd_scan1d")
         return out
 
     # ------------------------------------------------------------------ point evaluation
