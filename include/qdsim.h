@@ -353,8 +353,8 @@ int qd_eval_points(qd_handle* h, const int32_t* group_env_host, const int64_t* g
  * nq < 0, a struct_size that is not sizeof(qd_scan_opts), an unknown frame, vgm_dev with the physical frame, a noise bit
  * outside SENSOR | LATCH.  Axes arrive on the device: an axis outside [0, 2N), ax == ay or an env id outside [0, B) makes
  * the query inert, its destination slots are left untouched.  QD_ERR_STATE: QD_FLAG_VALIDATE handles and handles in the
- * full charge-state space, as qd_eval_points refuses them.  Radial noise, more than two swept controls and Rx != Ry are
- * not built. */
+ * full charge-state space, as qd_eval_points refuses them.  Radial noise and more than two swept controls are not
+ * built; Rx != Ry is qd_scan_grid's (without the tile search). */
 #define QD_SCAN_VIRTUAL 0
 #define QD_SCAN_PHYSICAL 1
 typedef struct qd_scan_opts {
@@ -407,8 +407,8 @@ int qd_scan2d(qd_handle* h, const int32_t* env_of_query_dev, int nq, const int32
  * nq < 0, a struct_size that is not sizeof(qd_scan_affine_opts), an unknown frame, vgm_dev with the physical frame, a noise
  * bit outside SENSOR | LATCH (the radial stage is centred on the env's own adjacent-pair observation).  An env id outside
  * [0, B) makes the query inert, its destination slots are left untouched.  QD_ERR_STATE: QD_FLAG_VALIDATE handles and
- * handles in the full charge-state space, as qd_scan2d refuses them.  Radial noise, more than two axes and Rx != Ry are
- * not built. */
+ * handles in the full charge-state space, as qd_scan2d refuses them.  Radial noise and more than two axes are not built;
+ * Rx != Ry is qd_scan_grid's (without the tile search). */
 typedef struct qd_scan_affine_opts {
     int32_t  struct_size;   /* = sizeof(qd_scan_affine_opts) */
     int32_t  frame;         /* QD_SCAN_VIRTUAL 0 / QD_SCAN_PHYSICAL 1 */
@@ -488,6 +488,76 @@ typedef struct qd_scan1d_opts {
 int qd_scan1d(qd_handle* h, const int32_t* env_of_query_dev, int nq, int n_points, const double* dir_dev,
               const double* range_dev, const double* gate_v_dev, const double* barrier_v_dev, const double* sensor_v_dev,
               double* raw_dst, float* image_dst, double* plohi_dst, const qd_scan1d_opts* opts, void* stream);
+
+/* Stateless 2-D scans on any nx x ny GRID of points along two DIRECTION VECTORS over the 2N controls: the reference model
+ * layer's do2d_open(x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points) over GateVoltageComposer.do2d
+ * (GateVoltageComposer.py:224-255), which takes the two point counts from the caller -- a detuning axis at 128 points
+ * against a barrier at 16, a coarse 24 x 24 preview on a 64 x 64 handle, a thin band around a transition -- nq grids in one
+ * call, at the cost of their point count, with the measurement stages of a step (sensor noise, latching along every row)
+ * and one normalisation per grid.  A grid sent through qd_eval_points is deterministic only, is not normalised and takes a
+ * whole slot of C*P records per group.
+ * Controls are indexed as in qd_scan2d.  With W0[2N] = [gate_v, sensor_v, barrier_v] of the query (the BASE POINT, as in
+ * qd_scan_affine), sx = linspace(x_lo, x_hi, nx)[x] and sy = linspace(y_lo, y_hi, ny)[y], point (row y, column x) has
+ *   W[i] = fma(sy, dy[i], fma(sx, dx[i], W0[i]))      i = 0..2N-1
+ * and the model sees W through the frame as in qd_scan2d.  The front end (csrc/qd_grid.h qd_grid_voltages) performs the
+ * operations of qd_scan_affine's in the same order.  Held bit for bit:
+ *   1. nx = ny = R of the handle: raw, occupations, percentiles and image equal qd_scan_affine with the same arguments on a
+ *      QD_FLAG_PIXEL_SEARCH handle, with noise too under the same serial and stream_base (Rl = R: point indices, telegraph
+ *      chain and row walks coincide).
+ *   2. ny = 1, dy = 0: every output equals qd_scan1d with n_points = nx, d = dx, [lo, hi] = [x_lo, x_hi], noise included.
+ *   3. raw equals qd_eval_points at the points' voltages on any handle; occ_dst equals it under the conditions qd_scan1d
+ *      documents.
+ *   env_of_query_dev [nq]          int32, the env whose device renders query q
+ *   nx, ny                         columns and rows, nx >= 1, ny >= 1, nx*ny <= P of the handle, the same for all queries
+ *   dir_dev          [nq][2][2N]   dx then dy of query q, as qd_scan_affine.  Zero vectors are legal
+ *   range_dev        [nq][4]       x_lo, x_hi, y_lo, y_hi; lo > hi sweeps downwards, lo == hi repeats a point
+ *   gate_v_dev       [nq][N], barrier_v_dev [nq][N-1], sensor_v_dev [nq] or NULL (0.0): the base point
+ *   raw_dst          [nq][ny][nx]  float64 unnormalised signal; may be NULL
+ *   image_dst        [nq][ny][nx]  float32, normalised with ONE 0.5 / 99.5 percentile pair per grid (all zero for a
+ *                                  constant grid); may be NULL
+ *   plohi_dst        [nq][2]       those percentiles; may be NULL
+ * opts (NULL: virtual frame, deterministic): the fields of qd_scan_affine_opts in the same order with the same meaning, except
+ *   occ_dst       [nq][ny][nx][N] float64 or NULL: the occupations the signal was formed from (after latching, if it ran)
+ *   noise_flags   QD_NOISE_LATCH: the held state is reset at every row start; row y is walked as qd_latch_row on the nx
+ *                 points from y*nx, the Philox counter of a point is y*nx + x.  QD_NOISE_SENSOR: the telegraph chain runs
+ *                 over the slot's Rl*Rl states from point 0, as a line's; white noise is keyed by the point index
+ *                 p = y*nx + x; the channel word is 0.  QD_NOISE_RADIAL is QD_ERR_ARG
+ *   gamma_dev     [nq] or NULL: the env's constant peak width (the width is constant, as in qd_scan_affine)
+ * A query occupies one slot of its OWN size: Rl x Rl records with Rl = ceil(sqrt(nx*ny)), record p = y*nx + x, the
+ * Rl*Rl - nx*ny tail records inert, as in a line's slot.  Per launch: gather, telegraph chain, the grid front kernel, the
+ * redo instantiation of the per-pixel search, the ground-state kernels, the latching walk (one lane per slot and row), the
+ * sensor stage, the pack of the nx*ny leading values into a dense row, the percentile kernel, the write -- the kernels of a
+ * step with the slot geometry as data, qd_scan1d's pack, and four small kernels of the grid's own (csrc/qd_grid.h).  The tile
+ * search does not run: its tiles are cut from R x R images.  Slots in flight per launch: those of a line of nx*ny points, at
+ * most QD_GRID_SLOTS.  Stream-ordered with no host wait after the first call.  The scratch is qd_scan1d's (a call of either
+ * grows it for both; hipFree waits for the device) and one descriptor per slot in flight of 4 + 4*8 doubles, the two
+ * counts and the frame, 304 bytes, allocated by the first call, grown by a later one with more slots, freed by qd_destroy.
+ * Calls of qd_scan_grid belong on the stream qd_scan2d, qd_scan_affine and qd_scan1d use on that handle: it shares its
+ * buffers with qd_scan1d and lane 0's records with all of them.  nq may exceed B, many queries may name one env, and results
+ * do not depend on how queries fall into launches.  The call changes nothing that qd_step, qd_observe, qd_probe*, qd_scan2d,
+ * qd_scan_affine, qd_scan1d, qd_eval_points or any qd_get_* function can see.
+ * QD_ERR_ARG, found without reading the device and before the state of the handle is looked at: NULL env_of_query_dev,
+ * dir_dev, range_dev, gate_v_dev or barrier_v_dev, nq < 0, nx < 1, ny < 1 or nx*ny > P, a struct_size that is not
+ * sizeof(qd_scan_grid_opts), an unknown frame, vgm_dev with the physical frame, a noise bit outside SENSOR | LATCH.  An env id
+ * outside [0, B) makes the query inert, its destination slots are left untouched.  QD_ERR_STATE: QD_FLAG_VALIDATE handles
+ * and handles in the full charge-state space, as qd_scan2d refuses them.  nq == 0 does nothing.
+ * Grids of more than P points, different shapes within one call, the tile search on a rectangular slot and radial noise
+ * are not built. */
+#define QD_GRID_SLOTS 4096
+typedef struct qd_scan_grid_opts {
+    int32_t  struct_size;   /* = sizeof(qd_scan_grid_opts) */
+    int32_t  frame;         /* QD_SCAN_VIRTUAL 0 / QD_SCAN_PHYSICAL 1 */
+    int32_t  noise_flags;   /* QD_NOISE_SENSOR | QD_NOISE_LATCH; 0 = none */
+    int32_t  reserved;
+    uint64_t serial;        /* the observation-number word of the Philox counter */
+    int64_t  stream_base;   /* query q draws from the streams of global env id stream_base + q (mod 2^32) */
+    const double* vgm_dev;  /* [nq][G][G] or NULL: the env's current matrix (virtual frame only) */
+    const double* gamma_dev;/* [nq] or NULL: the env's constant peak width */
+    double*  occ_dst;       /* [nq][ny][nx][N] or NULL */
+} qd_scan_grid_opts;
+int qd_scan_grid(qd_handle* h, const int32_t* env_of_query_dev, int nq, int nx, int ny, const double* dir_dev,
+                 const double* range_dev, const double* gate_v_dev, const double* barrier_v_dev, const double* sensor_v_dev,
+                 double* raw_dst, float* image_dst, double* plohi_dst, const qd_scan_grid_opts* opts, void* stream);
 
 /* Stitches one channel of nx*ny probe signals into one composite image on the device (map_device_range.py:134-170,
  * map_full_device_range.py:168-194).  raw_dev [nx*ny][C][P] as qd_probe wrote it, query index i*ny + j for scan (i, j);

@@ -15,6 +15,7 @@
 #include "qd_scan.h"
 #include "qd_affine.h"
 #include "qd_line.h"
+#include "qd_grid.h"
 #include "qd_scratch.h"
 
 // The owners of a stream and of an event.  With the two memory policies of qd_scratch.h these are the only places that
@@ -160,6 +161,8 @@ struct qd_handle {
     QdScratchSet line;
     QdDev<QdLineAxes> line_axes;
     QdDev<double> line_dense;
+    // grids (qd_scan_grid): the line buffers above and one descriptor per grid in flight
+    QdDev<QdGridAxes> grid_axes;
     mutable char err[512];                  // (the launchers take the handle const and still report through it)
 };
 
@@ -1086,6 +1089,92 @@ extern "C" int qd_scan1d(qd_handle* h, const int32_t* env_of_query, int nq, int 
         QD_HIP(hipGetLastError());
         if (raw_dst || image_dst || plohi_dst || occ_dst) {
             qd_k_line_write<<<dim3((n + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, n, SP, dense, b.plohi, b.occ, raw_dst,
+                                                                             image_dst, plohi_dst, occ_dst);
+            QD_HIP(hipGetLastError());
+        }
+    }
+    return QD_OK;
+}
+
+extern "C" int qd_scan_grid(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir, const double* range,
+                            const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst, float* image_dst,
+                            double* plohi_dst, const qd_scan_grid_opts* opts, void* stream) {
+    static_assert(QD_GRID_MAX_SLOTS == QD_GRID_SLOTS, "qdsim.h states the bound");
+    if (!h) return QD_ERR_ARG;
+    if (nq < 0) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: nq < 0");
+    if (!env_of_query || !dir || !range) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: env_of_query_dev, dir_dev or range_dev is NULL");
+    if (!gate_v || !barrier_v) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: gate_v_dev or barrier_v_dev is NULL");
+    if (nx < 1 || ny < 1 || (long long)nx * ny > h->P)
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: nx and ny must be >= 1 with nx*ny <= P (P = resolution^2 of the handle)");
+    if (opts && opts->struct_size != (int32_t)sizeof(qd_scan_grid_opts))
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: opts->struct_size is not sizeof(qd_scan_grid_opts)");
+    if (opts && opts->frame != QD_SCAN_VIRTUAL && opts->frame != QD_SCAN_PHYSICAL)
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL");
+    if (opts && opts->frame == QD_SCAN_PHYSICAL && opts->vgm_dev)
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: vgm_dev has no meaning in the physical frame");
+    if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_LATCH)))
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
+                                      "centred on the env's own adjacent-pair observation)");
+    if (h->cfg.flags & QD_FLAG_VALIDATE)
+        return qd_fail(h, QD_ERR_STATE, "qd_scan_grid: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
+                                        "B envs' last observe and renders no grids; use a handle without the flag");
+    if (h->full_m)
+        return qd_fail(h, QD_ERR_STATE, "qd_scan_grid: the full charge-state space synthesises its own voltages "
+                                        "(qd_k_full_structure); a grid front end for it is not built");
+    if (nq == 0) return QD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    QD_ON_DEVICE(h);
+    const int noise_flags = opts ? opts->noise_flags : 0;
+    const unsigned long long serial = opts ? opts->serial : 0;
+    const long long stream_base = opts ? opts->stream_base : 0;
+    double* const occ_dst = opts ? opts->occ_dst : nullptr;
+    const bool want_occ = (noise_flags & QD_NOISE_LATCH) || occ_dst, want_tel = (noise_flags & QD_NOISE_SENSOR) != 0;
+    const QdAffineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, opts ? opts->vgm_dev : nullptr,
+                          opts ? opts->gamma_dev : nullptr, opts ? opts->frame : QD_SCAN_VIRTUAL};
+    // the slot of a grid is that of a line of nx*ny points: side x side records, record p = y*nx + x, the tail inert
+    const int n = nx * ny, side = qd_line_side(n), SP = side * side, tel_words = (SP + 63) / 64;
+    const int cap = qd_line_slots(h, n), pc = nq < cap ? nq : cap;
+    QD_HIP(h->line.reserve(h->L, (size_t)SP, (size_t)pc, 2, want_occ ? (size_t)SP * h->N : 0, want_tel ? (size_t)tel_words : 0));
+    QD_HIP(h->grid_axes.reserve((size_t)pc));
+    QD_HIP(h->line_dense.reserve((size_t)pc * n));
+    QdEnvBufs b = h->line.view(1, side, QD_FRONT_LINE);
+    b.occ = want_occ ? h->line.occ.p : nullptr;
+    b.noise_flags = noise_flags;
+    if (want_tel) { b.tel = h->line.tel.p; b.tel_words = tel_words; }
+    b.serial = serial;
+    const QdLane& ln = h->lanes[0];
+    QdGridAxes* const axes = h->grid_axes.p;
+    double* const dense = h->line_dense.p;
+    // per launch, the stages of an observation in qd_observe's order on the slots alone; nothing of the envs is written
+    for (int base = 0; base < nq; base += pc) {
+        const int cnt = nq - base < pc ? nq - base : pc;
+        b.env_off = (uint32_t)(stream_base + base);          // slot k of the launch draws as global env stream_base + base + k
+        qd_k_grid_gather<<<dim3(cnt), dim3(QD_GRID_BLOCK), 0, s>>>(Q, base, h->B, h->N, nx, ny, h->params.p, h->state.p, b.params, b.state,
+                                                                   axes);
+        QD_HIP(hipGetLastError());
+        if (want_tel) {
+            // (a chain of SP states per slot; the sensor stage reads the first n bits)
+            qd_k_telegraph<<<dim3((cnt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, 1, SP, h->L.size, h->L.noise, b.params, b.tel,
+                                                                      qd_noise_cfg(h, b));
+            QD_HIP(hipGetLastError());
+        }
+        QD_DISPATCH_N(h->N, qd_k_grid_front<NN><<<dim3((SP + QD_GRID_BLOCK - 1) / QD_GRID_BLOCK, cnt), dim3(QD_GRID_BLOCK), 0, s>>>(
+                                SP, b.params, b.state, axes, ln.recs.p));
+        QD_HIP(hipGetLastError());
+        if (int rc = qd_launch_candidates(h, b, ln, nullptr, 0, cnt, s, true)) return rc;
+        if (int rc = qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND)) return rc;
+        if (noise_flags & QD_NOISE_LATCH) {
+            const long rows = (long)cnt * ny;
+            QD_DISPATCH_N(h->N, qd_k_latch_grid<NN><<<dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s>>>(cnt, nx, ny, SP, b.params, b.occ,
+                                                                                                          b.zraw, qd_noise_cfg(h, b)));
+            QD_HIP(hipGetLastError());
+        }
+        if (int rc = qd_launch_sensor(h, b, nullptr, cnt, s)) return rc;
+        qd_k_line_pack<<<dim3((n + 255) / 256, cnt), dim3(256), 0, s>>>(n, SP, b.zraw, dense);
+        qd_launch_percentile(nullptr, (unsigned)cnt, (long)n, dense, b.plohi, s);
+        QD_HIP(hipGetLastError());
+        if (raw_dst || image_dst || plohi_dst || occ_dst) {
+            qd_k_grid_write<<<dim3((n + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, n, SP, dense, b.plohi, b.occ, raw_dst,
                                                                              image_dst, plohi_dst, occ_dst);
             QD_HIP(hipGetLastError());
         }

@@ -19,6 +19,7 @@ QD_NOISE_LATCH = 4
 QD_MAP_GLOBAL, QD_MAP_PER_SCAN = 0, 1
 QD_POINTS_SLOTS = 64
 QD_LINE_SLOTS = 4096
+QD_GRID_SLOTS = 4096
 QD_SCAN_VIRTUAL, QD_SCAN_PHYSICAL = 0, 1
 QD_ERR_ARG, QD_ERR_HIP, QD_ERR_STATE = 1, 2, 3
 
@@ -29,6 +30,7 @@ EXPORTS = [
     "qd_get_occupations", "qd_get_candidates", "qd_get_eigen", "qd_get_search_stats", "qd_get_solver_stats", "qd_get_rng_state", "qd_set_rng_state",
     "qd_time_ground_kernel", "qd_time_candidates_kernel", "qd_time_kernels", "qd_timed_kernel_name", "qd_chunk_envs",
     "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex", "qd_scan_affine",
+    "qd_scan_grid",
 ]
 # exported too, kept apart: names with a digit, which a scan of qdsim.h for `qd_[a-z_]+(` does not find
 EXPORTS_WITH_DIGITS = ["qd_scan2d", "qd_scan1d"]
@@ -81,6 +83,11 @@ class QdScanAffineOpts(ctypes.Structure):
 
 class QdScan1dOpts(ctypes.Structure):
     """qd_scan1d_opts of include/qdsim.h: the fields of qd_scan_opts for a qd_scan1d call (occ_dst is [nq][n][N])."""
+    _fields_ = list(QdScanOpts._fields_)
+
+
+class QdScanGridOpts(ctypes.Structure):
+    """qd_scan_grid_opts of include/qdsim.h: the fields of qd_scan_opts for a qd_scan_grid call (occ_dst is [nq][ny][nx][N])."""
     _fields_ = list(QdScanOpts._fields_)
 
 
@@ -165,6 +172,9 @@ def lib():
     L.qd_scan_affine.restype = ctypes.c_int
     L.qd_scan1d.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, dp, fp, dp, ctypes.POINTER(QdScan1dOpts), vp]
     L.qd_scan1d.restype = ctypes.c_int
+    L.qd_scan_grid.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, dp, fp, dp,
+                               ctypes.POINTER(QdScanGridOpts), vp]
+    L.qd_scan_grid.restype = ctypes.c_int
     _LIB = L
     return L
 

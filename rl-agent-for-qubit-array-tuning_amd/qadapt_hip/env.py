@@ -56,17 +56,8 @@ class ModelFacade:
         """n_open (..., N) float64."""
         return self._points(vg, vb, ("occupations",))[1]
 
-    def do1d_open(self, gate, min, max, points):
-        """The reference's `do1d_open(gate, min, max, points)` (TunnelCoupledChargeSensed.py:192-205 over
-        GateVoltageComposer.do1d): a noise-free sweep of `points` points of one gate over [min, max] on the env's current
-        device, every other gate, the sensor gate and the barriers at 0 -- the base point is zero, as the composer builds it.
-        Returns (signal (points, 1), n_open (points, N)) float64, as charge_sensor_open does.  `gate` follows the composer's
-        grammar: an int g or "P{g}" (1-indexed; g = N+1 is the sensor gate) sweeps that PHYSICAL gate; "vP{i}", "e{i}_{j}"
-        (v_i - v_j) and "U{i}_{j}" ((v_i + v_j) / sqrt(2)) sweep in the VIRTUAL frame through the env's current virtual gate
-        matrix.  The composer's grid carries the virtual gate origin once on a "vP" sweep, sqrt(2) times on a "U" sweep, and
-        never on an "e" or a physical sweep (each _do1d_virtual term brings it along).  The facade renders through the
-        backend's scan1d, whose virtual frame adds the origin exactly ONCE: "vP", "P" and int sweeps are the composer's grid,
-        an "e" sweep sits one origin above it and a "U" sweep sqrt(2) - 1 origins below it; with a zero origin all agree."""
+    def _gate_axis(self, gate):
+        """(axis, frame) of one gate of the composer's grammar, as the backend's scans take them"""
         N = self.n_dot
         if isinstance(gate, (int, np.integer)) and not isinstance(gate, bool):
             g = int(gate)
@@ -82,11 +73,51 @@ class ModelFacade:
             axis, frame = gate, "virtual"
         else:
             raise ValueError(f"Invalid gate {gate!r} must be in the form P[int], vP[int], e[int]_[int], U[int]_[int]")
+        return axis, frame
+
+    def do1d_open(self, gate, min, max, points):
+        """The reference's `do1d_open(gate, min, max, points)` (TunnelCoupledChargeSensed.py:192-205 over
+        GateVoltageComposer.do1d): a noise-free sweep of `points` points of one gate over [min, max] on the env's current
+        device, every other gate, the sensor gate and the barriers at 0 -- the base point is zero, as the composer builds it.
+        Returns (signal (points, 1), n_open (points, N)) float64, as charge_sensor_open does.  `gate` follows the composer's
+        grammar: an int g or "P{g}" (1-indexed; g = N+1 is the sensor gate) sweeps that PHYSICAL gate; "vP{i}", "e{i}_{j}"
+        (v_i - v_j) and "U{i}_{j}" ((v_i + v_j) / sqrt(2)) sweep in the VIRTUAL frame through the env's current virtual gate
+        matrix.  The composer's grid carries the virtual gate origin once on a "vP" sweep, sqrt(2) times on a "U" sweep, and
+        never on an "e" or a physical sweep (each _do1d_virtual term brings it along).  The facade renders through the
+        backend's scan1d, whose virtual frame adds the origin exactly ONCE: "vP", "P" and int sweeps are the composer's grid,
+        an "e" sweep sits one origin above it and a "U" sweep sqrt(2) - 1 origins below it; with a zero origin all agree."""
+        N = self.n_dot
+        axis, frame = self._gate_axis(gate)
         gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
         out = self._b.scan1d([0], axis, (float(min), float(max)), int(points), np.zeros((1, N)), np.zeros((1, N - 1)), 0.0,
                              frame=frame, gamma=gamma, occupations=True)
         host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
         return (host(out["raw"]).astype(np.float64)[0][:, None], host(out["occupations"]).astype(np.float64)[0])
+
+    def do2d_open(self, x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points):
+        """The reference's `do2d_open(x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points)`
+        (TunnelCoupledChargeSensed.py:270-289 over GateVoltageComposer.do2d): a noise-free x_points x y_points grid over two
+        gates on the env's current device, every other gate, the sensor gate and the barriers at 0 -- the base point is zero, as
+        the composer builds it; the peak width is the model's, as in do1d_open.  Returns (signal (y_points, x_points, 1), n_open
+        (y_points, x_points, N)) float64: x runs along columns.  The gates follow the grammar of do1d_open.  One call has ONE
+        frame: two physical gates (ints, "P{g}") render in the physical frame, two virtual axes ("vP{i}", "e{i}_{j}",
+        "U{i}_{j}") in the virtual frame, and a pair that mixes the frames raises NotImplementedError (the composer adds a
+        physical and a virtual grid; the backend's grid has one frame per call).  The composer's grid is the sum of its two 1-D
+        grids, so it carries the virtual gate origin once per "vP" axis, sqrt(2) times per "U" axis and never per "e" or
+        physical axis: twice for "vP" against "vP", 1 + sqrt(2) times for "vP" against "U", not at all for "e" against "e".
+        The facade renders through the backend's scan_grid, whose virtual frame adds the origin exactly ONCE: a physical pair is
+        the composer's grid, a virtual pair sits (multiplicity - 1) origins below it; with a zero origin all agree."""
+        N = self.n_dot
+        (x_axis, x_frame), (y_axis, y_frame) = self._gate_axis(x_gate), self._gate_axis(y_gate)
+        if x_frame != y_frame:
+            raise NotImplementedError(f"do2d_open({x_gate!r}, ..., {y_gate!r}, ...): one call has one frame, and {x_gate!r} is "
+                                      f"{x_frame} while {y_gate!r} is {y_frame}; sweep two physical gates or two virtual axes")
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        out = self._b.scan_grid([0], x_axis, y_axis, (float(x_min), float(x_max)), (float(y_min), float(y_max)), int(x_points),
+                                int(y_points), np.zeros((1, N)), np.zeros((1, N - 1)), 0.0, frame=x_frame, gamma=gamma,
+                                occupations=True)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return (host(out["raw"]).astype(np.float64)[0][:, :, None], host(out["occupations"]).astype(np.float64)[0])
 
 
 class ArrayFacade:
@@ -185,6 +216,17 @@ class ArrayFacade:
                              sensor_voltage=None if sensor_voltage is None else float(sensor_voltage), **kw)
         host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
         return {k: host(v)[0] for k, v in out.items()}
+
+    def scan_grid(self, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage=None, **kw):
+        """The backend's scan_grid for this env (an nx x ny grid of points along two axes, as scan_affine takes them): one
+        query, numpy results without the query axis ("raw" (ny, nx), "image" (ny, nx), "plohi" (2,), "occupations"
+        (ny, nx, N))."""
+        out = self._b.scan_grid([0], x, y, x_range, y_range, nx, ny, np.asarray(gate_voltages, np.float64)[None, :],
+                                np.asarray(barrier_voltages, np.float64)[None, :],
+                                sensor_voltage=None if sensor_voltage is None else float(sensor_voltage), **kw)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return {k: host(v)[0] for k, v in out.items()}
+
 
 
 class QuantumDeviceEnv:

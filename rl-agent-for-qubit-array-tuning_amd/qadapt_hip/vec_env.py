@@ -644,6 +644,64 @@ class VecQuantumDeviceEnv:
         _lib.check(self._h, rc, "qd_scan1d")
         return out
 
+    def scan_grid(self, env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage=None, *,
+                  frame="virtual", vgm=None, gamma=None, noise=(), serial=None, stream_base=None, occupations=False):
+        """Stateless 2-D scans on any nx x ny grid of points along two direction vectors over the controls (qd_scan_grid): the
+        reference model layer's `do2d_open(x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points)` over
+        `GateVoltageComposer.do2d`, for nq queries in one call, each on the device of env `env_ids[q]`.  With W0 =
+        [gate_voltages, sensor_voltage, barrier_voltages] of the query, point (row r, column c) sits at
+        W0 + linspace(*x_range, nx)[c] * dx + linspace(*y_range, ny)[r] * dy.  A grid runs in a slot of its own size
+        (ceil(sqrt(nx*ny))^2 records), not in one of an image, and costs what its point count costs.  Nothing of the episodes
+        changes.
+          x, y              the two axes, resolved as scan_affine resolves them (scan_axis_vectors)
+          x_range, y_range  (lo, hi) of the scalar that multiplies the axis, for all queries or (nq, 2); lo > hi sweeps
+                            downwards, lo == hi repeats a point
+          nx, ny            columns and rows, both >= 1 with nx*ny <= R*R of this env, the same for all queries of a call
+          gate_voltages, barrier_voltages, sensor_voltage   the BASE POINT, as in scan_affine
+          frame, vgm, serial, stream_base   as in scan2d
+          gamma             None (each env's constant coulomb_peak_width), a scalar or (nq,) peak widths
+          noise             () / None / False: deterministic.  True: the sensor and latching stages this env was created with.
+                            Or an iterable of {"sensor", "latch"}.  Latching walks every row of nx points by itself: the held
+                            state is reset at every row start; the telegraph chain starts at point 0 and runs row after row
+          occupations       True adds the occupations the signal was formed from (after latching, if it ran)
+        With nx = ny = R this is scan_affine on a pixel_search env, with ny = 1 and a zero y it is scan1d (both bit for bit,
+        noise included).  Returns device tensors {"raw": (nq, ny, nx) float64, "image": (nq, ny, nx) float32 normalised per
+        grid with its own 0.5 / 99.5 percentiles, "plohi": (nq, 2)}, plus, with occupations=True, {"occupations":
+        (nq, ny, nx, N) float64}."""
+        N = self.N
+        if frame not in ("virtual", "physical"):
+            raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
+        if vgm is not None and frame == "physical":
+            raise ValueError("vgm has no meaning in the physical frame")
+        cx, cy = int(nx), int(ny)
+        if cx < 1 or cy < 1 or cx * cy > self.R * self.R:
+            raise ValueError(f"nx and ny must be >= 1 with nx*ny <= {self.R * self.R} (R*R of this env), got {nx} x {ny}")
+        nq, ids, gv, bv, sv = self._query_inputs(env_ids, gate_voltages, barrier_voltages, sensor_voltage)
+        dirs = np.stack([scan_axis_vectors(x, N, frame, nq), scan_axis_vectors(y, N, frame, nq)], axis=1)
+        rng = np.concatenate([np.broadcast_to(np.asarray(x_range, np.float64), (nq, 2)),
+                              np.broadcast_to(np.asarray(y_range, np.float64), (nq, 2))], axis=1)
+        if noise is True:
+            flags = self.noise_flags & ~_lib.QD_NOISE_RADIAL
+        else:
+            if noise and "radial" in tuple(noise):
+                raise ValueError("radial noise is centred on the env's own adjacent-pair observation: not defined for grids")
+            flags = self._noise_flags(noise)
+        dr = self._to_dev(dirs, torch.float64, (nq, 2, 2 * N))
+        rg = self._to_dev(rng, torch.float64, (nq, 4))
+        vm = None if vgm is None else self._to_dev(vgm, torch.float64, (nq, N + 1, N + 1))
+        gm = None if gamma is None else self._to_dev(gamma, torch.float64, (nq,))
+        out = self._query_outputs(nq, (), True, occupations, shape=(cy, cx))
+        addr = lambda t: None if t is None else t.data_ptr()                    # noqa: E731
+        opts = _lib.QdScanGridOpts(struct_size=ctypes.sizeof(_lib.QdScanGridOpts),
+                                   frame=_lib.QD_SCAN_PHYSICAL if frame == "physical" else _lib.QD_SCAN_VIRTUAL,
+                                   noise_flags=int(flags), reserved=0, serial=self._query_serial(serial, flags),
+                                   stream_base=int(self.env_id_offset if stream_base is None else stream_base),
+                                   vgm_dev=addr(vm), gamma_dev=addr(gm), occ_dst=addr(out.get("occupations")))
+        rc = self._lib.qd_scan_grid(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
+                                    _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]), ctypes.byref(opts), self._stream())
+        _lib.check(self._h, rc, "qd_scan_grid")
+        return out
+
     # ------------------------------------------------------------------ point evaluation
     def eval_points(self, env_ids, vg, vb, gamma=None, outputs=("signal", "occupations")):
         """The reference model's point function (qd_eval_points): `charge_sensor_open(vg, vb)` and `ground_state_open(vg, vb)`
