@@ -270,7 +270,20 @@ QD_HD void qd_vc_scales(const double* par, const QdLayout& L, const double* v_ex
     }
 }
 
-template <int N>
+// INTERLEAVED (the tile kernel): the 50 steps with A held in VECTOR registers and the N row sums of a step as N accumulators
+// advanced column by column.  Through scalar loads an 8x8 A needs 128 SGPRs, more than a kernel has: half of it was spilled
+// to VGPR lanes and reloaded by v_readlane in every step (112 of the loop's 236 instructions), and the fence after every
+// row made each row one dependent chain of 12 float64 operations.  Every accumulator still sums j = 0..N-1 from 0 with fma,
+// as qd_dotN does, and the update of a row is the same three operations from the old n (Jacobi), so the bits are those of
+// the row-major form (tests/hosttest_tile runs both forms of this source against each other).  The empty asm is device-only:
+// it makes the copy of A opaque, so that it stays in VGPRs and is not re-derived from the scalar loads.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define QD_VGPR_PIN(x) asm volatile("" : "+v"(x))
+#else
+#define QD_VGPR_PIN(x) ((void)0)
+#endif
+
+template <int N, bool INTERLEAVED = false>
 QD_HD void qd_pixel_continuous(const double* par, const double* v_ext, double* vd, double* ncont, double* isa) {
     constexpr int G = N + 1, V = 2 * N;
     const QdLayout L = qd_layout(N);
@@ -298,6 +311,31 @@ QD_HD void qd_pixel_continuous(const double* par, const double* v_ext, double* v
         for (int i = 0; i < N; ++i) n[i] = vd[i] > 0.0 ? vd[i] : 0.0;
 #pragma unroll
         for (int i = 0; i < N; ++i) { g2[i] = qd_dotN<N>(A + i * G, vd); QD_ROW_FENCE(); }
+        if constexpr (INTERLEAVED) {
+            double a[N][N];
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+#pragma unroll
+                for (int j = 0; j < N; ++j) { a[i][j] = A[i * G + j]; QD_VGPR_PIN(a[i][j]); }
+#pragma unroll 1
+            for (int it = 0; it < 50; ++it) {
+                double g1[N];
+#pragma unroll
+                for (int i = 0; i < N; ++i) g1[i] = 0.0;
+#pragma unroll
+                for (int j = 0; j < N; ++j)
+#pragma unroll
+                    for (int i = 0; i < N; ++i) g1[i] = fma(a[i][j], n[j], g1[i]);
+#pragma unroll
+                for (int i = 0; i < N; ++i) {
+                    double grad = g1[i] - g2[i];
+                    double v = n[i] - lr * grad;
+                    nn[i] = v > 0.0 ? v : 0.0;
+                }
+#pragma unroll
+                for (int i = 0; i < N; ++i) n[i] = nn[i];
+            }
+        } else {
         for (int it = 0; it < 50; ++it) {
 #pragma unroll
             for (int i = 0; i < N; ++i) {
@@ -309,6 +347,7 @@ QD_HD void qd_pixel_continuous(const double* par, const double* v_ext, double* v
             }
 #pragma unroll
             for (int i = 0; i < N; ++i) n[i] = nn[i];
+        }
         }
 #pragma unroll
         for (int i = 0; i < N; ++i) ncont[i] = n[i];

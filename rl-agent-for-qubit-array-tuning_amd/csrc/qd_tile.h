@@ -21,7 +21,117 @@
 #include "qd_pixel.h"
 #include "qd_groundstate.h"        // qd_rcp, qd_sqrt_rsqrt
 
+// ---------------------------------------------------------------------------------------------
+// Pieces of the tile search that are plain functions of arrays: compiled into the kernel below and, on the host, into
+// tests/hosttest_tile, which runs each against a literal restatement of the code it replaced.
+// ---------------------------------------------------------------------------------------------
+// Minimum AND maximum of a floor over the wave in one reduction: fl in the low 16 bits, BIAS - fl in the high 16, reduced
+// with a per-field unsigned minimum (v_pk_min_u16 on the device).  For 0 <= fl <= BIAS both fields lie in [0, BIAS] =
+// [0, 0x7FFF]: each fits its 16 bits, and a per-field minimum has no carry from one field into the other, so the packing
+// cannot overflow.  A floor outside that range (qd_fl_packable false in some lane) sends the tile to the plain reductions.
+#define QD_FL_BIAS 0x7FFF
+QD_HD bool qd_fl_packable(int fl) { return (unsigned)fl <= (unsigned)QD_FL_BIAS; }
+QD_HD uint32_t qd_fl_pack(int fl) { return (uint32_t)fl | ((uint32_t)(QD_FL_BIAS - fl) << 16); }
+QD_HD uint32_t qd_fl_pkmin(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+#else
+    const uint32_t la = a & 0xFFFFu, lb = b & 0xFFFFu, ha = a >> 16, hb = b >> 16;
+    return (la < lb ? la : lb) | ((ha < hb ? ha : hb) << 16);
+#endif
+}
+QD_HD void qd_fl_unpack(uint32_t w, int& mn, int& mx) { mn = (int)(w & 0xFFFFu); mx = QD_FL_BIAS - (int)(w >> 16); }
+
+// Step 6 for one lane: energies of the superset S (front part 0..nSfront-1, then the back part from the top of the arrays
+// down), own validity box [blo, bhi], the KC lowest in the lane's buffer ke / kid (slot k at k * 64).
+// The first nSfront states are valid in EVERY lane by construction (a state is `likely` only with a finite Mh, which is set
+// only under the all-valid test), and nSfront >= KC whenever the tile has not failed (count(M <= T) >= KC).  FILL: slots
+// 0..KC-1 are then written from states 0..KC-1 in a straight line, the group maxima tracked on the way with strict > in
+// ascending slot order (the tie rule of the rescan), and the loop goes on from state KC without the validity test up to
+// nSfront.  Without FILL, or with nSfront < KC, the general loop runs: same slots, ids, energies, eout and count.
+template <int KC, bool FILL>
+QD_HD void qd_tile_select(int nS, int nSfront, int scap, const uint32_t* scode, const double* sD, const double* sa, const double* sb,
+                          double xs, double ys, uint32_t blo, uint32_t bhi, double* ke, uint16_t* kid,
+                          double& maxE_out, int& maxS_out, int& maxG_out, int& count_out, double& eout_out) {
+    constexpr int NG = KC / 8;
+    double gE[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}; int gS[4] = {0, 8, 16, 24};     // (first NG groups used)
+    double maxE = -INFINITY; int maxS = 0, maxG = 0, count = 0;
+    double eout = INFINITY;                                                  // lowest energy NOT kept
+    int si0 = 0, nfree = 0;                                                  // states below nfree need no validity test
+    if (FILL && nSfront >= KC) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            double me = -INFINITY; int ms = g * 8;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const int s = g * 8 + t;
+                const double en = fma(xs, sa[s], fma(ys, sb[s], sD[s]));
+                ke[s * 64] = en; kid[s * 64] = (uint16_t)s;
+                if (en > me) { me = en; ms = s; }
+            }
+            gE[g] = me; gS[g] = ms;
+        }
+        maxE = gE[0]; maxS = gS[0]; maxG = 0;
+#pragma unroll
+        for (int g = 1; g < NG; ++g) if (gE[g] > maxE) { maxE = gE[g]; maxS = gS[g]; maxG = g; }
+        count = KC; si0 = KC; nfree = nSfront;
+    }
+    for (int si = si0; si < nS; ++si) {
+        const int s = si < nSfront ? si : scap - 1 - (si - nSfront);        // front part, then the back part
+        const uint32_t code = scode[s];
+        const bool valid = (si < nfree) ||
+                           (((((code | 0x88888888u) - blo) & 0x88888888u) == 0x88888888u) &&
+                            ((((bhi | 0x88888888u) - code) & 0x88888888u) == 0x88888888u));
+        const double en = fma(xs, sa[s], fma(ys, sb[s], sD[s]));
+        if (!valid) continue;
+        if (count < KC) {
+            ke[count * 64] = en; kid[count * 64] = (uint16_t)s;
+            count++;
+            if (count == KC) {
+#pragma unroll
+                for (int g = 0; g < NG; ++g) {
+                    double me = -INFINITY; int ms = g * 8;
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) { const double v = ke[(g * 8 + t) * 64]; if (v > me) { me = v; ms = g * 8 + t; } }
+                    gE[g] = me; gS[g] = ms;
+                }
+                maxE = gE[0]; maxS = gS[0]; maxG = 0;
+#pragma unroll
+                for (int g = 1; g < NG; ++g) if (gE[g] > maxE) { maxE = gE[g]; maxS = gS[g]; maxG = g; }
+            }
+        } else if (en < maxE) {
+            eout = fmin(eout, maxE);                                        // the evicted state
+            ke[maxS * 64] = en; kid[maxS * 64] = (uint16_t)s;
+            {
+                double me = -INFINITY; int ms = maxG * 8;
+#pragma unroll
+                for (int t = 0; t < 8; ++t) { const double v = ke[(maxG * 8 + t) * 64]; if (v > me) { me = v; ms = maxG * 8 + t; } }
+#pragma unroll
+                for (int g = 0; g < NG; ++g) if (g == maxG) { gE[g] = me; gS[g] = ms; }
+            }
+            maxE = gE[0]; maxS = gS[0]; maxG = 0;
+#pragma unroll
+            for (int g = 1; g < NG; ++g) if (gE[g] > maxE) { maxE = gE[g]; maxS = gS[g]; maxG = g; }
+        } else {
+            eout = fmin(eout, en);
+        }
+    }
+    maxE_out = maxE; maxS_out = maxS; maxG_out = maxG; count_out = count; eout_out = eout;
+}
+
 #if defined(__HIPCC__)
+
+// A/B switches of the three reworked pieces (scripts/ab_build.sh NAME -DQD_TILE_...=0 builds the earlier form of one)
+#ifndef QD_TILE_PG_INTERLEAVED
+#define QD_TILE_PG_INTERLEAVED 1    // front end: projected gradient with A in VGPRs, rows interleaved (qd_pixel.h)
+#endif
+#ifndef QD_TILE_DPP
+#define QD_TILE_DPP 1               // wave reductions by DPP row operations + readlane; packed min / max of the floors
+#endif
+#ifndef QD_TILE_FILL
+#define QD_TILE_FILL 1              // selection: uniform fill of the first KC slots
+#endif
 
 // Capacities, chosen so that the wave's LDS stays within 32 KB (5 waves per CU; measured: 3 waves per CU cost 14 %, 2 cost 50 %):
 // the frontier ping-pong (2 x 832 x 12 B) hides under the per-lane kept sets (20 KB), the superset arrays take 383 x 28 B.
@@ -59,25 +169,73 @@ __device__ __forceinline__ double qd_rl(double v, int lane) {                   
     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), lane);
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
+// Wave reductions, the same value in every lane.  Inside a row of 16 lanes the exchange is done by DPP modifiers (quad
+// permutations for lane ^ 1 and lane ^ 2, then the mirror of 8 and the mirror of 16, as qd_half_min does: a few cycles
+// each, where every __shfl_xor is a dependent round trip through the LDS crossbar); then the rows are uniform and the
+// four row values are read as scalars (v_readlane of lanes 0, 16, 32, 48).  All 64 lanes are on.  min and max do not depend
+// on the order (fmin / fmax: a NaN loses against a number in either order), so the results are those of the butterfly.
+template <int CTRL>
+__device__ __forceinline__ int qd_dpp_i32(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false); }
+#define QD_ROW_ALLREDUCE(v, OP, DPP)                                                                                   \
+    v = OP(v, DPP<0xB1>(v));  /* quad_perm [1, 0, 3, 2] */                                                             \
+    v = OP(v, DPP<0x4E>(v));  /* quad_perm [2, 3, 0, 1] */                                                             \
+    v = OP(v, DPP<0x141>(v)); /* row_half_mirror */                                                                    \
+    v = OP(v, DPP<0x140>(v))  /* row_mirror */
 __device__ __forceinline__ int qd_wmin_i(int v) {
+#if QD_TILE_DPP
+    QD_ROW_ALLREDUCE(v, min, qd_dpp_i32);
+    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+               min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+#else
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
     return __builtin_amdgcn_readfirstlane(v);
+#endif
 }
 __device__ __forceinline__ int qd_wmax_i(int v) {
+#if QD_TILE_DPP
+    QD_ROW_ALLREDUCE(v, max, qd_dpp_i32);
+    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+#else
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
     return __builtin_amdgcn_readfirstlane(v);
+#endif
 }
 __device__ __forceinline__ double qd_wmin_d(double v) {
+#if QD_TILE_DPP
+    QD_ROW_ALLREDUCE(v, fmin, qd_dpp_f64);
+    return fmin(fmin(qd_rl(v, 0), qd_rl(v, 16)), fmin(qd_rl(v, 32), qd_rl(v, 48)));
+#else
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
     return v;
+#endif
 }
 __device__ __forceinline__ double qd_wmax_d(double v) {
+#if QD_TILE_DPP
+    QD_ROW_ALLREDUCE(v, fmax, qd_dpp_f64);
+    return fmax(fmax(qd_rl(v, 0), qd_rl(v, 16)), fmax(qd_rl(v, 32), qd_rl(v, 48)));
+#else
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
     return v;
+#endif
+}
+// minimum and maximum of a packable floor (qd_fl_pack) in one reduction; the four row words are unpacked as scalars
+__device__ __forceinline__ void qd_wminmax_fl(int fl, int& mn, int& mx) {
+    int v = (int)qd_fl_pack(fl);
+#define QD_PKMIN_I(a, b) (int)qd_fl_pkmin((uint32_t)(a), (uint32_t)(b))
+    QD_ROW_ALLREDUCE(v, QD_PKMIN_I, qd_dpp_i32);
+#undef QD_PKMIN_I
+    int lo = QD_FL_BIAS, hi = QD_FL_BIAS;
+#pragma unroll
+    for (int r = 0; r < 64; r += 16) {
+        const unsigned w = (unsigned)__builtin_amdgcn_readlane(v, r);
+        lo = min(lo, (int)(w & 0xFFFFu)); hi = min(hi, (int)(w >> 16));
+    }
+    mn = lo; mx = QD_FL_BIAS - hi;
 }
 __device__ __forceinline__ int qd_lane_prefix(unsigned long long mask) {           // set bits below my lane
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
@@ -174,7 +332,7 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
         }
 #pragma unroll
         for (int i = 0; i < N; ++i) vd[i] = vpp[i];
-        qd_pixel_continuous<N>(spar, v_ext, vd, ncont, &isa);
+        qd_pixel_continuous<N, QD_TILE_PG_INTERLEAVED != 0>(spar, v_ext, vd, ncont, &isa);
     }
     int fl[N];
 #pragma unroll
@@ -230,9 +388,23 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
     // floor ranges: candidate digits of the tile [lo, hi], valid in EVERY pixel [alo, ahi]
     int lo_[N], alo_[N], ahi_[N], nd_[N];
     unsigned long long allvalid_count = 1;
+#if QD_TILE_DPP
+    bool packed;                                                           // every floor of the tile fits the packed reduction
+    {
+        int orfl = 0;                                                      // (a negative floor sets the sign bit of the OR)
+#pragma unroll
+        for (int i = 0; i < N; ++i) orfl |= fl[i];
+        packed = __ballot(!qd_fl_packable(orfl)) == 0ull;
+    }
+#endif
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-        const int fmn = qd_wmin_i(fl[i]), fmx = qd_wmax_i(fl[i]);
+        int fmn, fmx;
+#if QD_TILE_DPP
+        if (packed) qd_wminmax_fl(fl[i], fmn, fmx);
+        else
+#endif
+        { fmn = qd_wmin_i(fl[i]); fmx = qd_wmax_i(fl[i]); }
         lo_[i] = max(fmn - 1, 0); const int hi = fmx + 2;
         alo_[i] = max(fmx - 1, 0); ahi_[i] = fmn + 2;
         nd_[i] = hi - lo_[i] + 1;
@@ -241,7 +413,6 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
         if (lane == 0) { T.lo[i] = lo_[i]; T.nd[i] = nd_[i]; }
     }
     static_assert(KC == 8 || KC == 16 || KC == 32, "kept sets come in groups of 8");
-    constexpr int NG = KC / 8;
     if (allvalid_count < (unsigned long long)KC) { fail = true; why = 1; }
     __builtin_amdgcn_wave_barrier();
 
@@ -536,48 +707,9 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
         blo |= (uint32_t)(max(fl[i] - 1, 0) - lo_[i]) << (4 * (N - 1 - i));
         bhi |= (uint32_t)(fl[i] + 2 - lo_[i]) << (4 * (N - 1 - i));
     }
-    double gE[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}; int gS[4] = {0, 8, 16, 24};     // (first NG groups used)
-    double maxE = -INFINITY; int maxS = 0, maxG = 0, count = 0;
-    double eout = INFINITY;                                                  // lowest energy NOT kept
-    for (int si = 0; si < nS; ++si) {
-        const int s = si < nSfront ? si : QD_T_SCAP - 1 - (si - nSfront);      // front part, then the back part
-        const uint32_t code = T.scode[s];
-        const bool valid = ((((code | 0x88888888u) - blo) & 0x88888888u) == 0x88888888u) &&
-                           ((((bhi | 0x88888888u) - code) & 0x88888888u) == 0x88888888u);
-        const double en = fma(xs, T.sa[s], fma(ys, T.sb[s], T.sD[s]));
-        if (!valid) continue;
-        if (count < KC) {
-            T.u.k.e[count][lane] = en; T.u.k.id[count][lane] = (uint16_t)s;
-            count++;
-            if (count == KC) {
-#pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    double me = -INFINITY; int ms = g * 8;
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) { const double v = T.u.k.e[g * 8 + t][lane]; if (v > me) { me = v; ms = g * 8 + t; } }
-                    gE[g] = me; gS[g] = ms;
-                }
-                maxE = gE[0]; maxS = gS[0]; maxG = 0;
-#pragma unroll
-                for (int g = 1; g < NG; ++g) if (gE[g] > maxE) { maxE = gE[g]; maxS = gS[g]; maxG = g; }
-            }
-        } else if (en < maxE) {
-            eout = fmin(eout, maxE);                                        // the evicted state
-            T.u.k.e[maxS][lane] = en; T.u.k.id[maxS][lane] = (uint16_t)s;
-            {
-                double me = -INFINITY; int ms = maxG * 8;
-#pragma unroll
-                for (int t = 0; t < 8; ++t) { const double v = T.u.k.e[maxG * 8 + t][lane]; if (v > me) { me = v; ms = maxG * 8 + t; } }
-#pragma unroll
-                for (int g = 0; g < NG; ++g) if (g == maxG) { gE[g] = me; gS[g] = ms; }
-            }
-            maxE = gE[0]; maxS = gS[0]; maxG = 0;
-#pragma unroll
-            for (int g = 1; g < NG; ++g) if (gE[g] > maxE) { maxE = gE[g]; maxS = gS[g]; maxG = g; }
-        } else {
-            eout = fmin(eout, en);
-        }
-    }
+    double maxE, eout; int maxS, maxG, count;
+    qd_tile_select<KC, QD_TILE_FILL != 0>(nS, nSfront, QD_T_SCAP, T.scode, T.sD, T.sa, T.sb, xs, ys, blo, bhi, &T.u.k.e[0][lane],
+                                          &T.u.k.id[0][lane], maxE, maxS, maxG, count, eout);
     // a lane whose boundary is closer than what the arithmetic can tell apart is redone exactly
     const double amb = 2.0 * margin;
     const bool redo = (count < KC) || !(eout - maxE > amb);
