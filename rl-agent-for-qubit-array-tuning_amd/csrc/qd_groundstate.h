@@ -98,7 +98,7 @@ struct QdWaveLds {
     unsigned char nidx[NS][64];
     double buf[64];                 // publish buffer for per-component reductions
     double pv[2][16];               // per half: tc[0..N-2] at offset 9; [0], [1]: upper bound and margin of the pruning test
-    short pfl[2][8];                // per half: floor(n_cont)
+    int pfl[2][8];                  // per half: floor(n_cont) (32 bits: a plunger at 3e4 V has floors beyond a short)
 };
 struct QdBlockLds {
     unsigned pool_top;              // bump allocator of the batch's slab (doubles)
@@ -260,7 +260,7 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
     // pixel-uniform record fields go through LDS once (keeps them out of registers)
     const int hh = hb >> 5;
     if (m >= 9 && m < 9 + N - 1) W.pv[hh][m] = rec->tc[m - 9];
-    if (m >= 16 && m < 16 + N) W.pfl[hh][m - 16] = (short)rec->fl[m - 16];
+    if (m >= 16 && m < 16 + N) W.pfl[hh][m - 16] = rec->fl[m - 16];
     __builtin_amdgcn_wave_barrier();
     const double* pvv = W.pv[hh];
     const bool inK = m < kept;
@@ -326,12 +326,12 @@ __device__ __forceinline__ void qd_ground_structure(const QdPixelRec* __restrict
                 const int q = __builtin_ctz(ay) >> 2;
                 const int d = N - 2 - q;                   // adjacent pair (d, d+1)
                 // occupations of the pair's two dots straight from the code's digits and the floors in LDS
-                const int nd = (int)W.pfl[hh][d] + (int)((ecode >> (4 * (q + 1))) & 3u) - 1;
-                const int nd1 = (int)W.pfl[hh][d + 1] + (int)((ecode >> (4 * q)) & 3u) - 1;
+                const int nd = W.pfl[hh][d] + (int)((ecode >> (4 * (q + 1))) & 3u) - 1;
+                const int nd1 = W.pfl[hh][d + 1] + (int)((ecode >> (4 * q)) & 3u) - 1;
                 const double t = pvv[9 + d];
                 // Y < 0: s_j = s_i - e_d + e_{d+1} (forward); else backward
-                // (small integers: the product is formed exactly either way, so it is converted once)
-                const double prod = (double)((Y < 0) ? nd * (nd1 + 1) : nd1 * (nd + 1));
+                // (integers below 2^26: the float64 product is exact, where the 32-bit one overflows from 46341 electrons on)
+                const double prod = (Y < 0) ? (double)nd * (double)(nd1 + 1) : (double)nd1 * (double)(nd + 1);
                 double sq_ = 0.0;
                 if (prod > 0.0) sq_ = qd_sqrt1(prod);
                 c = -t * sq_;

@@ -15,7 +15,7 @@
 //   4. T by bisection on the count of M(c) <= t, superset S = {m(c) <= T} (typically 40-90 states)
 //   5. per lane: energies of S by two FMAs each, own validity box, top-KC buffer in LDS
 // Every bound carries explicit margins (affine residual, arithmetic); a lane whose KC-th / (KC+1)-th energies are closer
-// than the margin, and any tile that overflows a capacity, is flagged (nvalid = -1) and redone by the exact
+// than the margin (or, in unsorted records, its two lowest), and any tile that overflows a capacity, is flagged (nvalid = -1) and redone by the exact
 // per-pixel search (qd_k_candidates), so the kept SETS are bit-identical to the brute-force scan in every case.
 #pragma once
 #include "qd_pixel.h"
@@ -762,6 +762,7 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
             T.u.k.e[pos][lane] = E; T.u.k.id[pos][lane] = id;
         }
     }
+    double e1 = INFINITY, e2 = INFINITY;                                      // the two lowest plane energies of the kept set
     for (int k = 0; k < KC; ++k) {
         const uint32_t code = T.scode[T.u.k.id[k][lane]];
         const uint32_t dg = (code + off) - 0x44444444u;                       // nibbles: c - fl + 1 in 0..3 (no carries: each sum < 16)
@@ -771,9 +772,17 @@ qd_k_tile(const int* __restrict__ env_ids, int env_base, int R, const double* __
         idx = (idx | (idx >> 4)) & 0x00FF00FFu;
         idx = (idx | (idx >> 8)) & 0x0000FFFFu;
         rec->idx[k] = (uint16_t)idx;
-        const double E = sort_output ? T.u.k.e[k][lane] : T.u.k.e[k][lane] + Ecg;
+        const double ek = T.u.k.e[k][lane];
+        e2 = fmin(e2, fmax(e1, ek)); e1 = fmin(e1, ek);
+        const double E = sort_output ? ek : ek + Ecg;
         rec->E[k] = E * isa;
     }
+    // Unsorted records carry the PLANE energies, which tell two states apart only beyond the margin.  States whose canonical
+    // energies are exactly equal can be the ground state of a pixel only as its two lowest, and the ground-state stage breaks
+    // such a tie by the candidate index (qd_ground_select): a lane whose two lowest energies are that close is redone exactly
+    // as well, so that the tie reaches it as a tie and not as the round-off of the planes.  (Sorted records carry the
+    // canonical energies already.)
+    if (!sort_output && !(e2 - e1 > amb)) { qd_tile_hand_over<N>(rec, vd, ncont, isa); return; }
 #pragma unroll
     for (int i = 0; i < N; ++i) rec->fl[i] = fl[i];
     rec->nvalid = KC;

@@ -10,6 +10,7 @@
 extern "C" {
 int qdht_pg(int N, int interleaved, long n, const double* par, long par_stride, const double* v_ext, const double* vd_in,
             double* vd_out, double* ncont, double* isa);
+int qdht_fl_packable(int fl);
 void qdht_fl_minmax(const int* fl, int* mn, int* mx);
 int qdht_select(int KC, int fill, int nS, int nSfront, int scap, const uint32_t* scode, const double* sD, const double* sa,
                 const double* sb, double xs, double ys, uint32_t blo, uint32_t bhi, double amb, double* e_out, uint16_t* id_out,
@@ -39,12 +40,36 @@ int main() {
         }
         for (int k = 0; k < 3; ++k) bad |= memcmp(o[0][k].data(), o[1][k].data(), o[0][k].size() * sizeof(double)) != 0;
     }
-    for (int rep = 0; rep < 200; ++rep) {
-        int fl[64], mn, mx, rmn = 0x7FFF, rmx = 0;
-        for (int l = 0; l < 64; ++l) { fl[l] = (int)(urand() * 32768.0); rmn = fl[l] < rmn ? fl[l] : rmn; rmx = fl[l] > rmx ? fl[l] : rmx; }
-        qdht_fl_minmax(fl, &mn, &mx);
-        bad |= mn != rmn || mx != rmx;
+    // floors of a tile on both sides of 0x7FFF, the limit of the packed reduction.  kind 0: anywhere below 32768; 1: a tile's
+    // spread around the limit (some lanes packable, others not); 2: all above; 3: a spread around 0 with negative floors; 4: a
+    // spread that ends exactly at the limit.  Per lane qd_fl_packable is the range test, and the kernel's test of the OR of a
+    // lane's floors is the AND of the single tests; a tile whose lanes are all packable reduces to the plain min / max (any
+    // other tile takes the plain reductions in the kernel and is not packed here).
+    int packed_tiles = 0, plain_tiles = 0;
+    for (int rep = 0; rep < 1000; ++rep) {
+        const int kind = rep % 5;
+        const int base = kind == 1 ? 0x7FFF - 7 + (int)(urand() * 8.0) : kind == 2 ? 0x8000 + (int)(urand() * 40000.0)
+                       : kind == 3 ? -3 : kind == 4 ? 0x7FFF - 7 : 0;
+        int fl[64], mn, mx, rmn = 0x7FFFFFFF, rmx = -0x7FFFFFFF, orfl = 0;
+        bool all = true;
+        for (int l = 0; l < 64; ++l) {
+            fl[l] = kind == 0 ? (int)(urand() * 32768.0) : base + (int)(urand() * 8.0);
+            rmn = fl[l] < rmn ? fl[l] : rmn; rmx = fl[l] > rmx ? fl[l] : rmx;
+            const bool want = fl[l] >= 0 && fl[l] <= 0x7FFF;
+            bad |= (qdht_fl_packable(fl[l]) != 0) != want;
+            all = all && want;
+            orfl |= fl[l];
+        }
+        bad |= (qdht_fl_packable(orfl) != 0) != all;
+        if (kind == 0 || kind == 4) bad |= !all;
+        if (kind == 2) bad |= all;
+        if (all) {
+            qdht_fl_minmax(fl, &mn, &mx);
+            bad |= mn != rmn || mx != rmx;
+            packed_tiles++;
+        } else plain_tiles++;
     }
+    bad |= packed_tiles < 400 || plain_tiles < 300;                          // both sides were drawn
     const int scap = 383;
     std::vector<uint32_t> sc(scap); std::vector<double> sD(scap), sa(scap), sb(scap);
     for (int KC = 8; KC <= 32; KC *= 2)
