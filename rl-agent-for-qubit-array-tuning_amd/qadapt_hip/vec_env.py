@@ -994,15 +994,17 @@ class VecQuantumDeviceEnv:
 
     def solver_stats(self):
         """Eigen-solver counters of the ground-state kernel (validate mode): tasks = hop components of >= 2 states
-        solved, Laguerre iterations per task and per 64-task wave tile (a tile waits for its slowest lane), tasks by size;
-        wide_tasks: the blocks of 33..64 states (full space only), solved one per wavefront and in no tile."""
+        solved, Laguerre iterations per task and per 64-task wave tile (a tile waits for its slowest lane), tasks by size
+        (2 .. 8 states each; "9+": the classes of 9-10, 11-12 and 13-32 states together; the counters are per size class,
+        out[4 + class]); wide_tasks: the blocks of 33..64 states (full space only), solved one per wavefront and in no tile."""
         out = (ctypes.c_uint64 * 16)()
         _lib.check(self._h, self._lib.qd_get_solver_stats(self._h, out), "qd_get_solver_stats")
         tasks, tiles = max(int(out[0]), 1), max(int(out[2]), 1)
+        by_size = {str(k + 2): int(out[4 + k]) for k in range(7)}
+        by_size["9+"] = int(out[11]) + int(out[12]) + int(out[13])
         return {"tasks": int(out[0]), "laguerre_per_task": int(out[1]) / tasks, "tiles": int(out[2]),
                 "laguerre_per_tile_max": int(out[3]) / tiles, "lane_fill": (int(out[0]) - int(out[14])) / (64.0 * tiles),
-                "tasks_by_size": {("9+" if k == 7 else str(k + 2)): int(out[4 + k]) for k in range(8)},
-                "wide_tasks": int(out[14])}
+                "tasks_by_size": by_size, "wide_tasks": int(out[14])}
 
     def candidates(self):
         """(B,C,P,32,N) int32 kept charge states (validate mode): slots 0..K-1 the K = num_charge_states states in the

@@ -124,7 +124,12 @@ def cdd_inv_block(N, r):
 
 def make(name, N, R, tc_base=None):
     """(par, st) of family `name` with N dots, to be rendered at resolution R.  tc_base None keeps the sampled one."""
-    spec = FAMILIES[name](N, R)
+    return build(FAMILIES[name](N, R), N, R, tc_base=tc_base)
+
+
+def build(spec, N, R, tc_base=None):
+    """the recipe of the module docstring for one spec, dict(r, gate, step[, zero_cbg, minus_zero_dot]): tests/gs_cases.py
+    builds its own families on it"""
     L = layout(N); G = N + 1; V = 2 * N
     par, st = (a[0].copy() for a in sampled(N))
     A = par[L.cdd_inv:L.cdd_inv + G * G].reshape(G, G).copy()
