@@ -559,6 +559,41 @@ int qd_scan_grid(qd_handle* h, const int32_t* env_of_query_dev, int nq, int nx, 
                  const double* range_dev, const double* gate_v_dev, const double* barrier_v_dev, const double* sensor_v_dev,
                  double* raw_dst, float* image_dst, double* plohi_dst, const qd_scan_grid_opts* opts, void* stream);
 
+/* The CLOSED regime: the dot array is isolated from its reservoirs and holds exactly n_charge carriers -- the reference model
+ * class's ground_state_closed / charge_sensor_closed (qd_eval_points_closed) and do1d_closed / do2d_closed
+ * (qd_scan_grid_closed; TunnelCoupledChargeSensed.py:256-268, 291-309, 382-426).  The reference's own ground-state half is
+ * not defined there; the definition built here (DESIGN "closed regime") is the open algorithm restricted to one total-charge
+ * sector.  With the front end of the open call (vpp, tc, the voltage-dependent-capacitance scales, the scaled v'):
+ *   centre   m = argmin (n - v')^T A (n - v') over n >= 0, sum(n) = Q, A = cdd_inv[:N,:N], by a primal active-set iteration
+ *   kept     the K = num_charge_states lowest by (E, index) of c = floor(m) + delta, delta in {-1,0,1,2}^N, c >= 0,
+ *            sum(c) = Q, with the canonical energy and index of the open search, in the reference order
+ * (csrc/qd_closed.h, one kernel in the place of the open search's); fewer than K candidates (always at 2 and 3 dots) give
+ * an nv x nv problem.  The ground-state kernels and the noise-free sensor expression then run unchanged; the tunnelling
+ * Hamiltonian conserves the total charge, so the occupations sum to n_charge.
+ *
+ * qd_eval_points_closed takes the arguments of qd_eval_points and
+ *   n_charge_host    [ng]        HOST int32, the total charge of each group, 0..32767
+ *   states_dst       [np][K][N]  DEVICE int32 or NULL: the kept states of every point in list order, zeros behind the
+ *                                candidates found
+ * The lists are in the reference order as they come, so signal and occupations come from one run of the ground-state stage.
+ * qd_scan_grid_closed takes the arguments of qd_scan_grid and
+ *   n_charge_dev     [nq]        DEVICE int32, the total charge of each query, 0..32767
+ * It runs qd_scan_grid's slot loop with the one kernel exchanged, so a closed grid in the physical frame equals
+ * qd_eval_points_closed at the grid's voltages bit for bit in occupations and raw signal.  opts->noise_flags != 0 is QD_ERR_ARG:
+ * latching and sensor noise in the closed regime are not built.
+ * Both calls are stateless and stream-ordered, share scratch and stream discipline with their open siblings and change
+ * nothing that any other call can see.  QD_ERR_ARG: what the open sibling refuses, a NULL n_charge array, an n_charge outside
+ * 0..32767 (qd_scan_grid_closed reads n_charge_dev back for this check and waits for `stream` once per call).  QD_ERR_STATE:
+ * QD_FLAG_VALIDATE handles and handles in the full charge-state space, as the open siblings.  qd_step, the tile search, the
+ * full space and the noise stages have no closed form here. */
+int qd_eval_points_closed(qd_handle* h, const int32_t* group_env_host, const int64_t* group_start_host, int ng,
+                          const double* vg_dev, const double* vb_dev, const double* gamma_host, const int32_t* n_charge_host,
+                          double* signal_dst, double* occ_dst, int32_t* states_dst, void* stream);
+int qd_scan_grid_closed(qd_handle* h, const int32_t* env_of_query_dev, int nq, int nx, int ny, const double* dir_dev,
+                        const double* range_dev, const double* gate_v_dev, const double* barrier_v_dev,
+                        const double* sensor_v_dev, const int32_t* n_charge_dev, double* raw_dst, float* image_dst,
+                        double* plohi_dst, const qd_scan_grid_opts* opts, void* stream);
+
 /* Stitches one channel of nx*ny probe signals into one composite image on the device (map_device_range.py:134-170,
  * map_full_device_range.py:168-194).  raw_dev [nx*ny][C][P] as qd_probe wrote it, query index i*ny + j for scan (i, j);
  * composite_dst [ny*R][nx*R] float32; both DEVICE memory, stream-ordered, no host wait.

@@ -16,6 +16,7 @@
 #include "qd_affine.h"
 #include "qd_line.h"
 #include "qd_grid.h"
+#include "qd_closed.h"
 #include "qd_scratch.h"
 
 // The owners of a stream and of an event.  With the two memory policies of qd_scratch.h these are the only places that
@@ -163,6 +164,8 @@ struct qd_handle {
     QdDev<double> line_dense;
     // grids (qd_scan_grid): the line buffers above and one descriptor per grid in flight
     QdDev<QdGridAxes> grid_axes;
+    // the closed regime (qd_eval_points_closed): the total charge of every slot in flight, allocated by the first call
+    QdDev<int32_t> closed_q;
     mutable char err[512];                  // (the launchers take the handle const and still report through it)
 };
 
@@ -184,6 +187,11 @@ static int qd_fail(const qd_handle* h, int code, const char* what, hipError_t e 
         if (e != hipSuccess) snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
         else snprintf(h->err, sizeof(h->err), "%s", what);
     }
+    return code;
+}
+// a message that names the entry point: `fmt` has one %s, for `who`
+static int qd_failf(const qd_handle* h, int code, const char* fmt, const char* who) {
+    if (h) snprintf(h->err, sizeof(h->err), fmt, who);
     return code;
 }
 #define QD_HIP(call)                                                              \
@@ -672,6 +680,17 @@ static int qd_launch_candidates(const qd_handle* h, const QdEnvBufs& b, const Qd
     return QD_OK;
 }
 
+// The closed regime's place in a stateless query: behind a front kernel that left `cnt` slots of SP records in hand-over form,
+// and instead of the redo pass -- centre and sector search of every live record at the total charge qslot[slot] (device).
+static int qd_launch_closed(const qd_handle* h, const QdEnvBufs& b, const QdLane& ln, int SP, const int32_t* qslot, int cnt, hipStream_t s) {
+    const size_t shm = (size_t)h->kc * QD_CLOSED_BLOCK * (sizeof(double) + sizeof(uint16_t));
+    const dim3 grid((unsigned)((SP + QD_CLOSED_BLOCK - 1) / QD_CLOSED_BLOCK), cnt);
+    QD_DISPATCH_N(h->N, QD_DISPATCH_KC(h->kc,
+        qd_k_closed<NN, KK><<<grid, dim3(QD_CLOSED_BLOCK), shm, s>>>(SP, b.params, qslot, ln.recs.p)));
+    QD_HIP(hipGetLastError());
+    return QD_OK;
+}
+
 // a5-a13 for `cnt` envs starting at list position `base`: those of the stages in `st` that the handle has (qd_stages) --
 // tile search + exact redo pass or the per-pixel search alone, then the ground-state kernels.  On the blocks of a scan
 // (b.front) slot k renders ONE image over the axes in its state block copy instead of the env's C channel images.
@@ -1096,34 +1115,49 @@ extern "C" int qd_scan1d(qd_handle* h, const int32_t* env_of_query, int nq, int 
     return QD_OK;
 }
 
-extern "C" int qd_scan_grid(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir, const double* range,
-                            const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst, float* image_dst,
-                            double* plohi_dst, const qd_scan_grid_opts* opts, void* stream) {
+// qd_scan_grid (n_charge null) and qd_scan_grid_closed on one slot loop: the closed regime replaces the redo pass of the open
+// search by qd_k_closed at the queries' total charges and leaves every other launch as it is.
+static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
+                       const double* range, const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst,
+                       float* image_dst, double* plohi_dst, const qd_scan_grid_opts* opts, const int32_t* n_charge, void* stream) {
     static_assert(QD_GRID_MAX_SLOTS == QD_GRID_SLOTS, "qdsim.h states the bound");
-    if (!h) return QD_ERR_ARG;
-    if (nq < 0) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: nq < 0");
-    if (!env_of_query || !dir || !range) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: env_of_query_dev, dir_dev or range_dev is NULL");
-    if (!gate_v || !barrier_v) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: gate_v_dev or barrier_v_dev is NULL");
+    if (nq < 0) return qd_failf(h, QD_ERR_ARG, "%s: nq < 0", who);
+    if (!env_of_query || !dir || !range) return qd_failf(h, QD_ERR_ARG, "%s: env_of_query_dev, dir_dev or range_dev is NULL", who);
+    if (!gate_v || !barrier_v) return qd_failf(h, QD_ERR_ARG, "%s: gate_v_dev or barrier_v_dev is NULL", who);
     if (nx < 1 || ny < 1 || (long long)nx * ny > h->P)
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: nx and ny must be >= 1 with nx*ny <= P (P = resolution^2 of the handle)");
+        return qd_failf(h, QD_ERR_ARG, "%s: nx and ny must be >= 1 with nx*ny <= P (P = resolution^2 of the handle)", who);
     if (opts && opts->struct_size != (int32_t)sizeof(qd_scan_grid_opts))
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: opts->struct_size is not sizeof(qd_scan_grid_opts)");
+        return qd_failf(h, QD_ERR_ARG, "%s: opts->struct_size is not sizeof(qd_scan_grid_opts)", who);
     if (opts && opts->frame != QD_SCAN_VIRTUAL && opts->frame != QD_SCAN_PHYSICAL)
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL");
+        return qd_failf(h, QD_ERR_ARG, "%s: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL", who);
     if (opts && opts->frame == QD_SCAN_PHYSICAL && opts->vgm_dev)
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: vgm_dev has no meaning in the physical frame");
+        return qd_failf(h, QD_ERR_ARG, "%s: vgm_dev has no meaning in the physical frame", who);
     if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_LATCH)))
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
-                                      "centred on the env's own adjacent-pair observation)");
+        return qd_failf(h, QD_ERR_ARG, "%s: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
+                                      "centred on the env's own adjacent-pair observation)", who);
     if (h->cfg.flags & QD_FLAG_VALIDATE)
-        return qd_fail(h, QD_ERR_STATE, "qd_scan_grid: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
-                                        "B envs' last observe and renders no grids; use a handle without the flag");
+        return qd_failf(h, QD_ERR_STATE, "%s: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
+                                        "B envs' last observe and renders no grids; use a handle without the flag", who);
     if (h->full_m)
-        return qd_fail(h, QD_ERR_STATE, "qd_scan_grid: the full charge-state space synthesises its own voltages "
-                                        "(qd_k_full_structure); a grid front end for it is not built");
+        return qd_failf(h, QD_ERR_STATE, "%s: the full charge-state space synthesises its own voltages "
+                                        "(qd_k_full_structure); a grid front end for it is not built", who);
+    if (n_charge && opts && opts->noise_flags)
+        return qd_failf(h, QD_ERR_ARG, "%s: the closed regime has no noise stages: noise_flags must be 0", who);
     if (nq == 0) return QD_OK;
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
+    if (n_charge) {
+        // the range check reads the device: one copy of nq int32 and a wait for the stream
+        int32_t* qh = (int32_t*)malloc(sizeof(int32_t) * (size_t)nq);
+        if (!qh) return qd_fail(h, QD_ERR_NOMEM, "malloc");
+        hipError_t e_ = hipMemcpyAsync(qh, n_charge, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s);
+        if (e_ == hipSuccess) e_ = hipStreamSynchronize(s);
+        bool bad = false;
+        for (int q = 0; q < nq && e_ == hipSuccess; ++q) bad = bad || qh[q] < 0 || qh[q] > QD_CLOSED_QMAX;
+        free(qh);
+        if (e_ != hipSuccess) return qd_fail(h, QD_ERR_HIP, "hipMemcpyAsync(n_charge)", e_);
+        if (bad) return qd_failf(h, QD_ERR_ARG, "%s: n_charge must be in 0..32767", who);
+    }
     const int noise_flags = opts ? opts->noise_flags : 0;
     const unsigned long long serial = opts ? opts->serial : 0;
     const long long stream_base = opts ? opts->stream_base : 0;
@@ -1161,7 +1195,8 @@ extern "C" int qd_scan_grid(qd_handle* h, const int32_t* env_of_query, int nq, i
         QD_DISPATCH_N(h->N, qd_k_grid_front<NN><<<dim3((SP + QD_GRID_BLOCK - 1) / QD_GRID_BLOCK, cnt), dim3(QD_GRID_BLOCK), 0, s>>>(
                                 SP, b.params, b.state, axes, ln.recs.p));
         QD_HIP(hipGetLastError());
-        if (int rc = qd_launch_candidates(h, b, ln, nullptr, 0, cnt, s, true)) return rc;
+        if (n_charge) { if (int rc = qd_launch_closed(h, b, ln, SP, n_charge + base, cnt, s)) return rc; }
+        else if (int rc = qd_launch_candidates(h, b, ln, nullptr, 0, cnt, s, true)) return rc;
         if (int rc = qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND)) return rc;
         if (noise_flags & QD_NOISE_LATCH) {
             const long rows = (long)cnt * ny;
@@ -1182,27 +1217,47 @@ extern "C" int qd_scan_grid(qd_handle* h, const int32_t* env_of_query, int nq, i
     return QD_OK;
 }
 
+extern "C" int qd_scan_grid(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir, const double* range,
+                            const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst, float* image_dst,
+                            double* plohi_dst, const qd_scan_grid_opts* opts, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    return qd_grid_run(h, "qd_scan_grid", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
+                       plohi_dst, opts, nullptr, stream);
+}
+
+extern "C" int qd_scan_grid_closed(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
+                                   const double* range, const double* gate_v, const double* barrier_v, const double* sensor_v,
+                                   const int32_t* n_charge, double* raw_dst, float* image_dst, double* plohi_dst,
+                                   const qd_scan_grid_opts* opts, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    if (!n_charge) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_closed: n_charge_dev is NULL");
+    return qd_grid_run(h, "qd_scan_grid_closed", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
+                       plohi_dst, opts, n_charge, stream);
+}
+
 // slots in flight of qd_eval_points: one launch chunk of lane 0's records, at most QD_POINTS_SLOTS
 static int qd_points_slots(const qd_handle* h) { return h->chunk < QD_POINTS_MAX_SLOTS ? h->chunk : QD_POINTS_MAX_SLOTS; }
 
-extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
-                              const double* vb, const double* gamma, double* signal_dst, double* occ_dst, void* stream) {
+// qd_eval_points (n_charge null) and qd_eval_points_closed on one slot loop, as qd_grid_run
+static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
+                         const double* vb, const double* gamma, const int32_t* n_charge, double* signal_dst, double* occ_dst,
+                         int32_t* states_dst, void* stream) {
     static_assert(QD_POINTS_MAX_SLOTS == QD_POINTS_SLOTS, "qdsim.h states the bound");
-    if (!h) return QD_ERR_ARG;
-    if (ng < 0) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: ng < 0");
-    if (!group_env || !group_start) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: group_env_host or group_start_host is NULL");
-    if (!vg || !vb) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: vg_dev or vb_dev is NULL");
-    if (group_start[0] < 0) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: group_start is negative");
+    if (ng < 0) return qd_failf(h, QD_ERR_ARG, "%s: ng < 0", who);
+    if (!group_env || !group_start) return qd_failf(h, QD_ERR_ARG, "%s: group_env_host or group_start_host is NULL", who);
+    if (!vg || !vb) return qd_failf(h, QD_ERR_ARG, "%s: vg_dev or vb_dev is NULL", who);
+    if (group_start[0] < 0) return qd_failf(h, QD_ERR_ARG, "%s: group_start is negative", who);
     for (int g = 0; g < ng; ++g) {
-        if (group_start[g + 1] < group_start[g]) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: group_start is not non-decreasing");
-        if (group_env[g] < 0 || group_env[g] >= h->B) return qd_fail(h, QD_ERR_ARG, "qd_eval_points: env id out of range");
+        if (group_start[g + 1] < group_start[g]) return qd_failf(h, QD_ERR_ARG, "%s: group_start is not non-decreasing", who);
+        if (group_env[g] < 0 || group_env[g] >= h->B) return qd_failf(h, QD_ERR_ARG, "%s: env id out of range", who);
+        if (n_charge && (n_charge[g] < 0 || n_charge[g] > QD_CLOSED_QMAX)) return qd_failf(h, QD_ERR_ARG, "%s: n_charge must be in 0..32767", who);
     }
     if (h->cfg.flags & QD_FLAG_VALIDATE)
-        return qd_fail(h, QD_ERR_STATE, "qd_eval_points: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
-                                        "B envs' last observe and evaluates no points; use a handle without the flag");
+        return qd_failf(h, QD_ERR_STATE, "%s: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
+                                        "B envs' last observe and evaluates no points; use a handle without the flag", who);
     if (h->full_m)
-        return qd_fail(h, QD_ERR_STATE, "qd_eval_points: the full charge-state space synthesises its own voltages "
-                                        "(qd_k_full_structure); a point front end for it is not built yet");
+        return qd_failf(h, QD_ERR_STATE, "%s: the full charge-state space synthesises its own voltages "
+                                        "(qd_k_full_structure); a point front end for it is not built yet", who);
     if (ng == 0 || group_start[ng] == group_start[0]) return QD_OK;
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
@@ -1212,8 +1267,11 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
     // the ground-state launcher runs on the point buffers, without noise or eigenvalues; nothing of the envs is written
     const QdEnvBufs qb = h->points.view(h->C, h->R);
     const QdLane& ln = h->lanes[0];
+    if (n_charge) QD_HIP(h->closed_q.reserve((size_t)QD_POINTS_MAX_SLOTS));
     QdPointSlots T;
     memset(&T, 0, sizeof(T));
+    QdClosedQ TQ;
+    memset(&TQ, 0, sizeof(TQ));
     T.own_gamma = gamma ? 0 : 1;
     int n = 0;
     // one launch per `ps` slots: gather -> front end -> per-pixel search of the handed-over records -> ground state -> write
@@ -1226,11 +1284,21 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
         QD_HIP(hipGetLastError());
         // (the redo instantiation, and not through qd_launch_csd: on handles without a tile search that would pick the
         // whole per-pixel search and overwrite the front end)
-        if (int rc = qd_launch_candidates(h, qb, ln, nullptr, 0, n, s, true)) return rc;
+        if (n_charge) {
+            // the closed regime: the slots' total charges to the device, then centre and sector search instead of the redo pass
+            qd_k_closed_setq<<<dim3(1), dim3(QD_POINTS_MAX_SLOTS), 0, s>>>(TQ, n, h->closed_q.p);
+            QD_HIP(hipGetLastError());
+            if (int rc = qd_launch_closed(h, qb, ln, (int)CP, h->closed_q.p, n, s)) return rc;
+            if (states_dst) {
+                QD_DISPATCH_N(h->N, qd_k_closed_states<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, h->kept, ln.recs.p, states_dst));
+                QD_HIP(hipGetLastError());
+            }
+        } else if (int rc = qd_launch_candidates(h, qb, ln, nullptr, 0, n, s, true)) return rc;
         // The signal comes from the list as the search left it, which is what qd_observe and qd_probe solve: the probe's bits.
         // The occupations come from the list in the reference order, which is what a validate handle solves and
         // qd_get_occupations returns: with K == KC (search order) the records are sorted and the ground-state stage runs again.
-        const bool resort = !qd_sorted_records(h) && occ_dst;
+        // (the closed lists are in the reference order as they come)
+        const bool resort = !n_charge && !qd_sorted_records(h) && occ_dst;
         if (signal_dst || !resort) {
             if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND)) return rc;
             if (signal_dst || occ_dst) {
@@ -1256,10 +1324,26 @@ extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int6
             const long long left = group_start[g + 1] - p0;
             T.start[n] = p0; T.env[n] = group_env[g]; T.cnt[n] = (int)(left < CP ? left : CP);
             T.gamma[n] = gamma ? gamma[g] : 0.0;
+            TQ.q[n] = n_charge ? n_charge[g] : 0;
             if (++n == ps) if (int rc = flush()) return rc;
         }
     }
     return flush();
+}
+
+extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
+                              const double* vb, const double* gamma, double* signal_dst, double* occ_dst, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    return qd_points_run(h, "qd_eval_points", group_env, group_start, ng, vg, vb, gamma, nullptr, signal_dst, occ_dst, nullptr, stream);
+}
+
+extern "C" int qd_eval_points_closed(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
+                                     const double* vb, const double* gamma, const int32_t* n_charge, double* signal_dst,
+                                     double* occ_dst, int32_t* states_dst, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    if (!n_charge) return qd_fail(h, QD_ERR_ARG, "qd_eval_points_closed: n_charge_host is NULL");
+    return qd_points_run(h, "qd_eval_points_closed", group_env, group_start, ng, vg, vb, gamma, n_charge, signal_dst, occ_dst, states_dst,
+                         stream);
 }
 
 // numpy 'linear' percentile ranks of n values, as qd_k_percentile takes them

@@ -30,7 +30,7 @@ EXPORTS = [
     "qd_get_occupations", "qd_get_candidates", "qd_get_eigen", "qd_get_search_stats", "qd_get_solver_stats", "qd_get_rng_state", "qd_set_rng_state",
     "qd_time_ground_kernel", "qd_time_candidates_kernel", "qd_time_kernels", "qd_timed_kernel_name", "qd_chunk_envs",
     "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex", "qd_scan_affine",
-    "qd_scan_grid",
+    "qd_scan_grid", "qd_eval_points_closed", "qd_scan_grid_closed",
 ]
 # exported too, kept apart: names with a digit, which a scan of qdsim.h for `qd_[a-z_]+(` does not find
 EXPORTS_WITH_DIGITS = ["qd_scan2d", "qd_scan1d"]
@@ -175,6 +175,12 @@ def lib():
     L.qd_scan_grid.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, dp, fp, dp,
                                ctypes.POINTER(QdScanGridOpts), vp]
     L.qd_scan_grid.restype = ctypes.c_int
+    L.qd_eval_points_closed.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, dp, dp, ctypes.POINTER(ctypes.c_double),
+                                        ip, dp, dp, vp, vp]
+    L.qd_eval_points_closed.restype = ctypes.c_int
+    L.qd_scan_grid_closed.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, vp, dp, fp, dp,
+                                      ctypes.POINTER(QdScanGridOpts), vp]
+    L.qd_scan_grid_closed.restype = ctypes.c_int
     _LIB = L
     return L
 

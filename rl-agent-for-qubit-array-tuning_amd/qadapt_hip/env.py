@@ -22,7 +22,11 @@ class ModelFacade:
     `coulomb_peak_width` and the point functions `charge_sensor_open(vg, vb)` / `ground_state_open(vg, vb)`
     (TunnelCoupledChargeSensed.py:312-380), evaluated by the backend's `eval_points` on the env's current device without
     touching the episode and without noise.  `coulomb_peak_width` is the device's own at every reset and is read at call
-    time, so it may be assigned as the reference's `_get_obs` does (qarray_base_class.py:192-196)."""
+    time, so it may be assigned as the reference's `_get_obs` does (qarray_base_class.py:192-196).
+    The `_closed` siblings (TunnelCoupledChargeSensed.py:256-268, 291-309, 382-426) take the total charge `n_charge` of an
+    array that is isolated from its reservoirs: the kept states are the lowest of that total-charge sector around the
+    constrained continuous minimiser (DESIGN "closed regime"; the reference leaves its own ground-state half undefined), the
+    occupations of every point sum to n_charge, and the sensor half is the open one fed those occupations."""
 
     def __init__(self, backend, num_dots):
         self._b = backend
@@ -30,7 +34,7 @@ class ModelFacade:
         self.cgd_full = None
         self.coulomb_peak_width = None
 
-    def _points(self, vg, vb, outputs):
+    def _points(self, vg, vb, outputs, n_charge=None):
         if vb is None:
             raise NotImplementedError(
                 "charge_sensor_open / ground_state_open without barrier voltages: the reference's barrier-less branch uses a "
@@ -43,7 +47,8 @@ class ModelFacade:
                              f"got {vg.shape} and {vb.shape}")
         lead = vg.shape[:-1]
         gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
-        out = self._b.eval_points([0], vg.reshape(1, -1, N + 1), vb.reshape(1, -1, N - 1), gamma=gamma, outputs=outputs)
+        kw = {} if n_charge is None else {"n_charge": n_charge}
+        out = self._b.eval_points([0], vg.reshape(1, -1, N + 1), vb.reshape(1, -1, N - 1), gamma=gamma, outputs=outputs, **kw)
         host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
         signal = host(out["signal"]).astype(np.float64).reshape(lead + (1,)) if "signal" in outputs else None
         return signal, host(out["occupations"]).astype(np.float64).reshape(lead + (N,))
@@ -55,6 +60,15 @@ class ModelFacade:
     def ground_state_open(self, vg, vb=None):
         """n_open (..., N) float64."""
         return self._points(vg, vb, ("occupations",))[1]
+
+    def charge_sensor_closed(self, vg, n_charge, vb=None):
+        """(signal (..., 1), n_closed (..., N)) float64 with exactly `n_charge` carriers in the array; arguments in the
+        reference's order."""
+        return self._points(vg, vb, ("signal", "occupations"), n_charge=n_charge)
+
+    def ground_state_closed(self, vg, n_charge, vb=None):
+        """n_closed (..., N) float64; every row sums to n_charge."""
+        return self._points(vg, vb, ("occupations",), n_charge=n_charge)[1]
 
     def _gate_axis(self, gate):
         """(axis, frame) of one gate of the composer's grammar, as the backend's scans take them"""
@@ -94,7 +108,24 @@ class ModelFacade:
         host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
         return (host(out["raw"]).astype(np.float64)[0][:, None], host(out["occupations"]).astype(np.float64)[0])
 
-    def do2d_open(self, x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points):
+    def do1d_closed(self, gate, min, max, points, n_charge):
+        """The reference's `do1d_closed(gate, min, max, points, n_charge)`: do1d_open's sweep with exactly `n_charge` carriers
+        in the array, rendered as a one-row grid (the closed regime has the grid call alone).  Returns (signal (points, 1),
+        n_closed (points, N)) float64."""
+        N = self.n_dot
+        axis, frame = self._gate_axis(gate)
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        out = self._b.scan_grid_closed([0], axis, np.zeros(2 * N), (float(min), float(max)), (0.0, 0.0), int(points), 1,
+                                       np.zeros((1, N)), np.zeros((1, N - 1)), n_charge, 0.0, frame=frame, gamma=gamma, occupations=True)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return (host(out["raw"]).astype(np.float64)[0, 0][:, None], host(out["occupations"]).astype(np.float64)[0, 0])
+
+    def do2d_closed(self, x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points, n_charge):
+        """The reference's `do2d_closed(..., n_charge)`: do2d_open's grid with exactly `n_charge` carriers in the array (the
+        reference forgets to pass n_charge on; here it arrives).  Shapes, gate grammar and the one-frame rule of do2d_open."""
+        return self.do2d_open(x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points, _n_charge=n_charge)
+
+    def do2d_open(self, x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points, *, _n_charge=None):
         """The reference's `do2d_open(x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points)`
         (TunnelCoupledChargeSensed.py:270-289 over GateVoltageComposer.do2d): a noise-free x_points x y_points grid over two
         gates on the env's current device, every other gate, the sensor gate and the barriers at 0 -- the base point is zero, as
@@ -113,9 +144,12 @@ class ModelFacade:
             raise NotImplementedError(f"do2d_open({x_gate!r}, ..., {y_gate!r}, ...): one call has one frame, and {x_gate!r} is "
                                       f"{x_frame} while {y_gate!r} is {y_frame}; sweep two physical gates or two virtual axes")
         gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
-        out = self._b.scan_grid([0], x_axis, y_axis, (float(x_min), float(x_max)), (float(y_min), float(y_max)), int(x_points),
-                                int(y_points), np.zeros((1, N)), np.zeros((1, N - 1)), 0.0, frame=x_frame, gamma=gamma,
-                                occupations=True)
+        args = ([0], x_axis, y_axis, (float(x_min), float(x_max)), (float(y_min), float(y_max)), int(x_points), int(y_points),
+                np.zeros((1, N)), np.zeros((1, N - 1)))
+        if _n_charge is None:
+            out = self._b.scan_grid(*args, 0.0, frame=x_frame, gamma=gamma, occupations=True)
+        else:
+            out = self._b.scan_grid_closed(*args, _n_charge, 0.0, frame=x_frame, gamma=gamma, occupations=True)
         host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
         return (host(out["raw"]).astype(np.float64)[0][:, :, None], host(out["occupations"]).astype(np.float64)[0])
 

@@ -206,6 +206,22 @@ def scan_axis_vectors(axis, N, frame, nq):
     return np.tile(scan_axis_vector(axis, N, frame), (nq, 1))
 
 
+QD_CLOSED_QMAX = 32767
+
+
+def closed_charges(n_charge, n, what):
+    """n_charge of a closed query -- a scalar or one value per `what` -- as (n,) int32 on the host; integers in 0..32767"""
+    a = np.asarray(n_charge.detach().cpu().numpy() if isinstance(n_charge, torch.Tensor) else n_charge)
+    if a.dtype == bool or not (np.issubdtype(a.dtype, np.integer) or (np.issubdtype(a.dtype, np.floating) and np.all(a == np.rint(a)))):
+        raise ValueError(f"n_charge must hold integers, got {n_charge!r}")
+    if a.ndim > 1 or (a.ndim == 1 and a.size != n):
+        raise ValueError(f"n_charge must be a scalar or one value per {what} ({n}), got shape {a.shape}")
+    a = np.broadcast_to(a.astype(np.int64), (n,))
+    if a.size and (a.min() < 0 or a.max() > QD_CLOSED_QMAX):
+        raise ValueError(f"n_charge must be in 0..{QD_CLOSED_QMAX}, got {int(a.min())}..{int(a.max())}")
+    return np.ascontiguousarray(a, np.int32)
+
+
 def _ptr(t):
     """A device tensor's address as a pointer argument; None stays NULL."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
@@ -667,7 +683,25 @@ class VecQuantumDeviceEnv:
         With nx = ny = R this is scan_affine on a pixel_search env, with ny = 1 and a zero y it is scan1d (both bit for bit,
         noise included).  Returns device tensors {"raw": (nq, ny, nx) float64, "image": (nq, ny, nx) float32 normalised per
         grid with its own 0.5 / 99.5 percentiles, "plohi": (nq, 2)}, plus, with occupations=True, {"occupations":
-        (nq, ny, nx, N) float64}."""
+        (nq, ny, nx, N) float64}.  scan_grid_closed is the same grid at a fixed total charge."""
+        return self._scan_grid(env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm,
+                               gamma, noise, serial, stream_base, occupations, None)
+
+    def scan_grid_closed(self, env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, n_charge,
+                         sensor_voltage=None, *, frame="virtual", vgm=None, gamma=None, occupations=False):
+        """scan_grid in the CLOSED regime (qd_scan_grid_closed; the reference's `do2d_closed`, and `do1d_closed` as a one-row
+        grid): the array is isolated from its reservoirs and holds exactly `n_charge` carriers -- a scalar or (nq,) integers in
+        0..32767 -- so the occupations of every point sum to n_charge.  Arguments, frames and results are scan_grid's; there
+        are no noise stages.  In the physical frame the results equal eval_points(..., n_charge=) at the grid's voltages bit for
+        bit."""
+        if n_charge is None:
+            raise ValueError("scan_grid_closed needs n_charge; scan_grid is the open regime")
+        return self._scan_grid(env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm,
+                               gamma, (), None, None, occupations, n_charge)
+
+    def _scan_grid(self, env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm, gamma,
+                   noise, serial, stream_base, occupations, n_charge):
+        """scan_grid (n_charge None) and scan_grid_closed"""
         N = self.N
         if frame not in ("virtual", "physical"):
             raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
@@ -686,6 +720,11 @@ class VecQuantumDeviceEnv:
             if noise and "radial" in tuple(noise):
                 raise ValueError("radial noise is centred on the env's own adjacent-pair observation: not defined for grids")
             flags = self._noise_flags(noise)
+        qd = None
+        if n_charge is not None:
+            if flags:
+                raise ValueError("the closed regime has no noise stages: noise must be empty with n_charge")
+            qd = self._to_dev(closed_charges(n_charge, nq, "query"), torch.int32, (nq,))
         dr = self._to_dev(dirs, torch.float64, (nq, 2, 2 * N))
         rg = self._to_dev(rng, torch.float64, (nq, 4))
         vm = None if vgm is None else self._to_dev(vgm, torch.float64, (nq, N + 1, N + 1))
@@ -697,13 +736,19 @@ class VecQuantumDeviceEnv:
                                    noise_flags=int(flags), reserved=0, serial=self._query_serial(serial, flags),
                                    stream_base=int(self.env_id_offset if stream_base is None else stream_base),
                                    vgm_dev=addr(vm), gamma_dev=addr(gm), occ_dst=addr(out.get("occupations")))
+        if qd is not None:
+            rc = self._lib.qd_scan_grid_closed(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
+                                               _ptr(qd), _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]), ctypes.byref(opts),
+                                               self._stream())
+            _lib.check(self._h, rc, "qd_scan_grid_closed")
+            return out
         rc = self._lib.qd_scan_grid(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
                                     _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]), ctypes.byref(opts), self._stream())
         _lib.check(self._h, rc, "qd_scan_grid")
         return out
 
     # ------------------------------------------------------------------ point evaluation
-    def eval_points(self, env_ids, vg, vb, gamma=None, outputs=("signal", "occupations")):
+    def eval_points(self, env_ids, vg, vb, gamma=None, outputs=("signal", "occupations"), n_charge=None, states=False):
         """The reference model's point function (qd_eval_points): `charge_sensor_open(vg, vb)` and `ground_state_open(vg, vb)`
         (TunnelCoupledChargeSensed.py:312-380) at arbitrary PHYSICAL voltages, on the devices of the listed envs.  Nothing of
         the episodes changes and no noise stage runs; an env may be named many times.
@@ -715,14 +760,27 @@ class VecQuantumDeviceEnv:
                     qd_observe and qd_probe solve them (their bits), the occupations from the reference order a validate
                     handle keeps (the bits of `occupations()`); with num_charge_states 8, 16 or 32 those orders differ and
                     asking for both runs the ground-state stage twice
-        Returns device tensors {"signal": (n, m) float64, "occupations": (n, m, N) float64}; for list input, lists of n
-        tensors (m_i,) and (m_i, N)."""
+          n_charge  None: the open regime.  A scalar or (n,) integers in 0..32767, one per env id: the CLOSED regime
+                    (qd_eval_points_closed; the reference's `charge_sensor_closed` / `ground_state_closed`), the array isolated
+                    from its reservoirs with exactly that many carriers.  The kept states are the K lowest of that total-charge
+                    sector around the constrained continuous minimiser, the occupations of a point sum to n_charge, and signal
+                    and occupations come from one solve
+          states    True (closed regime only) adds "states": the kept charge states in list order, int32, zeros behind the
+                    candidates found
+        Returns device tensors {"signal": (n, m) float64, "occupations": (n, m, N) float64[, "states": (n, m, K, N) int32]};
+        for list input, lists of n tensors (m_i,), (m_i, N) and (m_i, K, N)."""
         outputs = tuple(outputs)
         if not outputs or any(o not in ("signal", "occupations") for o in outputs):
             raise ValueError(f"outputs must name 'signal' and / or 'occupations', got {outputs!r}")
         N, C = self.N, self.C
         ids = np.asarray(env_ids.detach().cpu().numpy() if isinstance(env_ids, torch.Tensor) else env_ids, np.int32).reshape(-1)
         n = int(ids.size)
+        if states and n_charge is None:
+            raise ValueError("states=True needs n_charge: the kept states are an output of the closed regime")
+        qh = None if n_charge is None else closed_charges(n_charge, n, "env id")
+        if states and self.num_charge_states is None:
+            raise _lib.QdError(f"qd_eval_points_closed refused (code {_lib.QD_ERR_STATE}): the full charge-state space has no "
+                               "kept list of K states")
         ragged = isinstance(vg, (list, tuple))
         if ragged != isinstance(vb, (list, tuple)):
             raise ValueError("vg and vb must both be arrays or both be lists of per-env arrays")
@@ -758,15 +816,30 @@ class VecQuantumDeviceEnv:
                 gamma.detach().cpu().numpy() if isinstance(gamma, torch.Tensor) else gamma, np.float64), (n,)))
         signal = torch.empty((total,), dtype=torch.float64, device=self.device) if "signal" in outputs else None
         occ = torch.empty((total, N), dtype=torch.float64, device=self.device) if "occupations" in outputs else None
-        rc = 0 if total == 0 else self._lib.qd_eval_points(          # (an empty tensor has no address to hand over)
-            self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
-            ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
-            None if gam is None else gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-            None if signal is None else ctypes.c_void_p(signal.data_ptr()),
-            None if occ is None else ctypes.c_void_p(occ.data_ptr()), self._stream())
-        _lib.check(self._h, rc, "qd_eval_points")
+        K = self.num_charge_states
+        kept = torch.empty((total, K, N), dtype=torch.int32, device=self.device) if states else None
+        if qh is not None:
+            rc = 0 if total == 0 else self._lib.qd_eval_points_closed(
+                self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
+                ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
+                None if gam is None else gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                qh.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                None if signal is None else ctypes.c_void_p(signal.data_ptr()),
+                None if occ is None else ctypes.c_void_p(occ.data_ptr()),
+                None if kept is None else ctypes.c_void_p(kept.data_ptr()), self._stream())
+            _lib.check(self._h, rc, "qd_eval_points_closed")
+        else:
+            rc = 0 if total == 0 else self._lib.qd_eval_points(          # (an empty tensor has no address to hand over)
+                self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
+                ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
+                None if gam is None else gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                None if signal is None else ctypes.c_void_p(signal.data_ptr()),
+                None if occ is None else ctypes.c_void_p(occ.data_ptr()), self._stream())
+            _lib.check(self._h, rc, "qd_eval_points")
         out = {}
         m = counts[0] if n else 0
+        if kept is not None:
+            out["states"] = [kept[start[i]:start[i + 1]] for i in range(n)] if ragged else kept.reshape(n, m, K, N)
         if signal is not None:
             out["signal"] = [signal[start[i]:start[i + 1]] for i in range(n)] if ragged else signal.reshape(n, m)
         if occ is not None:
