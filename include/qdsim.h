@@ -594,6 +594,47 @@ int qd_scan_grid_closed(qd_handle* h, const int32_t* env_of_query_dev, int nq, i
                         const double* sensor_v_dev, const int32_t* n_charge_dev, double* raw_dst, float* image_dst,
                         double* plohi_dst, const qd_scan_grid_opts* opts, void* stream);
 
+/* ENERGY LEVELS per point: qd_eval_points_ex is qd_eval_points / qd_eval_points_closed with an options struct that can also
+ * ask for the lowest eigenvalues of every point's Hamiltonian (csrc/qd_levels.h, one kernel, one point per wavefront).
+ *   Kept states.   For a point with kept list s_0 .. s_{K-1} (K = num_charge_states) the search leaves indices, floors, the
+ *                  number of valid candidates nvalid, the tunnel couplings and the energies E.  Let nv = min(nvalid, K).
+ *   Hamiltonian.   H = diag(E_0 .. E_{nv-1}) + H_t over those nv states: the reference's matrix of hamiltonian_build.py:75-137
+ *                  with the |0..0> PADDING COPIES LEFT OUT (they are always isolated and would only add copies of one
+ *                  diagonal entry).  E is the search's canonical energy, absolute, with the 1 / s_a factor of the
+ *                  voltage-dependent capacitance model included.
+ *   Levels.        level[k], k = 0 .. L-1, is the k-th smallest eigenvalue of H counted with multiplicity; k >= nv gives +inf.
+ *                  L = n_levels is in 1 .. QD_LEVELS_MAX.  Equal eigenvalues come back bitwise equal, and level[k] <=
+ *                  level[k + 1] always.  Accuracy: 1e-12 ||H||_inf, the bar of the ground-state solvers.
+ *   Norm.          hnorm = ||H||_inf = max_i (|E_i| + sum_j |H_ij|), unshifted.
+ *   Resolvability. The project's measure is rel_gap = (level[1] - level[0]) / hnorm: below about 1e-9 float64 does not
+ *                  resolve the ground vector, and the point's occupations and signal are round-off, here as in the
+ *                  reference's eigh.  (A spectrum that includes the padding copies reports gap 0 wherever |0..0> is the
+ *                  ground state of a short list; this one does not.)
+ *   Truncation.    The levels are those of the reference's TRUNCATED K-state Hamiltonian, not of the infinite system: an
+ *                  excited level is only as good as the kept list around the ground state.
+ *   Closed regime. With n_charge_host the same definition applies on the closed list (one total-charge sector, nvalid = nv).
+ * The levels kernel runs right behind the search, on the list as the search left it and before anything reorders it, so
+ * repeated calls give the same bits.  opts == NULL or n_levels == 0 launches exactly what qd_eval_points (n_charge_host NULL)
+ * or qd_eval_points_closed launches, with the same bits.  With signal_dst == occ_dst == NULL and n_levels > 0 the
+ * ground-state stage is not launched at all.  Stateless and stream-ordered as its siblings.
+ * QD_ERR_ARG: what the siblings refuse; opts->struct_size != sizeof(qd_points_opts); n_levels outside 0..QD_LEVELS_MAX;
+ * n_levels > 0 with levels_dst NULL; states_dst without n_charge_host.  QD_ERR_STATE: QD_FLAG_VALIDATE handles and handles in
+ * the full charge-state space, as the siblings.  Eigenvectors of excited levels, noisy or latched points and levels inside
+ * qd_step, probes, scans, lines and grids are not built. */
+#define QD_LEVELS_MAX 8
+typedef struct qd_points_opts {
+    int32_t struct_size;            /* = sizeof(qd_points_opts) */
+    int32_t n_levels;               /* 0: none */
+    const double*  gamma_host;      /* as qd_eval_points' gamma */
+    const int32_t* n_charge_host;   /* NULL: open regime; else the closed regime, as qd_eval_points_closed */
+    int32_t* states_dst;            /* closed regime only, as qd_eval_points_closed */
+    double*  levels_dst;            /* [points][n_levels], device */
+    double*  hnorm_dst;             /* [points], device, may be NULL */
+} qd_points_opts;
+int qd_eval_points_ex(qd_handle* h, const int32_t* group_env_host, const int64_t* group_start_host, int ng,
+                      const double* vg_dev, const double* vb_dev, double* signal_dst, double* occ_dst,
+                      const qd_points_opts* opts, void* stream);
+
 /* Stitches one channel of nx*ny probe signals into one composite image on the device (map_device_range.py:134-170,
  * map_full_device_range.py:168-194).  raw_dev [nx*ny][C][P] as qd_probe wrote it, query index i*ny + j for scan (i, j);
  * composite_dst [ny*R][nx*R] float32; both DEVICE memory, stream-ordered, no host wait.

@@ -17,6 +17,7 @@
 #include "qd_line.h"
 #include "qd_grid.h"
 #include "qd_closed.h"
+#include "qd_levels.h"
 #include "qd_scratch.h"
 
 // The owners of a stream and of an event.  With the two memory policies of qd_scratch.h these are the only places that
@@ -1238,10 +1239,11 @@ extern "C" int qd_scan_grid_closed(qd_handle* h, const int32_t* env_of_query, in
 // slots in flight of qd_eval_points: one launch chunk of lane 0's records, at most QD_POINTS_SLOTS
 static int qd_points_slots(const qd_handle* h) { return h->chunk < QD_POINTS_MAX_SLOTS ? h->chunk : QD_POINTS_MAX_SLOTS; }
 
-// qd_eval_points (n_charge null) and qd_eval_points_closed on one slot loop, as qd_grid_run
+// qd_eval_points (n_charge null), qd_eval_points_closed and qd_eval_points_ex on one slot loop, as qd_grid_run.  n_levels > 0: the
+// levels kernel (qd_levels.h) behind the search of every flush; n_levels == 0 launches what the first two always launched.
 static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
                          const double* vb, const double* gamma, const int32_t* n_charge, double* signal_dst, double* occ_dst,
-                         int32_t* states_dst, void* stream) {
+                         int32_t* states_dst, void* stream, int n_levels = 0, double* levels_dst = nullptr, double* hnorm_dst = nullptr) {
     static_assert(QD_POINTS_MAX_SLOTS == QD_POINTS_SLOTS, "qdsim.h states the bound");
     if (ng < 0) return qd_failf(h, QD_ERR_ARG, "%s: ng < 0", who);
     if (!group_env || !group_start) return qd_failf(h, QD_ERR_ARG, "%s: group_env_host or group_start_host is NULL", who);
@@ -1294,6 +1296,13 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
                 QD_HIP(hipGetLastError());
             }
         } else if (int rc = qd_launch_candidates(h, qb, ln, nullptr, 0, n, s, true)) return rc;
+        if (n_levels > 0) {
+            // the levels of the list as the search left it, before any qd_k_points_sort: one point per single-wave block
+            const dim3 lgrid((unsigned)(CP < 4096 ? CP : 4096), n);
+            QD_DISPATCH_N(h->N, qd_k_levels<NN><<<lgrid, dim3(64), 0, s>>>(T, (int)CP, h->kept, n_levels, ln.recs.p, levels_dst, hnorm_dst));
+            QD_HIP(hipGetLastError());
+            if (!signal_dst && !occ_dst) { n = 0; return QD_OK; }          // levels only: no ground-state stage
+        }
         // The signal comes from the list as the search left it, which is what qd_observe and qd_probe solve: the probe's bits.
         // The occupations come from the list in the reference order, which is what a validate handle solves and
         // qd_get_occupations returns: with K == KC (search order) the records are sorted and the ground-state stage runs again.
@@ -1344,6 +1353,23 @@ extern "C" int qd_eval_points_closed(qd_handle* h, const int32_t* group_env, con
     if (!n_charge) return qd_fail(h, QD_ERR_ARG, "qd_eval_points_closed: n_charge_host is NULL");
     return qd_points_run(h, "qd_eval_points_closed", group_env, group_start, ng, vg, vb, gamma, n_charge, signal_dst, occ_dst, states_dst,
                          stream);
+}
+
+extern "C" int qd_eval_points_ex(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
+                                 const double* vb, double* signal_dst, double* occ_dst, const qd_points_opts* opts, void* stream) {
+    static_assert(QD_LEVELS_MAX <= QD_LV_MAX, "a level per state at most");
+    if (!h) return QD_ERR_ARG;
+    if (!opts) return qd_points_run(h, "qd_eval_points_ex", group_env, group_start, ng, vg, vb, nullptr, nullptr, signal_dst, occ_dst, nullptr, stream);
+    if (opts->struct_size != (int32_t)sizeof(qd_points_opts))
+        return qd_fail(h, QD_ERR_ARG, "qd_eval_points_ex: opts->struct_size is not sizeof(qd_points_opts)");
+    if (opts->n_levels < 0 || opts->n_levels > QD_LEVELS_MAX)
+        return qd_fail(h, QD_ERR_ARG, "qd_eval_points_ex: opts->n_levels must be in 0..QD_LEVELS_MAX (8)");
+    if (opts->n_levels > 0 && !opts->levels_dst)
+        return qd_fail(h, QD_ERR_ARG, "qd_eval_points_ex: opts->n_levels > 0 needs opts->levels_dst");
+    if (opts->states_dst && !opts->n_charge_host)
+        return qd_fail(h, QD_ERR_ARG, "qd_eval_points_ex: opts->states_dst is an output of the closed regime and needs opts->n_charge_host");
+    return qd_points_run(h, "qd_eval_points_ex", group_env, group_start, ng, vg, vb, opts->gamma_host, opts->n_charge_host, signal_dst,
+                         occ_dst, opts->states_dst, stream, opts->n_levels, opts->levels_dst, opts->hnorm_dst);
 }
 
 // numpy 'linear' percentile ranks of n values, as qd_k_percentile takes them

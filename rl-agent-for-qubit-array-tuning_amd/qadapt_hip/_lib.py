@@ -20,6 +20,7 @@ QD_MAP_GLOBAL, QD_MAP_PER_SCAN = 0, 1
 QD_POINTS_SLOTS = 64
 QD_LINE_SLOTS = 4096
 QD_GRID_SLOTS = 4096
+QD_LEVELS_MAX = 8
 QD_SCAN_VIRTUAL, QD_SCAN_PHYSICAL = 0, 1
 QD_ERR_ARG, QD_ERR_HIP, QD_ERR_STATE = 1, 2, 3
 
@@ -30,7 +31,7 @@ EXPORTS = [
     "qd_get_occupations", "qd_get_candidates", "qd_get_eigen", "qd_get_search_stats", "qd_get_solver_stats", "qd_get_rng_state", "qd_set_rng_state",
     "qd_time_ground_kernel", "qd_time_candidates_kernel", "qd_time_kernels", "qd_timed_kernel_name", "qd_chunk_envs",
     "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex", "qd_scan_affine",
-    "qd_scan_grid", "qd_eval_points_closed", "qd_scan_grid_closed",
+    "qd_scan_grid", "qd_eval_points_closed", "qd_scan_grid_closed", "qd_eval_points_ex",
 ]
 # exported too, kept apart: names with a digit, which a scan of qdsim.h for `qd_[a-z_]+(` does not find
 EXPORTS_WITH_DIGITS = ["qd_scan2d", "qd_scan1d"]
@@ -89,6 +90,16 @@ class QdScan1dOpts(ctypes.Structure):
 class QdScanGridOpts(ctypes.Structure):
     """qd_scan_grid_opts of include/qdsim.h: the fields of qd_scan_opts for a qd_scan_grid call (occ_dst is [nq][ny][nx][N])."""
     _fields_ = list(QdScanOpts._fields_)
+
+
+class QdPointsOpts(ctypes.Structure):
+    """qd_points_opts of include/qdsim.h: the number of energy levels per point of a qd_eval_points_ex call, the peak widths and
+    (closed regime) total charges of its groups on the host, and the device destinations of kept states, levels and norms."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("n_levels", ctypes.c_int32), ("gamma_host", ctypes.POINTER(ctypes.c_double)),
+        ("n_charge_host", ctypes.POINTER(ctypes.c_int32)), ("states_dst", ctypes.c_void_p),
+        ("levels_dst", ctypes.c_void_p), ("hnorm_dst", ctypes.c_void_p),
+    ]
 
 
 class QdError(RuntimeError):
@@ -181,6 +192,9 @@ def lib():
     L.qd_scan_grid_closed.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, vp, dp, fp, dp,
                                       ctypes.POINTER(QdScanGridOpts), vp]
     L.qd_scan_grid_closed.restype = ctypes.c_int
+    L.qd_eval_points_ex.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, dp, dp, dp, dp,
+                                    ctypes.POINTER(QdPointsOpts), vp]
+    L.qd_eval_points_ex.restype = ctypes.c_int
     _LIB = L
     return L
 

@@ -70,6 +70,33 @@ class ModelFacade:
         """n_closed (..., N) float64; every row sums to n_charge."""
         return self._points(vg, vb, ("occupations",), n_charge=n_charge)[1]
 
+    def _levels(self, vg, vb, n_levels, n_charge=None):
+        if vb is None:
+            raise NotImplementedError("energy levels without barrier voltages: as charge_sensor_open, pass vb")
+        N = self.n_dot
+        vg, vb = np.asarray(vg, np.float64), np.asarray(vb, np.float64)
+        if vg.shape[-1:] != (N + 1,) or vb.shape[-1:] != (N - 1,) or vg.shape[:-1] != vb.shape[:-1]:
+            raise ValueError(f"vg must be (..., {N + 1}) and vb (..., {N - 1}) with equal leading shapes; "
+                             f"got {vg.shape} and {vb.shape}")
+        lead = vg.shape[:-1]
+        kw = {} if n_charge is None else {"n_charge": n_charge}
+        out = self._b.eval_points([0], vg.reshape(1, -1, N + 1), vb.reshape(1, -1, N - 1), outputs=(), levels=int(n_levels), **kw)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return (host(out["levels"]).astype(np.float64).reshape(lead + (int(n_levels),)),
+                host(out["hnorm"]).astype(np.float64).reshape(lead))
+
+    def energy_levels_open(self, vg, vb=None, n_levels=2):
+        """(levels (..., n_levels), hnorm (...)) float64: the n_levels (1..8) lowest eigenvalues, in increasing order and
+        counted with multiplicity, of the point's Hamiltonian over its valid kept charge states -- the reference's truncated
+        K-state matrix without the |0..0> padding copies, NOT the spectrum of the infinite system -- and its infinity norm.
+        Levels beyond the number of valid states are +inf.  (levels[..., 1] - levels[..., 0]) / hnorm is the relative gap
+        that says whether float64 resolves the point's ground vector (occupations and signal are round-off below ~1e-9)."""
+        return self._levels(vg, vb, n_levels)
+
+    def energy_levels_closed(self, vg, n_charge, n_levels=2, vb=None):
+        """energy_levels_open on the closed list: the kept states of the total-charge sector `n_charge`."""
+        return self._levels(vg, vb, n_levels, n_charge=n_charge)
+
     def _gate_axis(self, gate):
         """(axis, frame) of one gate of the composer's grammar, as the backend's scans take them"""
         N = self.n_dot

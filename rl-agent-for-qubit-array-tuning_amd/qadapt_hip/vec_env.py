@@ -748,7 +748,7 @@ class VecQuantumDeviceEnv:
         return out
 
     # ------------------------------------------------------------------ point evaluation
-    def eval_points(self, env_ids, vg, vb, gamma=None, outputs=("signal", "occupations"), n_charge=None, states=False):
+    def eval_points(self, env_ids, vg, vb, gamma=None, outputs=("signal", "occupations"), n_charge=None, states=False, levels=0):
         """The reference model's point function (qd_eval_points): `charge_sensor_open(vg, vb)` and `ground_state_open(vg, vb)`
         (TunnelCoupledChargeSensed.py:312-380) at arbitrary PHYSICAL voltages, on the devices of the listed envs.  Nothing of
         the episodes changes and no noise stage runs; an env may be named many times.
@@ -767,10 +767,20 @@ class VecQuantumDeviceEnv:
                     and occupations come from one solve
           states    True (closed regime only) adds "states": the kept charge states in list order, int32, zeros behind the
                     candidates found
-        Returns device tensors {"signal": (n, m) float64, "occupations": (n, m, N) float64[, "states": (n, m, K, N) int32]};
-        for list input, lists of n tensors (m_i,), (m_i, N) and (m_i, K, N)."""
+          levels    L in 1..8 adds "levels" and "hnorm" (qd_eval_points_ex, open or closed): per point the L lowest eigenvalues,
+                    increasing and counted with multiplicity, of H = diag(E) + H_t over the nv valid kept states -- the
+                    reference's truncated K-state Hamiltonian with the |0..0> padding copies left out, not the spectrum of
+                    the infinite system; +inf from level nv on -- and hnorm = ||H||_inf.  rel_gap = (levels[..., 1] -
+                    levels[..., 0]) / hnorm is the project's measure of whether float64 resolves the ground vector.  With
+                    levels > 0, outputs may be empty: then no ground-state kernel runs
+        Returns device tensors {"signal": (n, m) float64, "occupations": (n, m, N) float64[, "states": (n, m, K, N) int32]
+        [, "levels": (n, m, L) float64, "hnorm": (n, m) float64]}; for list input, lists of n tensors (m_i,), (m_i, N),
+        (m_i, K, N), (m_i, L) and (m_i,)."""
         outputs = tuple(outputs)
-        if not outputs or any(o not in ("signal", "occupations") for o in outputs):
+        levels = int(levels)
+        if not 0 <= levels <= _lib.QD_LEVELS_MAX:
+            raise ValueError(f"levels must be in 0..{_lib.QD_LEVELS_MAX}, got {levels}")
+        if (not outputs and levels == 0) or any(o not in ("signal", "occupations") for o in outputs):
             raise ValueError(f"outputs must name 'signal' and / or 'occupations', got {outputs!r}")
         N, C = self.N, self.C
         ids = np.asarray(env_ids.detach().cpu().numpy() if isinstance(env_ids, torch.Tensor) else env_ids, np.int32).reshape(-1)
@@ -818,7 +828,23 @@ class VecQuantumDeviceEnv:
         occ = torch.empty((total, N), dtype=torch.float64, device=self.device) if "occupations" in outputs else None
         K = self.num_charge_states
         kept = torch.empty((total, K, N), dtype=torch.int32, device=self.device) if states else None
-        if qh is not None:
+        lev = torch.empty((total, levels), dtype=torch.float64, device=self.device) if levels else None
+        hn = torch.empty((total,), dtype=torch.float64, device=self.device) if levels else None
+        if levels:
+            opts = _lib.QdPointsOpts(struct_size=ctypes.sizeof(_lib.QdPointsOpts), n_levels=levels)
+            if gam is not None:
+                opts.gamma_host = gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+            if qh is not None:
+                opts.n_charge_host = qh.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            opts.states_dst = None if kept is None else kept.data_ptr()
+            opts.levels_dst, opts.hnorm_dst = lev.data_ptr(), hn.data_ptr()
+            rc = 0 if total == 0 else self._lib.qd_eval_points_ex(
+                self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
+                ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
+                None if signal is None else ctypes.c_void_p(signal.data_ptr()),
+                None if occ is None else ctypes.c_void_p(occ.data_ptr()), ctypes.byref(opts), self._stream())
+            _lib.check(self._h, rc, "qd_eval_points_ex")
+        elif qh is not None:
             rc = 0 if total == 0 else self._lib.qd_eval_points_closed(
                 self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
                 ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
@@ -844,6 +870,9 @@ class VecQuantumDeviceEnv:
             out["signal"] = [signal[start[i]:start[i + 1]] for i in range(n)] if ragged else signal.reshape(n, m)
         if occ is not None:
             out["occupations"] = [occ[start[i]:start[i + 1]] for i in range(n)] if ragged else occ.reshape(n, m, N)
+        if levels:
+            out["levels"] = [lev[start[i]:start[i + 1]] for i in range(n)] if ragged else lev.reshape(n, m, levels)
+            out["hnorm"] = [hn[start[i]:start[i + 1]] for i in range(n)] if ragged else hn.reshape(n, m)
         return out
 
     # ------------------------------------------------------------------ reset
