@@ -635,6 +635,45 @@ int qd_eval_points_ex(qd_handle* h, const int32_t* group_env_host, const int64_t
                       const double* vg_dev, const double* vb_dev, double* signal_dst, double* occ_dst,
                       const qd_points_opts* opts, void* stream);
 
+/* FINITE TEMPERATURE per point: qd_eval_points_thermal is qd_eval_points / qd_eval_points_closed with the thermal state
+ * rho = exp(-H / kT) / Z in place of the ground state (csrc/qd_thermal.h, one kernel, one point per wavefront).
+ *   Hamiltonian.   The H of qd_eval_points_ex above: diag(E_0 .. E_{nv-1}) + H_t over the nv = min(nvalid, K) valid kept states,
+ *                  the |0..0> padding copies left out (a copy would carry Boltzmann weight of its own).
+ *   kT.            kT_host[g] > 0 and finite, one per group, in the energy units of the levels of qd_eval_points_ex.  The
+ *                  reference's conversion from its temperature field, as written, is kT = 8.617333262145e-5 * T.
+ *   Populations.   With H V = V diag(lam), w_k = exp(-(lam_k - lam_min) / kT) / Z:  P_m = sum_k w_k V[m,k]^2 is the
+ *                  probability of kept state s_m.  A weight that underflows to zero is expected.  At an exact degeneracy
+ *                  the state is the equal mixture: no point needs the rel_gap exemption of the ground state.  Pairs
+ *                  whose coupling is exactly zero never mix: tc == 0 gives the classical Boltzmann distribution.
+ *   Outputs.       occ_dst [points][N]: <n_d> = sum_m P_m s_m[d].  signal_dst [points]: the noise-free sensor signal of
+ *                  qd_eval_points evaluated at those occupations (c0 = 2 b + a (2 (Ns - v''_s) + 1), ten Lorentzians).
+ *                  opts->var_dst [points][N]: sum_m P_m (s_m[d] - <n_d>)^2.  opts->ztail_dst [points]: the normalised
+ *                  weight w of the HIGHEST of the nv levels.  Any of the four may be NULL.
+ *   Truncation.    The state is that of the reference's TRUNCATED K-state Hamiltonian, not of the infinite system.  ztail is
+ *                  the caller's check: where it is not negligible (against the accuracy wanted of <n>), states outside the
+ *                  kept list would carry weight too, and K kept states are too few for this kT.
+ *   Accuracy.      Populations within 4 (1e-12 ||H - min(diag H)||_inf + 1e-13 ||H||_inf) min(1 / kT, 1 / (lam_1 - lam_0))
+ *                  of an eigh of the oracle's matrix (tests/thermal_helpers.py).
+ * The call runs on the slot loop of its siblings (same slots, QD_POINTS_SLOTS, same scratch); the thermal kernel takes the
+ * place of the ground-state stage, on the list as the search left it, once: signal and occupations come from one solve.
+ * opts == NULL: the open regime and each env's own peak width.  Stateless, stream-ordered, deterministic: repeated calls
+ * give the same bits, and nothing any other call can see changes.
+ * QD_ERR_ARG (decided on the host, before anything is launched): what the siblings refuse; kT_host NULL; a kT that is not
+ * finite or not > 0; opts->struct_size != sizeof(qd_thermal_opts).  QD_ERR_STATE: QD_FLAG_VALIDATE handles and handles in the
+ * full charge-state space, as the siblings.  Temperature inside qd_step, probes, scans, lines and grids, noisy or latched
+ * thermal points and eigenvectors returned to the caller are not built. */
+typedef struct qd_thermal_opts {
+    int32_t struct_size;            /* = sizeof(qd_thermal_opts) */
+    int32_t reserved;               /* 0 */
+    const double*  gamma_host;      /* as qd_eval_points' gamma */
+    const int32_t* n_charge_host;   /* NULL: open regime; else the closed regime, as qd_eval_points_closed */
+    double* var_dst;                /* [points][N], device, may be NULL */
+    double* ztail_dst;              /* [points], device, may be NULL */
+} qd_thermal_opts;
+int qd_eval_points_thermal(qd_handle* h, const int32_t* group_env_host, const int64_t* group_start_host, int ng,
+                           const double* vg_dev, const double* vb_dev, const double* kT_host,
+                           double* signal_dst, double* occ_dst, const qd_thermal_opts* opts, void* stream);
+
 /* Stitches one channel of nx*ny probe signals into one composite image on the device (map_device_range.py:134-170,
  * map_full_device_range.py:168-194).  raw_dev [nx*ny][C][P] as qd_probe wrote it, query index i*ny + j for scan (i, j);
  * composite_dst [ny*R][nx*R] float32; both DEVICE memory, stream-ordered, no host wait.

@@ -18,6 +18,7 @@
 #include "qd_grid.h"
 #include "qd_closed.h"
 #include "qd_levels.h"
+#include "qd_thermal.h"
 #include "qd_scratch.h"
 
 // The owners of a stream and of an event.  With the two memory policies of qd_scratch.h these are the only places that
@@ -1241,9 +1242,12 @@ static int qd_points_slots(const qd_handle* h) { return h->chunk < QD_POINTS_MAX
 
 // qd_eval_points (n_charge null), qd_eval_points_closed and qd_eval_points_ex on one slot loop, as qd_grid_run.  n_levels > 0: the
 // levels kernel (qd_levels.h) behind the search of every flush; n_levels == 0 launches what the first two always launched.
+// kT (one per group, checked by the caller): qd_eval_points_thermal, the thermal kernel (qd_thermal.h) in place of the
+// ground-state stage, once, on the list as the search left it.
 static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
                          const double* vb, const double* gamma, const int32_t* n_charge, double* signal_dst, double* occ_dst,
-                         int32_t* states_dst, void* stream, int n_levels = 0, double* levels_dst = nullptr, double* hnorm_dst = nullptr) {
+                         int32_t* states_dst, void* stream, int n_levels = 0, double* levels_dst = nullptr, double* hnorm_dst = nullptr,
+                         const double* kT = nullptr, double* var_dst = nullptr, double* ztail_dst = nullptr) {
     static_assert(QD_POINTS_MAX_SLOTS == QD_POINTS_SLOTS, "qdsim.h states the bound");
     if (ng < 0) return qd_failf(h, QD_ERR_ARG, "%s: ng < 0", who);
     if (!group_env || !group_start) return qd_failf(h, QD_ERR_ARG, "%s: group_env_host or group_start_host is NULL", who);
@@ -1274,6 +1278,8 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
     memset(&T, 0, sizeof(T));
     QdClosedQ TQ;
     memset(&TQ, 0, sizeof(TQ));
+    QdThermalKT TK;
+    memset(&TK, 0, sizeof(TK));
     T.own_gamma = gamma ? 0 : 1;
     int n = 0;
     // one launch per `ps` slots: gather -> front end -> per-pixel search of the handed-over records -> ground state -> write
@@ -1302,6 +1308,20 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
             QD_DISPATCH_N(h->N, qd_k_levels<NN><<<lgrid, dim3(64), 0, s>>>(T, (int)CP, h->kept, n_levels, ln.recs.p, levels_dst, hnorm_dst));
             QD_HIP(hipGetLastError());
             if (!signal_dst && !occ_dst) { n = 0; return QD_OK; }          // levels only: no ground-state stage
+        }
+        if (kT) {
+            // the thermal state instead of the ground state: c0 and <n> into the slots' zraw and occ, then the unchanged write
+            const dim3 tgrid((unsigned)(CP < 4096 ? CP : 4096), n);
+            QD_DISPATCH_N(h->N, qd_k_thermal<NN><<<tgrid, dim3(64), 0, s>>>(T, TK, (int)CP, h->kept, qb.params, ln.recs.p, qb.zraw, qb.occ,
+                                                                           var_dst, ztail_dst));
+            QD_HIP(hipGetLastError());
+            if (signal_dst || occ_dst) {
+                QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, qb.params, qb.zraw, qb.occ,
+                                                                                               signal_dst, occ_dst));
+                QD_HIP(hipGetLastError());
+            }
+            n = 0;
+            return QD_OK;
         }
         // The signal comes from the list as the search left it, which is what qd_observe and qd_probe solve: the probe's bits.
         // The occupations come from the list in the reference order, which is what a validate handle solves and
@@ -1334,6 +1354,7 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
             T.start[n] = p0; T.env[n] = group_env[g]; T.cnt[n] = (int)(left < CP ? left : CP);
             T.gamma[n] = gamma ? gamma[g] : 0.0;
             TQ.q[n] = n_charge ? n_charge[g] : 0;
+            TK.kT[n] = kT ? kT[g] : 0.0;
             if (++n == ps) if (int rc = flush()) return rc;
         }
     }
@@ -1370,6 +1391,21 @@ extern "C" int qd_eval_points_ex(qd_handle* h, const int32_t* group_env, const i
         return qd_fail(h, QD_ERR_ARG, "qd_eval_points_ex: opts->states_dst is an output of the closed regime and needs opts->n_charge_host");
     return qd_points_run(h, "qd_eval_points_ex", group_env, group_start, ng, vg, vb, opts->gamma_host, opts->n_charge_host, signal_dst,
                          occ_dst, opts->states_dst, stream, opts->n_levels, opts->levels_dst, opts->hnorm_dst);
+}
+
+extern "C" int qd_eval_points_thermal(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
+                                      const double* vb, const double* kT, double* signal_dst, double* occ_dst,
+                                      const qd_thermal_opts* opts, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    if (!kT) return qd_fail(h, QD_ERR_ARG, "qd_eval_points_thermal: kT_host is NULL");
+    for (int g = 0; g < ng; ++g)
+        if (!(kT[g] > 0.0) || !(kT[g] < INFINITY))
+            return qd_fail(h, QD_ERR_ARG, "qd_eval_points_thermal: kT must be finite and > 0");
+    if (opts && opts->struct_size != (int32_t)sizeof(qd_thermal_opts))
+        return qd_fail(h, QD_ERR_ARG, "qd_eval_points_thermal: opts->struct_size is not sizeof(qd_thermal_opts)");
+    return qd_points_run(h, "qd_eval_points_thermal", group_env, group_start, ng, vg, vb, opts ? opts->gamma_host : nullptr,
+                         opts ? opts->n_charge_host : nullptr, signal_dst, occ_dst, nullptr, stream, 0, nullptr, nullptr, kT,
+                         opts ? opts->var_dst : nullptr, opts ? opts->ztail_dst : nullptr);
 }
 
 // numpy 'linear' percentile ranks of n values, as qd_k_percentile takes them

@@ -200,7 +200,8 @@ class DeviceSampler:
                    telegraph=dict(p01=d["telegraph"][:, 0], p10=d["telegraph"][:, 1] * d["telegraph"][:, 0],
                                   amplitude=d["telegraph"][:, 2]),
                    offset=d["offset"], radial=d["radial"],
-                   vc_alpha=d["vcap"][:, 0], vc_beta=d["vcap"][:, 1], vpw_alpha=d["vpw_alpha"][:, 0])
+                   vc_alpha=d["vcap"][:, 0], vc_beta=d["vcap"][:, 1], vpw_alpha=d["vpw_alpha"][:, 0],
+                   T=d["T"][:, 0])                 # the model's temperature field: extras["T"], used by the thermal point functions only
         for k in ("u_plunger_range", "u_plunger_center", "u_barrier_range", "u_barrier_center",
                   "u_start_plunger", "u_start_barrier"):
             out[k] = d[k]

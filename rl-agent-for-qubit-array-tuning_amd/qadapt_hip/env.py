@@ -26,7 +26,9 @@ class ModelFacade:
     The `_closed` siblings (TunnelCoupledChargeSensed.py:256-268, 291-309, 382-426) take the total charge `n_charge` of an
     array that is isolated from its reservoirs: the kept states are the lowest of that total-charge sector around the
     constrained continuous minimiser (DESIGN "closed regime"; the reference leaves its own ground-state half undefined), the
-    occupations of every point sum to n_charge, and the sensor half is the open one fed those occupations."""
+    occupations of every point sum to n_charge, and the sensor half is the open one fed those occupations.
+    `thermal_state_open / thermal_state_closed` are the same point functions at the model's temperature `T`, which the
+    reference samples and never uses: occupations, their variances and the signal of exp(-H / kT) / Z."""
 
     def __init__(self, backend, num_dots):
         self._b = backend
@@ -96,6 +98,51 @@ class ModelFacade:
     def energy_levels_closed(self, vg, n_charge, n_levels=2, vb=None):
         """energy_levels_open on the closed list: the kept states of the total-charge sector `n_charge`."""
         return self._levels(vg, vb, n_levels, n_charge=n_charge)
+
+    @property
+    def T(self):
+        """the device's sampled temperature (the model's `T` field), read from the backend at call time; NaN for a device
+        loaded from raw parameter blocks, None on a backend that keeps none"""
+        t = getattr(self._b, "_T_host", None)
+        return None if t is None else float(t[0])
+
+    def _thermal(self, vg, vb, T, n_charge=None):
+        if vb is None:
+            raise NotImplementedError("the thermal state without barrier voltages: as charge_sensor_open, pass vb")
+        N = self.n_dot
+        vg, vb = np.asarray(vg, np.float64), np.asarray(vb, np.float64)
+        if vg.shape[-1:] != (N + 1,) or vb.shape[-1:] != (N - 1,) or vg.shape[:-1] != vb.shape[:-1]:
+            raise ValueError(f"vg must be (..., {N + 1}) and vb (..., {N - 1}) with equal leading shapes; "
+                             f"got {vg.shape} and {vb.shape}")
+        if T is None:
+            T = self.T
+            if T is None or not np.isfinite(T):
+                raise ValueError("T=None needs the device's own sampled temperature, and this device was loaded from raw "
+                                 "parameter blocks, which carry none; pass T")
+        kT = 8.617333262145e-5 * float(T)
+        lead = vg.shape[:-1]
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        kw = {} if n_charge is None else {"n_charge": n_charge}
+        out = self._b.eval_points([0], vg.reshape(1, -1, N + 1), vb.reshape(1, -1, N - 1), gamma=gamma,
+                                  outputs=("signal", "occupations", "variance"), kT=kT, **kw)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return (host(out["signal"]).astype(np.float64).reshape(lead + (1,)),
+                host(out["occupations"]).astype(np.float64).reshape(lead + (N,)),
+                host(out["variance"]).astype(np.float64).reshape(lead + (N,)))
+
+    def thermal_state_open(self, vg, vb=None, T=None):
+        """(signal (..., 1), n (..., N), var (..., N)) float64 of the thermal state rho = exp(-H / kT) / Z of the point's
+        Hamiltonian over its valid kept charge states (the truncated K-state matrix of `energy_levels_open`): n the mean
+        occupations, var their variances, the signal that of `charge_sensor_open` evaluated at n.  `T` is the model's
+        temperature field and is converted by the reference's line as it is written (ground_state.py:48),
+        kT = 8.617333262145e-5 * T, which the reference itself never uses; the unit-free way in is `kT` on the backend's
+        `eval_points`, which also hands out "ztail", the check on the truncation.  T=None: the device's own sampled T
+        (`self.T`, the qarray_config draw); a device loaded from raw parameter blocks has none and raises ValueError."""
+        return self._thermal(vg, vb, T)
+
+    def thermal_state_closed(self, vg, n_charge, T=None, vb=None):
+        """thermal_state_open on the closed list: the kept states of the total-charge sector `n_charge`; every n sums to it."""
+        return self._thermal(vg, vb, T, n_charge=n_charge)
 
     def _gate_axis(self, gate):
         """(axis, frame) of one gate of the composer's grammar, as the backend's scans take them"""

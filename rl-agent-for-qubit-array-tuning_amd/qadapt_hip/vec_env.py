@@ -334,6 +334,7 @@ class VecQuantumDeviceEnv:
                                                       self.barrier_images.data_ptr(),
                                                       self.voltages.data_ptr()), "qd_bind_outputs")
         self._params_host = np.zeros((B, self.L.size))
+        self._T_host = np.full(B, np.nan)             # each device's sampled temperature (extras["T"]); NaN: loaded from raw blocks
         self._steps_host = np.zeros(B, np.int64)      # host mirror of the device step counters (truncation is
         self._needs_reset = True                      # deterministic, so auto-reset needs no device read-back)
         self.obs_count = 0
@@ -748,7 +749,8 @@ class VecQuantumDeviceEnv:
         return out
 
     # ------------------------------------------------------------------ point evaluation
-    def eval_points(self, env_ids, vg, vb, gamma=None, outputs=("signal", "occupations"), n_charge=None, states=False, levels=0):
+    def eval_points(self, env_ids, vg, vb, gamma=None, outputs=("signal", "occupations"), n_charge=None, states=False, *, kT=None,
+                    levels=0):
         """The reference model's point function (qd_eval_points): `charge_sensor_open(vg, vb)` and `ground_state_open(vg, vb)`
         (TunnelCoupledChargeSensed.py:312-380) at arbitrary PHYSICAL voltages, on the devices of the listed envs.  Nothing of
         the episodes changes and no noise stage runs; an env may be named many times.
@@ -773,14 +775,28 @@ class VecQuantumDeviceEnv:
                     the infinite system; +inf from level nv on -- and hnorm = ||H||_inf.  rel_gap = (levels[..., 1] -
                     levels[..., 0]) / hnorm is the project's measure of whether float64 resolves the ground vector.  With
                     levels > 0, outputs may be empty: then no ground-state kernel runs
+          kT        None: the T = 0 ground state, as above.  A scalar or (n,) values, finite and > 0, one per env id, in the energy
+                    units of `levels` (qd_eval_points_thermal): "signal" and "occupations" are those of the THERMAL state
+                    rho = exp(-H / kT) / Z of the same truncated Hamiltonian -- P_m = sum_k w_k V[m,k]^2 over the whole
+                    eigendecomposition, <n_d> = sum_m P_m s_m[d], the sensor signal evaluated at <n>; both from one solve --
+                    and outputs may also name "variance" (sum_m P_m (s_m[d] - <n_d>)^2) and "ztail", the normalised
+                    Boltzmann weight of the HIGHEST kept level: where that is not negligible the K kept states are too few for
+                    this kT.  Defined at exact degeneracies (the equal mixture): no point needs the rel_gap exemption.  With
+                    n_charge: the closed list.  Not together with levels or states=True: ask for those in a second call.
+                    (keyword only, as `levels` is from here on)
         Returns device tensors {"signal": (n, m) float64, "occupations": (n, m, N) float64[, "states": (n, m, K, N) int32]
-        [, "levels": (n, m, L) float64, "hnorm": (n, m) float64]}; for list input, lists of n tensors (m_i,), (m_i, N),
-        (m_i, K, N), (m_i, L) and (m_i,)."""
+        [, "levels": (n, m, L) float64, "hnorm": (n, m) float64][, "variance": (n, m, N), "ztail": (n, m) float64]}; for list
+        input, lists of n tensors (m_i,), (m_i, N), (m_i, K, N), (m_i, L), (m_i,), (m_i, N) and (m_i,)."""
         outputs = tuple(outputs)
         levels = int(levels)
         if not 0 <= levels <= _lib.QD_LEVELS_MAX:
             raise ValueError(f"levels must be in 0..{_lib.QD_LEVELS_MAX}, got {levels}")
-        if (not outputs and levels == 0) or any(o not in ("signal", "occupations") for o in outputs):
+        if kT is not None:
+            if levels or states:
+                raise ValueError("kT together with levels or states=True: ask for those in a second call")
+            if not outputs or any(o not in ("signal", "occupations", "variance", "ztail") for o in outputs):
+                raise ValueError(f"outputs must name 'signal', 'occupations', 'variance' and / or 'ztail', got {outputs!r}")
+        elif (not outputs and levels == 0) or any(o not in ("signal", "occupations") for o in outputs):
             raise ValueError(f"outputs must name 'signal' and / or 'occupations', got {outputs!r}")
         N, C = self.N, self.C
         ids = np.asarray(env_ids.detach().cpu().numpy() if isinstance(env_ids, torch.Tensor) else env_ids, np.int32).reshape(-1)
@@ -788,6 +804,12 @@ class VecQuantumDeviceEnv:
         if states and n_charge is None:
             raise ValueError("states=True needs n_charge: the kept states are an output of the closed regime")
         qh = None if n_charge is None else closed_charges(n_charge, n, "env id")
+        kth = None
+        if kT is not None:
+            kth = np.ascontiguousarray(np.broadcast_to(np.asarray(
+                kT.detach().cpu().numpy() if isinstance(kT, torch.Tensor) else kT, np.float64), (n,)))
+            if not (np.isfinite(kth).all() and (kth > 0).all()):
+                raise ValueError(f"kT must be finite and > 0, got {kT!r}")
         if states and self.num_charge_states is None:
             raise _lib.QdError(f"qd_eval_points_closed refused (code {_lib.QD_ERR_STATE}): the full charge-state space has no "
                                "kept list of K states")
@@ -830,7 +852,24 @@ class VecQuantumDeviceEnv:
         kept = torch.empty((total, K, N), dtype=torch.int32, device=self.device) if states else None
         lev = torch.empty((total, levels), dtype=torch.float64, device=self.device) if levels else None
         hn = torch.empty((total,), dtype=torch.float64, device=self.device) if levels else None
-        if levels:
+        var = torch.empty((total, N), dtype=torch.float64, device=self.device) if "variance" in outputs else None
+        zt = torch.empty((total,), dtype=torch.float64, device=self.device) if "ztail" in outputs else None
+        if kth is not None:
+            opts = _lib.QdThermalOpts(struct_size=ctypes.sizeof(_lib.QdThermalOpts))
+            if gam is not None:
+                opts.gamma_host = gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+            if qh is not None:
+                opts.n_charge_host = qh.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            opts.var_dst = None if var is None else var.data_ptr()
+            opts.ztail_dst = None if zt is None else zt.data_ptr()
+            rc = 0 if total == 0 else self._lib.qd_eval_points_thermal(
+                self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
+                ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
+                kth.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                None if signal is None else ctypes.c_void_p(signal.data_ptr()),
+                None if occ is None else ctypes.c_void_p(occ.data_ptr()), ctypes.byref(opts), self._stream())
+            _lib.check(self._h, rc, "qd_eval_points_thermal")
+        elif levels:
             opts = _lib.QdPointsOpts(struct_size=ctypes.sizeof(_lib.QdPointsOpts), n_levels=levels)
             if gam is not None:
                 opts.gamma_host = gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
@@ -873,6 +912,10 @@ class VecQuantumDeviceEnv:
         if levels:
             out["levels"] = [lev[start[i]:start[i + 1]] for i in range(n)] if ragged else lev.reshape(n, m, levels)
             out["hnorm"] = [hn[start[i]:start[i + 1]] for i in range(n)] if ragged else hn.reshape(n, m)
+        if var is not None:
+            out["variance"] = [var[start[i]:start[i + 1]] for i in range(n)] if ragged else var.reshape(n, m, N)
+        if zt is not None:
+            out["ztail"] = [zt[start[i]:start[i + 1]] for i in range(n)] if ragged else zt.reshape(n, m)
         return out
 
     # ------------------------------------------------------------------ reset
@@ -886,6 +929,7 @@ class VecQuantumDeviceEnv:
         u = np.stack([self._rngs[e].random(self.sampler.n_draws) for e in ids])
         eb = self.sampler.build(u)
         self._params_host[ids] = eb.params
+        self._T_host[ids] = eb.extras["T"]
         self.last_episode = eb
         ip = ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
         rc = self._lib.qd_load_episodes(self._h, ip, int(ids.size), eb.params.ctypes.data, eb.state.ctypes.data,
@@ -1032,12 +1076,13 @@ class VecQuantumDeviceEnv:
     # ------------------------------------------------------------------ checkpoint
     def get_checkpoint(self):
         """Everything needed to continue bit-identically (SURVEY 5 "expose RNG seeds/counters"): device state and
-        step counters, the current devices' parameter blocks, every env's host generator state, the Philox
-        observation counter of the stochastic stages and the synthetic CNN's call counter if one is used."""
+        step counters, the current devices' parameter blocks and sampled temperatures ("T"; a checkpoint without it restores
+        NaN), every env's host generator state, the Philox observation counter of the stochastic stages and the synthetic CNN's
+        call counter if one is used."""
         st, steps = self.get_state()
         ser = ctypes.c_uint64(0)
         _lib.check(self._h, self._lib.qd_get_rng_state(self._h, ctypes.byref(ser)), "qd_get_rng_state")
-        return {"state": st, "steps": steps, "params": self._params_host.copy(),
+        return {"state": st, "steps": steps, "params": self._params_host.copy(), "T": self._T_host.copy(),
                 "rng": [g.bit_generator.state for g in self._rngs], "obs_serial": int(ser.value),
                 "seed": self.seed, "env_id_offset": self.env_id_offset,
                 "capacitance_model_calls": getattr(self.capacitance_model, "calls", None)}
@@ -1054,6 +1099,7 @@ class VecQuantumDeviceEnv:
                                         params.ctypes.data, state.ctypes.data, 0, self._stream())
         _lib.check(self._h, rc, "qd_load_episodes")
         self._params_host[:] = params
+        self._T_host[:] = ck["T"] if "T" in ck else np.nan
         self.set_state(state, ck["steps"])
         for g, s_ in zip(self._rngs, ck["rng"]):
             g.bit_generator.state = s_
