@@ -15,11 +15,18 @@
 //   iters[n]         Laguerre iterations (validate only, else 0)
 //   err, errlen      text of a failure
 // Return: 0, 1 for a bad argument, 2 for a HIP failure (nothing is launched or read after one).
+//
+// Below them, the two one-point-per-wavefront cores of the point queries, csrc/qd_levels.h (qd_levels_solve) and
+// csrc/qd_thermal.h (qd_thermal_solve), behind qd_levels_load_packed in persistent single-wave blocks, the shape of
+// qd_k_levels / qd_k_thermal: qdg_levels and qdg_thermal, loaded by tests/test_gpu_spectrum_device.py.  Their arguments
+// are described where they are defined.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 #include <vector>
 #include "qd_fullspace.h"          // qd_kernels.h (size class -> solver, launch bounds), qd_eig_wave.h, the wide record
+#include "qd_thermal.h"            // qd_levels.h: the two cores and their workspaces
 
 // ---- per-lane classes: one task per lane in 256-thread blocks, as qd_k_gs_solve<BIN> runs a tile ----
 template <int BIN, bool VALIDATE>
@@ -223,5 +230,196 @@ extern "C" int qdg_prims(int n, const double* x, double* out, char* err, int err
     QDG_HIP(hipGetLastError());
     QDG_HIP(hipDeviceSynchronize());
     QDG_HIP(hipMemcpy(out, d.lam, 5 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The levels and the thermal core (csrc/qd_levels.h, csrc/qd_thermal.h).  Common arguments:
+//   n, sizes[n]      tasks and their block sizes, 1 .. 32
+//   packed, ld       task t's lower triangle, row-major, at packed + t * ld
+//   blocks           persistent single-wave blocks striding over the tasks; 0: one per task, at most 256
+//   poison           0: LDS as found.  1: before a block's first task every lane overwrites the whole __shared__ workspace
+//                    with all-ones bits (a NaN as a double, -1 as an int), then a barrier.  2: the same before every task
+// qdg_levels:  L in 1 .. QD_LEVELS_MAX;  lev[n][8]: the levels, +inf from min(L, s) on, as qd_k_levels writes them
+// qdg_thermal: kT[n] finite and > 0;  pop[n][32], lam[n][32] (zero from s on), ztail[n], sweeps[n], V[n][32][32] (row-major,
+//              zero outside the block; a null pointer skips it), and from the workspace after the solve, in the scaled units
+//              of the block (||A||_inf in [1, 2)):  asym[n] = max |A_ij - A_ji|,  off[n] = max over i != j of |A_ij|
+//              (NaN if any entry is; both 0 for s == 1, whose block the core never mirrors)
+// ---------------------------------------------------------------------------------------------------------------
+template <class WS>
+__device__ void qdg_poison(WS& W) {
+    static_assert(sizeof(WS) % 8 == 0, "whole 64-bit words");
+    unsigned long long* p = reinterpret_cast<unsigned long long*>(&W);
+    for (unsigned i = threadIdx.x; i < (unsigned)(sizeof(WS) / 8); i += 64u) p[i] = ~0ull;
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(64)
+qdg_k_levels(const double* __restrict__ packed, int ld, const int* __restrict__ sizes, unsigned n, int L, int poison,
+             double* __restrict__ lev_out) {
+    __shared__ QdLevelsWs W;
+    if (poison == 1) qdg_poison(W);
+    for (unsigned t = blockIdx.x; t < n; t += gridDim.x) {
+        if (poison == 2) qdg_poison(W);
+        const int s = __builtin_amdgcn_readfirstlane(sizes[t]);
+        qd_levels_load_packed(W, packed + (size_t)t * (size_t)ld, s);
+        qd_levels_solve(W, s, L);
+        if (threadIdx.x == 0)
+            for (int i = 0; i < QD_LEVELS_MAX; ++i) lev_out[(size_t)t * QD_LEVELS_MAX + i] = (i < L && i < s) ? W.lev[i] : INFINITY;
+        __syncthreads();                                   // (lane 0 has read W.lev before the next task overwrites it)
+    }
+}
+
+__global__ void __launch_bounds__(64)
+qdg_k_thermal(const double* __restrict__ packed, int ld, const int* __restrict__ sizes, const double* __restrict__ kT, unsigned n,
+              int poison, double* __restrict__ pop, double* __restrict__ lam, double* __restrict__ ztail, int* __restrict__ sweeps,
+              double* __restrict__ V, double* __restrict__ asym, double* __restrict__ off) {
+    __shared__ QdThermalWs W;
+    const int l = (int)threadIdx.x;
+    if (poison == 1) qdg_poison(W);
+    for (unsigned t = blockIdx.x; t < n; t += gridDim.x) {
+        if (poison == 2) qdg_poison(W);
+        const int s = __builtin_amdgcn_readfirstlane(sizes[t]);
+        qd_levels_load_packed(W.B, packed + (size_t)t * (size_t)ld, s);
+        const int sw = qd_thermal_solve(W, s, kT[t]);
+        // what is left of A: lane i takes row i; a NaN anywhere makes the figure NaN (fmax would drop it)
+        double da = 0.0, df = 0.0;
+        bool bad = false;
+        if (s > 1 && l < s)
+            for (int j = 0; j < s; ++j) {
+                const double a = W.B.A[l * QD_LV_LD + j], b = W.B.A[j * QD_LV_LD + l];
+                bad |= (a != a) | (b != b);
+                da = fmax(da, fabs(a - b));
+                if (j != l) df = fmax(df, fabs(a));
+            }
+        W.B.v[l] = bad ? NAN : da;
+        W.B.w[l] = bad ? NAN : df;
+        __syncthreads();
+        if (l < QD_LV_MAX) {
+            pop[(size_t)t * QD_LV_MAX + l] = l < s ? W.pop[l] : 0.0;
+            lam[(size_t)t * QD_LV_MAX + l] = l < s ? W.lam[l] : 0.0;
+        }
+        if (V)
+            for (int e = l; e < QD_LV_MAX * QD_LV_MAX; e += 64) {
+                const int i = e / QD_LV_MAX, j = e % QD_LV_MAX;
+                V[(size_t)t * (QD_LV_MAX * QD_LV_MAX) + e] = (i < s && j < s) ? W.V[i * QD_LV_LD + j] : 0.0;
+            }
+        if (l == 0) {
+            double ma = 0.0, mf = 0.0;
+            bool nan = false;
+            for (int i = 0; i < s; ++i) {
+                const double a = W.B.v[i], f = W.B.w[i];
+                nan |= (a != a) | (f != f);
+                ma = fmax(ma, a); mf = fmax(mf, f);
+            }
+            asym[t] = nan ? NAN : ma;
+            off[t] = nan ? NAN : mf;
+            ztail[t] = W.ztail;
+            sweeps[t] = sw;
+        }
+        __syncthreads();                                   // (the lanes have read W before the next task overwrites it)
+    }
+}
+
+namespace {
+
+// device buffers of one call, freed on every way out
+struct DevList {
+    std::vector<void*> p;
+    ~DevList() { for (void* q : p) (void)hipFree(q); }
+};
+
+// the checks both entry points share; smax out
+int spectrum_args(int n, const int* sizes, const double* packed, int ld, int blocks, int poison, char* err, int errlen) {
+    if (n < 1 || !sizes || !packed) return bad_arg(err, errlen, "null argument or n < 1");
+    int smax = 0;
+    for (int t = 0; t < n; ++t) {
+        if (sizes[t] < 1 || sizes[t] > QD_LV_MAX) return bad_arg(err, errlen, "block size outside 1..32");
+        if (sizes[t] > smax) smax = sizes[t];
+    }
+    if (ld < smax * (smax + 1) / 2) return bad_arg(err, errlen, "ld too small");
+    if (blocks < 0 || blocks > 65535) return bad_arg(err, errlen, "blocks outside 0..65535");
+    if (poison < 0 || poison > 2) return bad_arg(err, errlen, "poison outside 0..2");
+    return 0;
+}
+
+#define QDG_ALLOC(ptr, bytes)                                  \
+    do {                                                       \
+        void* q_ = nullptr;                                    \
+        QDG_HIP(hipMalloc(&q_, (bytes)));                      \
+        d.p.push_back(q_);                                     \
+        (ptr) = reinterpret_cast<decltype(ptr)>(q_);           \
+    } while (0)
+
+}  // namespace
+
+extern "C" int qdg_levels(int n, const int* sizes, const double* packed, int ld, int L, int blocks, int poison, double* lev,
+                          char* err, int errlen) {
+    if (err && errlen > 0) err[0] = 0;
+    if (int rc = spectrum_args(n, sizes, packed, ld, blocks, poison, err, errlen)) return rc;
+    if (!lev) return bad_arg(err, errlen, "null output");
+    if (L < 1 || L > QD_LEVELS_MAX) return bad_arg(err, errlen, "L outside 1..8");
+    const size_t un = (size_t)n, pb = un * (size_t)ld * sizeof(double), lb = un * QD_LEVELS_MAX * sizeof(double);
+    DevList d;
+    double *dpk, *dlev;
+    int* dsz;
+    QDG_ALLOC(dpk, pb);
+    QDG_ALLOC(dsz, un * sizeof(int));
+    QDG_ALLOC(dlev, lb);
+    QDG_HIP(hipMemcpy(dpk, packed, pb, hipMemcpyHostToDevice));
+    QDG_HIP(hipMemcpy(dsz, sizes, un * sizeof(int), hipMemcpyHostToDevice));
+    QDG_HIP(hipMemset(dlev, 0xFF, lb));
+    const dim3 grid(blocks > 0 ? (unsigned)blocks : (n < 256 ? (unsigned)n : 256u)), block(64);
+    qdg_k_levels<<<grid, block>>>(dpk, ld, dsz, (unsigned)n, L, poison, dlev);
+    QDG_HIP(hipGetLastError());
+    QDG_HIP(hipDeviceSynchronize());
+    QDG_HIP(hipMemcpy(lev, dlev, lb, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int qdg_thermal(int n, const int* sizes, const double* packed, int ld, const double* kT, int blocks, int poison,
+                           double* pop, double* lam, double* ztail, int* sweeps, double* V, double* asym, double* off, char* err,
+                           int errlen) {
+    if (err && errlen > 0) err[0] = 0;
+    if (int rc = spectrum_args(n, sizes, packed, ld, blocks, poison, err, errlen)) return rc;
+    if (!kT || !pop || !lam || !ztail || !sweeps || !asym || !off) return bad_arg(err, errlen, "null argument");
+    for (int t = 0; t < n; ++t)
+        if (!(kT[t] > 0.0) || !isfinite(kT[t])) return bad_arg(err, errlen, "kT must be finite and > 0");
+    const size_t un = (size_t)n, pb = un * (size_t)ld * sizeof(double), vb = un * QD_LV_MAX * sizeof(double),
+                 sb = un * sizeof(double), Vb = un * QD_LV_MAX * QD_LV_MAX * sizeof(double);
+    DevList d;
+    double *dpk, *dkt, *dpop, *dlam, *dzt, *dV = nullptr, *dasym, *doff;
+    int *dsz, *dsw;
+    QDG_ALLOC(dpk, pb);
+    QDG_ALLOC(dsz, un * sizeof(int));
+    QDG_ALLOC(dkt, sb);
+    QDG_ALLOC(dpop, vb);
+    QDG_ALLOC(dlam, vb);
+    QDG_ALLOC(dzt, sb);
+    QDG_ALLOC(dsw, un * sizeof(int));
+    QDG_ALLOC(dasym, sb);
+    QDG_ALLOC(doff, sb);
+    if (V) QDG_ALLOC(dV, Vb);
+    QDG_HIP(hipMemcpy(dpk, packed, pb, hipMemcpyHostToDevice));
+    QDG_HIP(hipMemcpy(dsz, sizes, un * sizeof(int), hipMemcpyHostToDevice));
+    QDG_HIP(hipMemcpy(dkt, kT, sb, hipMemcpyHostToDevice));
+    QDG_HIP(hipMemset(dpop, 0xFF, vb));
+    QDG_HIP(hipMemset(dlam, 0xFF, vb));
+    QDG_HIP(hipMemset(dzt, 0xFF, sb));
+    QDG_HIP(hipMemset(dsw, 0xFF, un * sizeof(int)));
+    QDG_HIP(hipMemset(dasym, 0xFF, sb));
+    QDG_HIP(hipMemset(doff, 0xFF, sb));
+    if (V) QDG_HIP(hipMemset(dV, 0xFF, Vb));
+    const dim3 grid(blocks > 0 ? (unsigned)blocks : (n < 256 ? (unsigned)n : 256u)), block(64);
+    qdg_k_thermal<<<grid, block>>>(dpk, ld, dsz, dkt, (unsigned)n, poison, dpop, dlam, dzt, dsw, dV, dasym, doff);
+    QDG_HIP(hipGetLastError());
+    QDG_HIP(hipDeviceSynchronize());
+    QDG_HIP(hipMemcpy(pop, dpop, vb, hipMemcpyDeviceToHost));
+    QDG_HIP(hipMemcpy(lam, dlam, vb, hipMemcpyDeviceToHost));
+    QDG_HIP(hipMemcpy(ztail, dzt, sb, hipMemcpyDeviceToHost));
+    QDG_HIP(hipMemcpy(sweeps, dsw, un * sizeof(int), hipMemcpyDeviceToHost));
+    QDG_HIP(hipMemcpy(asym, dasym, sb, hipMemcpyDeviceToHost));
+    QDG_HIP(hipMemcpy(off, doff, sb, hipMemcpyDeviceToHost));
+    if (V) QDG_HIP(hipMemcpy(V, dV, Vb, hipMemcpyDeviceToHost));
     return 0;
 }

@@ -533,3 +533,66 @@ def test_facade_energy_levels(tmp_path):
     with pytest.raises(NotImplementedError):
         model.energy_levels_open(vg)
     env.close()
+
+
+# ------------------------------------------------------------------ 10. more than one point per block
+TRIP_BLOCKS = 4096                                       # blocks per slot of qd_k_levels / qd_k_thermal, at most
+
+
+def _second_trip_points(N, R):
+    """C P points on one 3-dot device (R = 48: C P = 4608, the smallest slot above 4096), ordered for a launch whose blocks stride
+    over a full slot: block j solves point j and, for j < C P - 4096, point j + 4096 on the same __shared__ workspace.  Around the
+    optimum the oracle keeps 32 valid states where a floor is above zero and 27 (the deltas 0, 1, 2 of every dot) where the array
+    is empty: the first trip of those blocks gets lists of 32, their second trip lists of 27, the odd size whose idle index the
+    Jacobi ordering needs zeroed.  -> (params, state, dev, vg, vb, states, nv) with the oracle's kept lists"""
+    CP = (N - 1) * R * R
+    assert CP > TRIP_BLOCKS
+    eb = H.sample_blocks(N, [61])
+    par = eb.params[0]
+    L = layout(N)
+    dev = H.dev_view(N, par)
+    rng = np.random.default_rng(8950)
+    vg = par[L.vopt:L.vopt + N + 1] + rng.uniform(-4, 4, (CP, N + 1))
+    vb = par[L.vbopt:L.vbopt + N - 1] + rng.uniform(-3, 3, (CP, N - 1))
+    states, nv = _open_lists(dev, vg, vb, 32)
+    again = CP - TRIP_BLOCKS
+    big, small = np.flatnonzero(nv == nv.max()), np.flatnonzero(nv < nv.max())
+    assert big.size >= again and small.size >= again, (big.size, small.size)
+    head, tail = big[:again], small[-again:]
+    rest = np.setdiff1d(np.arange(CP), np.concatenate([head, tail]))
+    order = np.concatenate([head, rest, tail])
+    vg, vb, states, nv = vg[order], vb[order], states[order], nv[order]
+    first, second = nv[:again], nv[TRIP_BLOCKS:]
+    assert np.sum(second < first) >= 100, "too few blocks that see a smaller block after a larger one"
+    assert np.any((second % 2 == 1) & (first % 2 == 0) & (first > second)), "no block sees an odd size after a larger even one"
+    return eb.params, eb.state, dev, vg, vb, states, nv
+
+
+def _subsample(CP):
+    """256 points of the slot: of the first and of the second trip, and from the blocks that take one trip"""
+    pick = np.concatenate([np.arange(0, 64), np.arange(TRIP_BLOCKS, TRIP_BLOCKS + 64),
+                           np.random.default_rng(8951).choice(np.arange(64, TRIP_BLOCKS), 128, replace=False)])
+    assert pick.size == 256 and pick.max() < CP
+    return pick
+
+
+def test_second_point_of_a_block_keeps_nothing_from_the_first(tmp_path):
+    """one group of exactly C P points fills one slot, whose 4096 blocks stride over it: 512 of them solve a second point.  The
+    same points as two groups of half the size (two slots, one point per block): the same levels and norm, bit for bit, and 256
+    of those within the module's bound of the oracle, so that the equality is not one of two wrong answers"""
+    N, R = 3, 48
+    params, state, dev, vg, vb, states, nv = _second_trip_points(N, R)
+    CP = vg.shape[0]
+    env = _vec(tmp_path, 1, N, R, 61)
+    _load(env, params, state)
+    one = env.eval_points([0], vg[None], vb[None], outputs=(), levels=8)
+    half = CP // 2
+    two = env.eval_points([0, 0], vg.reshape(2, half, N + 1), vb.reshape(2, half, N - 1), outputs=(), levels=8)
+    lev1, hn1 = _np(one["levels"]).reshape(CP, 8), _np(one["hnorm"]).reshape(CP)
+    lev2, hn2 = _np(two["levels"]).reshape(CP, 8), _np(two["hnorm"]).reshape(CP)
+    diff = np.flatnonzero((lev1.view(np.uint64) != lev2.view(np.uint64)).any(axis=1) | (hn1.view(np.uint64) != hn2.view(np.uint64)))
+    assert diff.size == 0, (diff.size, diff[:8], nv[diff[:8]])
+    pick = _subsample(CP)
+    lev_ref, hn_ref, tc = _spectrum(dev, vg[pick], vb[pick], states[pick], nv[pick])
+    _compare(f"two trips N={N} R={R} (tc up to {tc.max():.1e})", lev2[pick], hn2[pick], lev_ref, hn_ref)
+    env.close()

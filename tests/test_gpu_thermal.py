@@ -465,3 +465,29 @@ def test_facade_thermal_state(tmp_path):
         model.thermal_state_open(vg, vb)
     assert model.thermal_state_open(vg, vb, T=T)[1].shape == (12, N)
     env.close()
+
+
+# ------------------------------------------------------------------ 9. more than one point per block
+def test_second_point_of_a_block_keeps_nothing_from_the_first(tmp_path):
+    """the slot of C P = 4608 points of test_gpu_levels.py, whose first 512 blocks solve a list of 32 states and then one of 27 on
+    the same workspace (V, the upper triangle and the zeroed idle row and column of the point before are still in it), against
+    the same points in two slots with one point per block: occupations, variance, ztail and signal bit for bit, and 256 of them
+    against the reference"""
+    from test_gpu_levels import _second_trip_points, _subsample
+    N, R = 3, 48
+    params, state, dev, vg, vb, states, nv = _second_trip_points(N, R)
+    CP = vg.shape[0]
+    env = _vec(tmp_path, 1, N, R, 61)
+    _load(env, params, state)
+    one = env.eval_points([0], vg[None], vb[None], kT=KT_100K, outputs=ALL)
+    half = CP // 2
+    two = env.eval_points([0, 0], vg.reshape(2, half, N + 1), vb.reshape(2, half, N - 1), kT=KT_100K, outputs=ALL)
+    for key in ALL:
+        a, b = np.ascontiguousarray(_np(one[key]).reshape(CP, -1)), np.ascontiguousarray(_np(two[key]).reshape(CP, -1))
+        diff = np.flatnonzero((a.view(np.uint64) != b.view(np.uint64)).any(axis=1))
+        assert diff.size == 0, (key, diff.size, diff[:8], nv[diff[:8]])
+    pick = _subsample(CP)
+    Hs, _ = TH.hamiltonians(dev, vg[pick], vb[pick], states[pick], nv[pick])
+    flat = {k: _np(two[k]).reshape((CP,) + _np(two[k]).shape[2:])[pick][None] for k in ALL}
+    _check(f"two trips N={N} R={R} kT={KT_100K:.2e}", N, params[0], vg[pick], vb[pick], Hs, states[pick], nv[pick], KT_100K, flat, 0)
+    env.close()
