@@ -660,8 +660,8 @@ int qd_eval_points_ex(qd_handle* h, const int32_t* group_env_host, const int64_t
  * give the same bits, and nothing any other call can see changes.
  * QD_ERR_ARG (decided on the host, before anything is launched): what the siblings refuse; kT_host NULL; a kT that is not
  * finite or not > 0; opts->struct_size != sizeof(qd_thermal_opts).  QD_ERR_STATE: QD_FLAG_VALIDATE handles and handles in the
- * full charge-state space, as the siblings.  Temperature inside qd_step, probes, scans, lines and grids, noisy or latched
- * thermal points and eigenvectors returned to the caller are not built. */
+ * full charge-state space, as the siblings.  Grids at a temperature are qd_scan_grid_thermal below.  Temperature inside
+ * qd_step, probes, scans and lines, noisy or latched thermal points and eigenvectors returned to the caller are not built. */
 typedef struct qd_thermal_opts {
     int32_t struct_size;            /* = sizeof(qd_thermal_opts) */
     int32_t reserved;               /* 0 */
@@ -673,6 +673,44 @@ typedef struct qd_thermal_opts {
 int qd_eval_points_thermal(qd_handle* h, const int32_t* group_env_host, const int64_t* group_start_host, int ng,
                            const double* vg_dev, const double* vb_dev, const double* kT_host,
                            double* signal_dst, double* occ_dst, const qd_thermal_opts* opts, void* stream);
+
+/* FINITE TEMPERATURE on a grid: qd_scan_grid_thermal is qd_scan_grid / qd_scan_grid_closed with the thermal state of
+ * qd_eval_points_thermal at every point in place of the ground state -- the thermally broadened charge-stability diagram.
+ * It takes the arguments of qd_scan_grid and
+ *   kT_dev         [nq] DEVICE float64: kT of each query, finite and > 0, in the units of qd_eval_points_thermal.  The call reads
+ *                  it back for this check and waits for `stream` once, as qd_scan_grid_closed does for n_charge_dev
+ *   topts          NULL: the open regime, no further outputs.  n_charge_dev [nq] DEVICE int32 or NULL: the closed regime of
+ *                  qd_scan_grid_closed.  var_dst [nq][ny][nx][N], ztail_dst [nq][ny][nx] DEVICE float64 or NULL: the variances
+ *                  of the occupations and the normalised weight of the highest kept level, as qd_eval_points_thermal defines them
+ * Hamiltonian, populations, truncation and accuracy are those of qd_eval_points_thermal.  raw, image, plohi and opts->occ_dst are
+ * those of the thermal state: the sensor expression at <n>, the grid's own percentiles of that signal.
+ * The call runs qd_scan_grid's slot loop with ONE kernel exchanged: the thermal grid kernel of csrc/qd_thermal_blocks.h, one
+ * point per wavefront, takes the place of the ground-state kernels.  Its solver is not the one of qd_eval_points_thermal: the Jacobi
+ * iteration runs inside the connected components of the coupling pattern only (states of different components never mix;
+ * exact zeros do not link), so a sweep has as many rounds as the largest component needs, not as the whole list.  The two
+ * calls agree within the sum of their tolerances at the same voltages and are NOT bitwise equal in the open regime.  A closed
+ * list is one total-charge sector, which hops connect: one component, so the closed regime runs the kernel on the whole-block
+ * solver of qd_eval_points_thermal, and a closed thermal grid in the physical frame equals that call at the grid's voltages
+ * bit for bit, as qd_scan_grid_closed equals qd_eval_points_closed.  Results do not depend on how queries fall into launches,
+ * and repeated calls give the same bits.
+ * Noise: QD_NOISE_SENSOR is allowed in the open regime (the sensor stage reads the thermal c0 alone).  QD_NOISE_LATCH is
+ * QD_ERR_ARG: the latching model holds an integer configuration, and a thermal mean has none.
+ * QD_ERR_ARG: what qd_scan_grid refuses; kT_dev NULL; a kT that is not finite or not > 0; topts->struct_size !=
+ * sizeof(qd_grid_thermal_opts); QD_NOISE_LATCH; any noise flag together with n_charge_dev; an n_charge outside 0..32767.
+ * QD_ERR_STATE: QD_FLAG_VALIDATE handles and handles in the full charge-state space.  Stateless and stream-ordered as its
+ * siblings, on their scratch; nothing any other call can see changes.  Temperature in qd_scan1d, qd_scan2d, qd_scan_affine,
+ * probes and qd_step, levels over a grid and latched thermal points are not built. */
+typedef struct qd_grid_thermal_opts {
+    int32_t struct_size;            /* = sizeof(qd_grid_thermal_opts) */
+    int32_t reserved;               /* 0 */
+    const int32_t* n_charge_dev;    /* NULL: open regime; else [nq], the closed regime, as qd_scan_grid_closed */
+    double* var_dst;                /* [nq][ny][nx][N], device, may be NULL */
+    double* ztail_dst;              /* [nq][ny][nx], device, may be NULL */
+} qd_grid_thermal_opts;
+int qd_scan_grid_thermal(qd_handle* h, const int32_t* env_of_query_dev, int nq, int nx, int ny, const double* dir_dev,
+                         const double* range_dev, const double* gate_v_dev, const double* barrier_v_dev,
+                         const double* sensor_v_dev, const double* kT_dev, double* raw_dst, float* image_dst,
+                         double* plohi_dst, const qd_scan_grid_opts* opts, const qd_grid_thermal_opts* topts, void* stream);
 
 /* Stitches one channel of nx*ny probe signals into one composite image on the device (map_device_range.py:134-170,
  * map_full_device_range.py:168-194).  raw_dev [nx*ny][C][P] as qd_probe wrote it, query index i*ny + j for scan (i, j);

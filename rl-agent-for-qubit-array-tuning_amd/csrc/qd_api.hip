@@ -19,6 +19,7 @@
 #include "qd_closed.h"
 #include "qd_levels.h"
 #include "qd_thermal.h"
+#include "qd_thermal_blocks.h"
 #include "qd_scratch.h"
 
 // The owners of a stream and of an event.  With the two memory policies of qd_scratch.h these are the only places that
@@ -1118,11 +1119,15 @@ extern "C" int qd_scan1d(qd_handle* h, const int32_t* env_of_query, int nq, int 
 }
 
 // qd_scan_grid (n_charge null) and qd_scan_grid_closed on one slot loop: the closed regime replaces the redo pass of the open
-// search by qd_k_closed at the queries' total charges and leaves every other launch as it is.
+// search by qd_k_closed at the queries' total charges and leaves every other launch as it is.  kT ([nq], device):
+// qd_scan_grid_thermal, the thermal kernel of qd_thermal_blocks.h in place of the ground-state stage, once, on the lists as the
+// search left them; the slots always carry occupations then.
 static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
                        const double* range, const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst,
-                       float* image_dst, double* plohi_dst, const qd_scan_grid_opts* opts, const int32_t* n_charge, void* stream) {
+                       float* image_dst, double* plohi_dst, const qd_scan_grid_opts* opts, const int32_t* n_charge, void* stream,
+                       const double* kT = nullptr, double* var_dst = nullptr, double* ztail_dst = nullptr) {
     static_assert(QD_GRID_MAX_SLOTS == QD_GRID_SLOTS, "qdsim.h states the bound");
+    static_assert(QD_THG_BLOCKS <= QD_GRID_MAX_SLOTS, "a launch dimension");
     if (nq < 0) return qd_failf(h, QD_ERR_ARG, "%s: nq < 0", who);
     if (!env_of_query || !dir || !range) return qd_failf(h, QD_ERR_ARG, "%s: env_of_query_dev, dir_dev or range_dev is NULL", who);
     if (!gate_v || !barrier_v) return qd_failf(h, QD_ERR_ARG, "%s: gate_v_dev or barrier_v_dev is NULL", who);
@@ -1137,6 +1142,9 @@ static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_quer
     if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_LATCH)))
         return qd_failf(h, QD_ERR_ARG, "%s: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
                                       "centred on the env's own adjacent-pair observation)", who);
+    if (kT && opts && (opts->noise_flags & QD_NOISE_LATCH))
+        return qd_failf(h, QD_ERR_ARG, "%s: QD_NOISE_LATCH has no thermal form: the latching model holds an integer "
+                                      "configuration, a thermal mean has none", who);
     if (h->cfg.flags & QD_FLAG_VALIDATE)
         return qd_failf(h, QD_ERR_STATE, "%s: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
                                         "B envs' last observe and renders no grids; use a handle without the flag", who);
@@ -1160,11 +1168,23 @@ static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_quer
         if (e_ != hipSuccess) return qd_fail(h, QD_ERR_HIP, "hipMemcpyAsync(n_charge)", e_);
         if (bad) return qd_failf(h, QD_ERR_ARG, "%s: n_charge must be in 0..32767", who);
     }
+    if (kT) {
+        // as n_charge: one copy of nq doubles and a wait for the stream
+        double* th = (double*)malloc(sizeof(double) * (size_t)nq);
+        if (!th) return qd_fail(h, QD_ERR_NOMEM, "malloc");
+        hipError_t e_ = hipMemcpyAsync(th, kT, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, s);
+        if (e_ == hipSuccess) e_ = hipStreamSynchronize(s);
+        bool bad = false;
+        for (int q = 0; q < nq && e_ == hipSuccess; ++q) bad = bad || !(th[q] > 0.0) || !(th[q] < INFINITY);
+        free(th);
+        if (e_ != hipSuccess) return qd_fail(h, QD_ERR_HIP, "hipMemcpyAsync(kT)", e_);
+        if (bad) return qd_failf(h, QD_ERR_ARG, "%s: kT must be finite and > 0", who);
+    }
     const int noise_flags = opts ? opts->noise_flags : 0;
     const unsigned long long serial = opts ? opts->serial : 0;
     const long long stream_base = opts ? opts->stream_base : 0;
     double* const occ_dst = opts ? opts->occ_dst : nullptr;
-    const bool want_occ = (noise_flags & QD_NOISE_LATCH) || occ_dst, want_tel = (noise_flags & QD_NOISE_SENSOR) != 0;
+    const bool want_occ = (noise_flags & QD_NOISE_LATCH) || occ_dst || kT, want_tel = (noise_flags & QD_NOISE_SENSOR) != 0;
     const QdAffineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, opts ? opts->vgm_dev : nullptr,
                           opts ? opts->gamma_dev : nullptr, opts ? opts->frame : QD_SCAN_VIRTUAL};
     // the slot of a grid is that of a line of nx*ny points: side x side records, record p = y*nx + x, the tail inert
@@ -1199,7 +1219,20 @@ static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_quer
         QD_HIP(hipGetLastError());
         if (n_charge) { if (int rc = qd_launch_closed(h, b, ln, SP, n_charge + base, cnt, s)) return rc; }
         else if (int rc = qd_launch_candidates(h, b, ln, nullptr, 0, cnt, s, true)) return rc;
-        if (int rc = qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND)) return rc;
+        if (kT) {
+            // the thermal state instead of the ground state: c0 and <n> into the slots' zraw and occ, then the unchanged stages
+            const dim3 tgrid((unsigned)(n < QD_THG_BLOCKS ? n : QD_THG_BLOCKS), cnt);
+            // (a closed list is one hop component: the whole-block core, see qd_k_thermal_grid)
+            if (n_charge) {
+                QD_DISPATCH_N(h->N, qd_k_thermal_grid<NN, QdThermalWs><<<tgrid, dim3(64), 0, s>>>(Q, base, h->B, n, SP, h->kept, kT, b.params,
+                                                                                                ln.recs.p, b.zraw, b.occ, var_dst, ztail_dst));
+            } else {
+                QD_DISPATCH_N(h->N, qd_k_thermal_grid<NN, QdThermalBlocksWs><<<tgrid, dim3(64), 0, s>>>(Q, base, h->B, n, SP, h->kept, kT,
+                                                                                                      b.params, ln.recs.p, b.zraw, b.occ,
+                                                                                                      var_dst, ztail_dst));
+            }
+            QD_HIP(hipGetLastError());
+        } else if (int rc = qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND)) return rc;
         if (noise_flags & QD_NOISE_LATCH) {
             const long rows = (long)cnt * ny;
             QD_DISPATCH_N(h->N, qd_k_latch_grid<NN><<<dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s>>>(cnt, nx, ny, SP, b.params, b.occ,
@@ -1235,6 +1268,19 @@ extern "C" int qd_scan_grid_closed(qd_handle* h, const int32_t* env_of_query, in
     if (!n_charge) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_closed: n_charge_dev is NULL");
     return qd_grid_run(h, "qd_scan_grid_closed", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
                        plohi_dst, opts, n_charge, stream);
+}
+
+extern "C" int qd_scan_grid_thermal(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
+                                    const double* range, const double* gate_v, const double* barrier_v, const double* sensor_v,
+                                    const double* kT, double* raw_dst, float* image_dst, double* plohi_dst,
+                                    const qd_scan_grid_opts* opts, const qd_grid_thermal_opts* topts, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    if (!kT) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_thermal: kT_dev is NULL");
+    if (topts && topts->struct_size != (int32_t)sizeof(qd_grid_thermal_opts))
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_thermal: topts->struct_size is not sizeof(qd_grid_thermal_opts)");
+    return qd_grid_run(h, "qd_scan_grid_thermal", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
+                       plohi_dst, opts, topts ? topts->n_charge_dev : nullptr, stream, kT, topts ? topts->var_dst : nullptr,
+                       topts ? topts->ztail_dst : nullptr);
 }
 
 // slots in flight of qd_eval_points: one launch chunk of lane 0's records, at most QD_POINTS_SLOTS

@@ -32,7 +32,7 @@ EXPORTS = [
     "qd_time_ground_kernel", "qd_time_candidates_kernel", "qd_time_kernels", "qd_timed_kernel_name", "qd_chunk_envs",
     "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex", "qd_scan_affine",
     "qd_scan_grid", "qd_eval_points_closed", "qd_scan_grid_closed", "qd_eval_points_ex",
-    "qd_eval_points_thermal",
+    "qd_eval_points_thermal", "qd_scan_grid_thermal",
 ]
 # exported too, kept apart: names with a digit, which a scan of qdsim.h for `qd_[a-z_]+(` does not find
 EXPORTS_WITH_DIGITS = ["qd_scan2d", "qd_scan1d"]
@@ -109,6 +109,15 @@ class QdThermalOpts(ctypes.Structure):
     _fields_ = [
         ("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("gamma_host", ctypes.POINTER(ctypes.c_double)),
         ("n_charge_host", ctypes.POINTER(ctypes.c_int32)), ("var_dst", ctypes.c_void_p), ("ztail_dst", ctypes.c_void_p),
+    ]
+
+
+class QdGridThermalOpts(ctypes.Structure):
+    """qd_grid_thermal_opts of include/qdsim.h: the (closed regime) total charges of the queries of a qd_scan_grid_thermal call
+    and the destinations of the occupation variances and the tail weights, all on the device."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_charge_dev", ctypes.c_void_p),
+        ("var_dst", ctypes.c_void_p), ("ztail_dst", ctypes.c_void_p),
     ]
 
 
@@ -208,6 +217,9 @@ def lib():
     L.qd_eval_points_thermal.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, dp, dp, ctypes.POINTER(ctypes.c_double),
                                          dp, dp, ctypes.POINTER(QdThermalOpts), vp]
     L.qd_eval_points_thermal.restype = ctypes.c_int
+    L.qd_scan_grid_thermal.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, dp, dp, fp, dp,
+                                       ctypes.POINTER(QdScanGridOpts), ctypes.POINTER(QdGridThermalOpts), vp]
+    L.qd_scan_grid_thermal.restype = ctypes.c_int
     _LIB = L
     return L
 

@@ -227,6 +227,49 @@ class ModelFacade:
         host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
         return (host(out["raw"]).astype(np.float64)[0][:, :, None], host(out["occupations"]).astype(np.float64)[0])
 
+    def _grid_kT(self, T):
+        """kT of a thermal grid by the rule of _thermal: the reference's line as written, T=None the device's sampled T"""
+        if T is None:
+            T = self.T
+            if T is None or not np.isfinite(T):
+                raise ValueError("T=None needs the device's own sampled temperature, and this device was loaded from raw "
+                                 "parameter blocks, which carry none; pass T")
+        return 8.617333262145e-5 * float(T)
+
+    def do2d_thermal(self, x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points, T=None, n_charge=None):
+        """do2d_open (n_charge None) or do2d_closed at the model's temperature: the grid of thermal_state_open /
+        thermal_state_closed, rendered by the backend's scan_grid_thermal in one call -- the thermally broadened diagram.  Gate
+        grammar, base point, frames and the one-frame rule are do2d_open's; `T` is converted as in thermal_state_open
+        (kT = 8.617333262145e-5 * T; T=None is the device's own sampled T, and a device loaded from raw parameter blocks has none
+        and raises ValueError).  Returns (signal (y_points, x_points, 1), n (y_points, x_points, N), var (y_points, x_points, N))
+        float64."""
+        N = self.n_dot
+        (x_axis, x_frame), (y_axis, y_frame) = self._gate_axis(x_gate), self._gate_axis(y_gate)
+        if x_frame != y_frame:
+            raise NotImplementedError(f"do2d_thermal({x_gate!r}, ..., {y_gate!r}, ...): one call has one frame, and {x_gate!r} is "
+                                      f"{x_frame} while {y_gate!r} is {y_frame}; sweep two physical gates or two virtual axes")
+        kT = self._grid_kT(T)
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        args = ([0], x_axis, y_axis, (float(x_min), float(x_max)), (float(y_min), float(y_max)), int(x_points), int(y_points),
+                np.zeros((1, N)), np.zeros((1, N - 1)))
+        out = self._b.scan_grid_thermal(*args, kT, 0.0, n_charge=n_charge, frame=x_frame, gamma=gamma, occupations=True, variance=True)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return (host(out["raw"]).astype(np.float64)[0][:, :, None], host(out["occupations"]).astype(np.float64)[0],
+                host(out["variance"]).astype(np.float64)[0])
+
+    def do1d_thermal(self, gate, min, max, points, T=None, n_charge=None):
+        """do1d_open (n_charge None) or do1d_closed at the model's temperature, rendered as a one-row thermal grid.  Returns
+        (signal (points, 1), n (points, N), var (points, N)) float64; `T` as in do2d_thermal."""
+        N = self.n_dot
+        axis, frame = self._gate_axis(gate)
+        kT = self._grid_kT(T)
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        args = ([0], axis, np.zeros(2 * N), (float(min), float(max)), (0.0, 0.0), int(points), 1, np.zeros((1, N)), np.zeros((1, N - 1)))
+        out = self._b.scan_grid_thermal(*args, kT, 0.0, n_charge=n_charge, frame=frame, gamma=gamma, occupations=True, variance=True)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return (host(out["raw"]).astype(np.float64)[0, 0][:, None], host(out["occupations"]).astype(np.float64)[0, 0],
+                host(out["variance"]).astype(np.float64)[0, 0])
+
 
 class ArrayFacade:
     """`env.array` of the reference (a QarrayBaseClass) as far as its users outside step() need it: `model.cgd_full`,
@@ -332,6 +375,15 @@ class ArrayFacade:
         out = self._b.scan_grid([0], x, y, x_range, y_range, nx, ny, np.asarray(gate_voltages, np.float64)[None, :],
                                 np.asarray(barrier_voltages, np.float64)[None, :],
                                 sensor_voltage=None if sensor_voltage is None else float(sensor_voltage), **kw)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return {k: host(v)[0] for k, v in out.items()}
+
+    def scan_grid_thermal(self, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, kT, sensor_voltage=None, **kw):
+        """The backend's scan_grid_thermal for this env (scan_grid at the temperature kT, open or with n_charge= closed): one
+        query, numpy results without the query axis, "variance" (ny, nx, N) and "ztail" (ny, nx) among them when asked for."""
+        out = self._b.scan_grid_thermal([0], x, y, x_range, y_range, nx, ny, np.asarray(gate_voltages, np.float64)[None, :],
+                                        np.asarray(barrier_voltages, np.float64)[None, :], kT,
+                                        sensor_voltage=None if sensor_voltage is None else float(sensor_voltage), **kw)
         host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
         return {k: host(v)[0] for k, v in out.items()}
 

@@ -684,7 +684,8 @@ class VecQuantumDeviceEnv:
         With nx = ny = R this is scan_affine on a pixel_search env, with ny = 1 and a zero y it is scan1d (both bit for bit,
         noise included).  Returns device tensors {"raw": (nq, ny, nx) float64, "image": (nq, ny, nx) float32 normalised per
         grid with its own 0.5 / 99.5 percentiles, "plohi": (nq, 2)}, plus, with occupations=True, {"occupations":
-        (nq, ny, nx, N) float64}.  scan_grid_closed is the same grid at a fixed total charge."""
+        (nq, ny, nx, N) float64}.  scan_grid_closed is the same grid at a fixed total charge, scan_grid_thermal the same grid
+        at a temperature."""
         return self._scan_grid(env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm,
                                gamma, noise, serial, stream_base, occupations, None)
 
@@ -700,9 +701,33 @@ class VecQuantumDeviceEnv:
         return self._scan_grid(env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm,
                                gamma, (), None, None, occupations, n_charge)
 
+    def scan_grid_thermal(self, env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, kT, sensor_voltage=None, *,
+                          n_charge=None, frame="virtual", vgm=None, gamma=None, noise=(), serial=None, stream_base=None,
+                          occupations=False, variance=False, ztail=False):
+        """scan_grid (n_charge None) or scan_grid_closed at a TEMPERATURE (qd_scan_grid_thermal): every point of the grid is in the
+        thermal state rho = exp(-H / kT) / Z of eval_points(kT=), and "raw", "image", "plohi" and "occupations" are those of that
+        state -- the thermally broadened charge-stability diagram.  scan_grid and scan_grid_closed themselves are the T = 0 calls
+        they were, with the signatures they had.  Arguments, frames and results are scan_grid's, and
+          kT                a scalar or (nq,) values, finite and > 0, one per query, in the energy units of `levels` of eval_points
+          n_charge          None: the open regime.  A scalar or (nq,) integers in 0..32767: the closed regime of scan_grid_closed
+          noise             "sensor" is allowed in the open regime (the sensor stage reads the thermal sensor constant alone);
+                            "latch" raises ValueError (the latching model holds an integer configuration, a thermal mean has
+                            none), also when noise=True would bring it along; no noise stage with n_charge
+          variance, ztail   True adds "variance" (nq, ny, nx, N), sum_m P_m (s_m[d] - <n_d>)^2, and "ztail" (nq, ny, nx), the
+                            normalised Boltzmann weight of the highest kept level (the check on the truncation to K states at
+                            this kT)
+        In the open regime the kernel solves each hop component of a point by itself; it agrees with eval_points(kT=) at the same
+        voltages within the sum of both tolerances, not bit for bit.  A closed list is one hop component, so the whole-block
+        solver of eval_points(kT=) runs, and in the physical frame the results equal eval_points(..., n_charge=, kT=) at the
+        grid's voltages bit for bit."""
+        if kT is None:
+            raise ValueError("scan_grid_thermal needs kT; scan_grid and scan_grid_closed are the T = 0 calls")
+        return self._scan_grid(env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm,
+                               gamma, noise, serial, stream_base, occupations, n_charge, kT, variance, ztail)
+
     def _scan_grid(self, env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm, gamma,
-                   noise, serial, stream_base, occupations, n_charge):
-        """scan_grid (n_charge None) and scan_grid_closed"""
+                   noise, serial, stream_base, occupations, n_charge, kT=None, variance=False, ztail=False):
+        """scan_grid (n_charge None) and scan_grid_closed; with kT, scan_grid_thermal in either regime"""
         N = self.N
         if frame not in ("virtual", "physical"):
             raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
@@ -721,6 +746,15 @@ class VecQuantumDeviceEnv:
             if noise and "radial" in tuple(noise):
                 raise ValueError("radial noise is centred on the env's own adjacent-pair observation: not defined for grids")
             flags = self._noise_flags(noise)
+        kth = None
+        if kT is not None:
+            if flags & _lib.QD_NOISE_LATCH:
+                raise ValueError("latching has no thermal form (the latching model holds an integer configuration, a thermal "
+                                 "mean has none): a thermal grid's noise may name 'sensor' only")
+            kth = np.ascontiguousarray(np.broadcast_to(np.asarray(
+                kT.detach().cpu().numpy() if isinstance(kT, torch.Tensor) else kT, np.float64), (nq,)))
+            if not (np.isfinite(kth).all() and (kth > 0).all()):
+                raise ValueError(f"kT must be finite and > 0, got {kT!r}")
         qd = None
         if n_charge is not None:
             if flags:
@@ -737,6 +771,19 @@ class VecQuantumDeviceEnv:
                                    noise_flags=int(flags), reserved=0, serial=self._query_serial(serial, flags),
                                    stream_base=int(self.env_id_offset if stream_base is None else stream_base),
                                    vgm_dev=addr(vm), gamma_dev=addr(gm), occ_dst=addr(out.get("occupations")))
+        if kth is not None:
+            kd = self._to_dev(kth, torch.float64, (nq,))
+            if variance:
+                out["variance"] = torch.zeros((nq, cy, cx, N), dtype=torch.float64, device=self.device)
+            if ztail:
+                out["ztail"] = torch.zeros((nq, cy, cx), dtype=torch.float64, device=self.device)
+            topts = _lib.QdGridThermalOpts(struct_size=ctypes.sizeof(_lib.QdGridThermalOpts), reserved=0, n_charge_dev=addr(qd),
+                                           var_dst=addr(out.get("variance")), ztail_dst=addr(out.get("ztail")))
+            rc = self._lib.qd_scan_grid_thermal(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
+                                                _ptr(kd), _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]),
+                                                ctypes.byref(opts), ctypes.byref(topts), self._stream())
+            _lib.check(self._h, rc, "qd_scan_grid_thermal")
+            return out
         if qd is not None:
             rc = self._lib.qd_scan_grid_closed(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
                                                _ptr(qd), _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]), ctypes.byref(opts),
