@@ -456,8 +456,8 @@ int qd_scan_affine(qd_handle* h, const int32_t* env_of_query_dev, int nq, const 
  * records inert (all zero: no search, no eigen task).  With n <= P, Rl <= R.  Per launch: gather, telegraph chain, the line
  * front kernel (records in the hand-over form of the tile search), the redo instantiation of the per-pixel search, the
  * ground-state kernels, the latching walk, the sensor stage, a pack of the n leading values of each slot into a dense row,
- * the percentile kernel, the write -- the kernels of a step with the slot geometry as data, and five small kernels of the
- * line's own (csrc/qd_line.h).  Slots in flight per launch: what lane 0's record buffer (qd_chunk_envs * C * P records) and
+ * the percentile kernel, the write -- the kernels of a step with the slot geometry as data, four small kernels of the
+ * line's own (csrc/qd_line.h) and the scans' write kernel (csrc/qd_query.h).  Slots in flight per launch: what lane 0's record buffer (qd_chunk_envs * C * P records) and
  * slabs hold, floor(qd_chunk_envs * C * P / Rl^2) and floor(slab capacity / ceil(Rl^2 / 256)), at most QD_LINE_SLOTS.
  * Stream-ordered with no host wait after the first call, which allocates the scratch with hipMalloc (per slot in flight: a
  * parameter copy, a state block, Rl^2 + n doubles of signal, 2 of percentiles, one descriptor of 2 + 2*8 doubles and the
@@ -527,7 +527,8 @@ int qd_scan1d(qd_handle* h, const int32_t* env_of_query_dev, int nq, int n_point
  * Rl*Rl - nx*ny tail records inert, as in a line's slot.  Per launch: gather, telegraph chain, the grid front kernel, the
  * redo instantiation of the per-pixel search, the ground-state kernels, the latching walk (one lane per slot and row), the
  * sensor stage, the pack of the nx*ny leading values into a dense row, the percentile kernel, the write -- the kernels of a
- * step with the slot geometry as data, qd_scan1d's pack, and four small kernels of the grid's own (csrc/qd_grid.h).  The tile
+ * step with the slot geometry as data, qd_scan1d's pack, the scans' write kernel (csrc/qd_query.h) and three small kernels of
+ * the grid's own (csrc/qd_grid.h).  The tile
  * search does not run: its tiles are cut from R x R images.  Slots in flight per launch: those of a line of nx*ny points, at
  * most QD_GRID_SLOTS.  Stream-ordered with no host wait after the first call.  The scratch is qd_scan1d's (a call of either
  * grows it for both; hipFree waits for the device) and one descriptor per slot in flight of 4 + 4*8 doubles, the two

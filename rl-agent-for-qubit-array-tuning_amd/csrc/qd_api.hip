@@ -192,9 +192,9 @@ static int qd_fail(const qd_handle* h, int code, const char* what, hipError_t e 
     }
     return code;
 }
-// a message that names the entry point: `fmt` has one %s, for `who`
-static int qd_failf(const qd_handle* h, int code, const char* fmt, const char* who) {
-    if (h) snprintf(h->err, sizeof(h->err), fmt, who);
+// a message that names the entry point: `fmt` has one %s for `who`, and may have a second one for `what`
+static int qd_failf(const qd_handle* h, int code, const char* fmt, const char* who, const char* what = "") {
+    if (h) snprintf(h->err, sizeof(h->err), fmt, who, what);
     return code;
 }
 #define QD_HIP(call)                                                              \
@@ -838,65 +838,86 @@ extern "C" int qd_snapshot(qd_handle* h, const int32_t* env_ids, int n, float* g
     return QD_OK;
 }
 
-// The option values qd_probe_opts and qd_scan_opts share.
+// The option values of a stateless query: qd_probe_opts gives the first four, the scans' option structs all of them.
 struct QdQueryOpts {
     int noise_flags; unsigned long long serial; long long stream_base;
-    bool occ;                               // the caller takes the occupations
+    bool occ;                               // the slots carry occupations: the caller takes them, or a thermal kernel writes them
+    double* occ_dst; const double *vgm, *gamma; int frame;
 };
 
-// The stateless queries (qd_probe_ex, qd_scan2d, qd_scan_affine): `nq` of them in launch chunks of h->chunk slots on the blocks of `set`,
-// each slot `channels` images filled by `front`.  Per chunk: gather(base, cnt, bufs) copies the envs' blocks into the slots
-// and applies the queries; then the stages of an observation in qd_observe's order -- telegraph words, search and ground
-// state, latching, sensor, percentiles -- on the slots alone, without eigenvalues; occupations, telegraph words and noise
-// only as asked for, keyed by the caller's serial and stream base; write(base, cnt, bufs) hands the results out.  Both
-// only launch, the runner checks.  Nothing of the envs is written.
-template <class Gather, class Write>
-static int qd_run_queries(qd_handle* h, QdScratchSet& set, int channels, QdFront front, const QdQueryOpts& o, int nq, hipStream_t s,
-                          Gather gather, Write write) {
+// The slots of a stateless query: `channels` images of side x side records each, of which the percentile kernel reads
+// `count` values per slot; `slots` of them in flight; `front` fills the records.
+struct QdSlotGeom { int channels, side; long count; int slots; QdFront front; };
+
+// The stateless queries: `nq` of them in launches of g.slots slots on the blocks of `set`.  Per launch: gather(base, cnt, bufs)
+// copies the envs' blocks into the slots and applies the queries; then the stages of an observation in qd_observe's order --
+// telegraph words, solve(base, cnt, bufs): search and ground (or thermal) state, latch(cnt, bufs), sensor, pack(cnt, bufs): the rows
+// of g.count values that the percentile kernel reads, percentiles -- on the slots alone, without eigenvalues; occupations,
+// telegraph words and noise only as asked for, keyed by the caller's serial and stream base; write(base, cnt, bufs, rows)
+// hands the results out.  gather, pack and write only launch, the runner checks; solve and latch return a status.  Nothing
+// of the envs is written.
+template <class Gather, class Solve, class Latch, class Pack, class Write>
+static int qd_run_queries(qd_handle* h, QdScratchSet& set, const QdSlotGeom& g, const QdQueryOpts& o, int nq, hipStream_t s,
+                          Gather gather, Solve solve, Latch latch, Pack pack, Write write) {
     const bool want_occ = (o.noise_flags & QD_NOISE_LATCH) || o.occ, want_tel = (o.noise_flags & QD_NOISE_SENSOR) != 0;
-    const int pc = h->chunk;                                  // queries in flight = envs per launch chunk (lane 0's scratch)
-    const size_t CP = (size_t)channels * h->P;                // (slots of the handle's own image size: b.R, b.P below)
-    QD_HIP(set.reserve(h->L, CP, (size_t)pc, 2, want_occ ? CP * h->N : 0, want_tel ? (size_t)channels * h->tel_words : 0));
-    QdEnvBufs b = set.view(channels, h->R, front);
+    const int pc = g.slots, tel_words = (g.side * g.side + 63) / 64;     // (a chain of side^2 states per channel image)
+    const size_t CP = (size_t)g.channels * g.side * g.side;
+    QD_HIP(set.reserve(h->L, CP, (size_t)pc, 2, want_occ ? CP * h->N : 0, want_tel ? (size_t)g.channels * tel_words : 0));
+    QdEnvBufs b = set.view(g.channels, g.side, g.front);
     b.occ = want_occ ? set.occ.p : nullptr;
     b.noise_flags = o.noise_flags;
-    if (want_tel) { b.tel = set.tel.p; b.tel_words = h->tel_words; }
+    if (want_tel) { b.tel = set.tel.p; b.tel_words = tel_words; }
     b.serial = o.serial;
     for (int base = 0; base < nq; base += pc) {
         const int cnt = nq - base < pc ? nq - base : pc;
-        b.env_off = (uint32_t)(o.stream_base + base);        // slot k of the chunk draws as global env stream_base + base + k
+        b.env_off = (uint32_t)(o.stream_base + base);        // slot k of the launch draws as global env stream_base + base + k
         gather(base, cnt, b);
         QD_HIP(hipGetLastError());
         if (want_tel) {
-            const int nt = cnt * channels;
-            qd_k_telegraph<<<dim3((nt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, channels, b.P, h->L.size, h->L.noise, b.params, b.tel,
+            const int nt = cnt * g.channels;
+            qd_k_telegraph<<<dim3((nt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, g.channels, b.P, h->L.size, h->L.noise, b.params, b.tel,
                                                                      qd_noise_cfg(h, b));
             QD_HIP(hipGetLastError());
         }
-        if (int rc = qd_launch_csd(h, b, h->lanes[0], nullptr, 0, cnt, s, QD_ST_ALL)) return rc;
+        if (int rc = solve(base, cnt, b)) return rc;
         if (o.noise_flags & QD_NOISE_LATCH) {
+            if (int rc = latch(cnt, b)) return rc;
+            QD_HIP(hipGetLastError());
+        }
+        if (int rc = qd_launch_sensor(h, b, nullptr, cnt, s)) return rc;
+        const double* rows = pack(cnt, b);
+        qd_launch_percentile(nullptr, (unsigned)cnt, g.count, rows, b.plohi, s);
+        QD_HIP(hipGetLastError());
+        write(base, cnt, b, rows);
+        QD_HIP(hipGetLastError());
+    }
+    return QD_OK;
+}
+
+// The queries that render images of the handle's own size (qd_probe_ex, qd_scan2d, qd_scan_affine): h->chunk slots in flight
+// (lane 0's scratch), each `channels` images filled by `front` inside the search; the latching walk by rows; no pack.
+template <class Gather, class Write>
+static int qd_run_queries(qd_handle* h, QdScratchSet& set, int channels, QdFront front, const QdQueryOpts& o, int nq, hipStream_t s,
+                          Gather gather, Write write) {
+    return qd_run_queries(h, set, QdSlotGeom{channels, h->R, (long)channels * h->P, h->chunk, front}, o, nq, s, gather,
+        [&](int, int cnt, const QdEnvBufs& b) { return qd_launch_csd(h, b, h->lanes[0], nullptr, 0, cnt, s, QD_ST_ALL); },
+        [&](int cnt, const QdEnvBufs& b) {
 #ifdef QD_PROBE_SERIAL_LATCH        // (measurement only, DESIGN.md 7: probes take the one-thread walk of qd_observe on their buffers)
             if (front == QD_FRONT_ENV) {
                 QD_DISPATCH_N(h->N, qd_k_latch<NN><<<dim3((cnt * channels + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, h->R, b.params, b.state,
                                                                                                        b.occ, b.zraw, qd_noise_cfg(h, b)));
-            } else
-#endif
-            {
-                const long rows = (long)cnt * channels * b.R;
-                const dim3 grid((unsigned)((rows + QD_LATCH_ROWS_BLOCK - 1) / QD_LATCH_ROWS_BLOCK));
-                QD_DISPATCH_BOOL(channels == 1, ONE, QD_DISPATCH_N(h->N,
-                    qd_k_latch_rows<NN, (ONE ? 1 : NN - 1)><<<grid, dim3(QD_LATCH_ROWS_BLOCK), 0, s>>>(cnt, b.R, b.params, b.state, b.occ,
-                                                                                                       b.zraw, qd_noise_cfg(h, b))));
+                return (int)QD_OK;
             }
-            QD_HIP(hipGetLastError());
-        }
-        if (int rc = qd_launch_sensor(h, b, nullptr, cnt, s)) return rc;
-        qd_launch_percentile(nullptr, (unsigned)cnt, (long)channels * b.P, b.zraw, b.plohi, s);
-        QD_HIP(hipGetLastError());
-        write(base, cnt, b);
-        QD_HIP(hipGetLastError());
-    }
-    return QD_OK;
+#endif
+            const long rows = (long)cnt * channels * b.R;
+            const dim3 grid((unsigned)((rows + QD_LATCH_ROWS_BLOCK - 1) / QD_LATCH_ROWS_BLOCK));
+            QD_DISPATCH_BOOL(channels == 1, ONE, QD_DISPATCH_N(h->N,
+                qd_k_latch_rows<NN, (ONE ? 1 : NN - 1)><<<grid, dim3(QD_LATCH_ROWS_BLOCK), 0, s>>>(cnt, b.R, b.params, b.state, b.occ,
+                                                                                                   b.zraw, qd_noise_cfg(h, b))));
+            return (int)QD_OK;
+        },
+        [](int, const QdEnvBufs& b) { return (const double*)b.zraw; },
+        [&](int base, int cnt, const QdEnvBufs& b, const double*) { write(base, cnt, b); });
 }
 
 extern "C" int qd_probe_ex(qd_handle* h, const int32_t* env_of_query, int nq, const double* gate_v, const double* barrier_v,
@@ -939,44 +960,85 @@ extern "C" int qd_probe(qd_handle* h, const int32_t* env_of_query, int nq, const
     return qd_probe_ex(h, env_of_query, nq, gate_v, barrier_v, sensor_v, window, raw_dst, image_dst, plohi_dst, nullptr, stream);
 }
 
+// qdsim.h keeps one option struct per scan family; they are one layout, and the library reads them all as a qd_scan_opts
+template <class T>
+constexpr bool qd_is_scan_opts() {
+    return sizeof(T) == sizeof(qd_scan_opts) && offsetof(T, struct_size) == offsetof(qd_scan_opts, struct_size) &&
+           offsetof(T, frame) == offsetof(qd_scan_opts, frame) && offsetof(T, noise_flags) == offsetof(qd_scan_opts, noise_flags) &&
+           offsetof(T, reserved) == offsetof(qd_scan_opts, reserved) && offsetof(T, serial) == offsetof(qd_scan_opts, serial) &&
+           offsetof(T, stream_base) == offsetof(qd_scan_opts, stream_base) && offsetof(T, vgm_dev) == offsetof(qd_scan_opts, vgm_dev) &&
+           offsetof(T, gamma_dev) == offsetof(qd_scan_opts, gamma_dev) && offsetof(T, occ_dst) == offsetof(qd_scan_opts, occ_dst);
+}
+static_assert(qd_is_scan_opts<qd_scan_affine_opts>() && qd_is_scan_opts<qd_scan1d_opts>() && qd_is_scan_opts<qd_scan_grid_opts>(),
+              "the scans' option structs are one layout");
+static_assert(QD_SCAN_VIRTUAL == 0, "a call without options is one with all-zero options");
+
+// The first checks of every scan: the count and the arrays that none can do without (`second`: axes_dev or dir_dev).
+static int qd_check_scan_arrays(const qd_handle* h, const char* who, int nq, const void* env_of_query, const void* second,
+                                const char* second_name, const void* range, const void* gate_v, const void* barrier_v) {
+    if (nq < 0) return qd_failf(h, QD_ERR_ARG, "%s: nq < 0", who);
+    if (!env_of_query || !second || !range) return qd_failf(h, QD_ERR_ARG, "%s: env_of_query_dev, %s or range_dev is NULL", who, second_name);
+    if (!gate_v || !barrier_v) return qd_failf(h, QD_ERR_ARG, "%s: gate_v_dev or barrier_v_dev is NULL", who);
+    return QD_OK;
+}
+
+// The checks of a scan's options (`opts`: null, or one of the scans' option structs, `opts_type` by name) and of the handle,
+// for the entry point `who` that renders `what` (scan, line, grid; thermal: at a temperature); o <- the options.
+static int qd_check_scan(const qd_handle* h, const char* who, const char* opts_type, const char* what, const void* opts, bool thermal,
+                         QdQueryOpts& o) {
+    qd_scan_opts so{};
+    if (opts) {
+        memcpy(&so.struct_size, opts, sizeof(so.struct_size));
+        if (so.struct_size != (int32_t)sizeof(qd_scan_opts))
+            return qd_failf(h, QD_ERR_ARG, "%s: opts->struct_size is not sizeof(%s)", who, opts_type);
+        memcpy(&so, opts, sizeof(so));
+    }
+    if (so.frame != QD_SCAN_VIRTUAL && so.frame != QD_SCAN_PHYSICAL)
+        return qd_failf(h, QD_ERR_ARG, "%s: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL", who);
+    if (so.frame == QD_SCAN_PHYSICAL && so.vgm_dev) return qd_failf(h, QD_ERR_ARG, "%s: vgm_dev has no meaning in the physical frame", who);
+    if (so.noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_LATCH))
+        return qd_failf(h, QD_ERR_ARG, "%s: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
+                                      "centred on the env's own adjacent-pair observation)", who);
+    if (thermal && (so.noise_flags & QD_NOISE_LATCH))
+        return qd_failf(h, QD_ERR_ARG, "%s: QD_NOISE_LATCH has no thermal form: the latching model holds an integer "
+                                      "configuration, a thermal mean has none", who);
+    if (h->cfg.flags & QD_FLAG_VALIDATE)
+        return qd_failf(h, QD_ERR_STATE, "%s: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
+                                        "B envs' last observe and renders no %ss; use a handle without the flag", who, what);
+    if (h->full_m)
+        return qd_failf(h, QD_ERR_STATE, "%s: the full charge-state space synthesises its own voltages "
+                                        "(qd_k_full_structure); a %s front end for it is not built", who, what);
+    o = QdQueryOpts{so.noise_flags, so.serial, so.stream_base, so.occ_dst || thermal, so.occ_dst, so.vgm_dev, so.gamma_dev, so.frame};
+    return QD_OK;
+}
+
+// the one write kernel of the scans: `n` values per slot from rows of stride zs, occupations from slots of `os` points
+static void qd_launch_query_write(const qd_handle* h, const int32_t* env_of_query, const int32_t* axes, int base, int cnt, int n, int zs,
+                                  int os, const double* rows, const QdEnvBufs& b, double* raw_dst, float* image_dst, double* plohi_dst,
+                                  double* occ_dst, hipStream_t s) {
+    if (raw_dst || image_dst || plohi_dst || occ_dst)
+        qd_k_query_write<<<dim3((n + 255) / 256, cnt), dim3(256), 0, s>>>(env_of_query, axes, base, h->B, h->N, n, zs, os, rows, b.plohi,
+                                                                          b.occ, raw_dst, image_dst, plohi_dst, occ_dst);
+}
+
 extern "C" int qd_scan2d(qd_handle* h, const int32_t* env_of_query, int nq, const int32_t* axes, const double* range,
                          const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst, float* image_dst,
                          double* plohi_dst, const qd_scan_opts* opts, void* stream) {
     if (!h) return QD_ERR_ARG;
-    if (nq < 0) return qd_fail(h, QD_ERR_ARG, "qd_scan2d: nq < 0");
-    if (!env_of_query || !axes || !range) return qd_fail(h, QD_ERR_ARG, "qd_scan2d: env_of_query_dev, axes_dev or range_dev is NULL");
-    if (!gate_v || !barrier_v) return qd_fail(h, QD_ERR_ARG, "qd_scan2d: gate_v_dev or barrier_v_dev is NULL");
-    if (opts && opts->struct_size != (int32_t)sizeof(qd_scan_opts))
-        return qd_fail(h, QD_ERR_ARG, "qd_scan2d: opts->struct_size is not sizeof(qd_scan_opts)");
-    if (opts && opts->frame != QD_SCAN_VIRTUAL && opts->frame != QD_SCAN_PHYSICAL)
-        return qd_fail(h, QD_ERR_ARG, "qd_scan2d: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL");
-    if (opts && opts->frame == QD_SCAN_PHYSICAL && opts->vgm_dev)
-        return qd_fail(h, QD_ERR_ARG, "qd_scan2d: vgm_dev has no meaning in the physical frame");
-    if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_LATCH)))
-        return qd_fail(h, QD_ERR_ARG, "qd_scan2d: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
-                                      "centred on the env's own adjacent-pair observation)");
-    if (h->cfg.flags & QD_FLAG_VALIDATE)
-        return qd_fail(h, QD_ERR_STATE, "qd_scan2d: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
-                                        "B envs' last observe and renders no scans; use a handle without the flag");
-    if (h->full_m)
-        return qd_fail(h, QD_ERR_STATE, "qd_scan2d: the full charge-state space synthesises its own voltages "
-                                        "(qd_k_full_structure); a scan front end for it is not built");
+    QdQueryOpts o;
+    if (int rc = qd_check_scan_arrays(h, "qd_scan2d", nq, env_of_query, axes, "axes_dev", range, gate_v, barrier_v)) return rc;
+    if (int rc = qd_check_scan(h, "qd_scan2d", "qd_scan_opts", "scan", opts, false, o)) return rc;
     if (nq == 0) return QD_OK;
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
-    const QdQueryOpts o = opts ? QdQueryOpts{opts->noise_flags, opts->serial, opts->stream_base, opts->occ_dst != nullptr} : QdQueryOpts{};
-    double* const occ_dst = opts ? opts->occ_dst : nullptr;
-    const QdScanQuery Q{env_of_query, axes, range, gate_v, barrier_v, sensor_v, opts ? opts->vgm_dev : nullptr,
-                        opts ? opts->gamma_dev : nullptr, opts ? opts->frame : QD_SCAN_VIRTUAL};
+    const QdScanQuery Q{env_of_query, axes, range, gate_v, barrier_v, sensor_v, o.vgm, o.gamma, o.frame};
     // ONE channel image per slot, over the axes that the gather kernel leaves in the slot's state block copy
     return qd_run_queries(h, h->scan, 1, QD_FRONT_SCAN, o, nq, s,
         [&](int base, int cnt, const QdEnvBufs& sb) {
             qd_k_scan_gather<<<dim3(cnt), dim3(QD_SCAN_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, sb.params, sb.state);
         },
         [&](int base, int cnt, const QdEnvBufs& sb) {
-            if (raw_dst || image_dst || plohi_dst || occ_dst)
-                qd_k_scan_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, h->P, sb.zraw, sb.plohi, sb.occ,
-                                                                                    raw_dst, image_dst, plohi_dst, occ_dst);
+            qd_launch_query_write(h, env_of_query, axes, base, cnt, h->P, h->P, h->P, sb.zraw, sb, raw_dst, image_dst, plohi_dst, o.occ_dst, s);
         });
 }
 
@@ -984,31 +1046,13 @@ extern "C" int qd_scan_affine(qd_handle* h, const int32_t* env_of_query, int nq,
                               const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst,
                               float* image_dst, double* plohi_dst, const qd_scan_affine_opts* opts, void* stream) {
     if (!h) return QD_ERR_ARG;
-    if (nq < 0) return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: nq < 0");
-    if (!env_of_query || !dir || !range) return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: env_of_query_dev, dir_dev or range_dev is NULL");
-    if (!gate_v || !barrier_v) return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: gate_v_dev or barrier_v_dev is NULL");
-    if (opts && opts->struct_size != (int32_t)sizeof(qd_scan_affine_opts))
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: opts->struct_size is not sizeof(qd_scan_affine_opts)");
-    if (opts && opts->frame != QD_SCAN_VIRTUAL && opts->frame != QD_SCAN_PHYSICAL)
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL");
-    if (opts && opts->frame == QD_SCAN_PHYSICAL && opts->vgm_dev)
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: vgm_dev has no meaning in the physical frame");
-    if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_LATCH)))
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_affine: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
-                                      "centred on the env's own adjacent-pair observation)");
-    if (h->cfg.flags & QD_FLAG_VALIDATE)
-        return qd_fail(h, QD_ERR_STATE, "qd_scan_affine: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
-                                        "B envs' last observe and renders no scans; use a handle without the flag");
-    if (h->full_m)
-        return qd_fail(h, QD_ERR_STATE, "qd_scan_affine: the full charge-state space synthesises its own voltages "
-                                        "(qd_k_full_structure); a scan front end for it is not built");
+    QdQueryOpts o;
+    if (int rc = qd_check_scan_arrays(h, "qd_scan_affine", nq, env_of_query, dir, "dir_dev", range, gate_v, barrier_v)) return rc;
+    if (int rc = qd_check_scan(h, "qd_scan_affine", "qd_scan_affine_opts", "scan", opts, false, o)) return rc;
     if (nq == 0) return QD_OK;
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
-    const QdQueryOpts o = opts ? QdQueryOpts{opts->noise_flags, opts->serial, opts->stream_base, opts->occ_dst != nullptr} : QdQueryOpts{};
-    double* const occ_dst = opts ? opts->occ_dst : nullptr;
-    const QdAffineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, opts ? opts->vgm_dev : nullptr,
-                          opts ? opts->gamma_dev : nullptr, opts ? opts->frame : QD_SCAN_VIRTUAL};
+    const QdAffineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, o.vgm, o.gamma, o.frame};
     // one descriptor per query in flight (qd_run_queries: h->chunk slots), beside the slots of the scan buffers
     QD_HIP(h->affine_axes.reserve((size_t)h->chunk));
     QdAffineAxes* const axes = h->affine_axes.p;
@@ -1018,21 +1062,39 @@ extern "C" int qd_scan_affine(qd_handle* h, const int32_t* env_of_query, int nq,
                                                                            axes);
         },
         [&](int base, int cnt, const QdEnvBufs& sb) {
-            if (raw_dst || image_dst || plohi_dst || occ_dst)
-                qd_k_affine_write<<<dim3((h->P + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, h->P, sb.zraw, sb.plohi, sb.occ,
-                                                                                      raw_dst, image_dst, plohi_dst, occ_dst);
+            qd_launch_query_write(h, env_of_query, nullptr, base, cnt, h->P, h->P, h->P, sb.zraw, sb, raw_dst, image_dst, plohi_dst, o.occ_dst, s);
         });
 }
 
-// slots in flight of qd_scan1d for lines of n points: what lane 0's record buffer (chunk * C * P records) and its slabs
-// (gs_batches) hold in slots of the line's own size, at most QD_LINE_SLOTS.  With n <= P both hold one slot at the least.
-static int qd_line_slots(const qd_handle* h, int n) {
+// slots in flight of qd_scan1d and qd_scan_grid* for nq queries of n points: what lane 0's record buffer (chunk * C * P records)
+// and its slabs (gs_batches) hold in slots of the line's own size, at most QD_LINE_SLOTS.  With n <= P both hold one slot at
+// the least.
+static int qd_line_slots(const qd_handle* h, int n, int nq) {
     const int side = qd_line_side(n);
     const size_t sp = (size_t)side * side;
     size_t slots = (size_t)h->chunk * h->C * h->P / sp;
     const size_t by_slabs = h->gs_batches / (size_t)qd_line_batches(n, h->ppb);
     if (by_slabs < slots) slots = by_slabs;
-    return (int)(slots < QD_LINE_MAX_SLOTS ? slots : QD_LINE_MAX_SLOTS);
+    if (slots > QD_LINE_MAX_SLOTS) slots = QD_LINE_MAX_SLOTS;
+    return (size_t)nq < slots ? nq : (int)slots;
+}
+
+// qd_scan1d and qd_scan_grid* on the runner, `pc` slots in flight: the slot of n points is side x side records, record p =
+// point p, the tail inert, filled by a front kernel of the caller's (in solve) before the redo pass; the n leading values of a
+// slot are packed into a dense row for the percentile and the write kernel.
+template <class Gather, class Solve, class Latch>
+static int qd_run_lines(qd_handle* h, int n, int pc, const QdQueryOpts& o, const int32_t* env_of_query, int nq, double* raw_dst,
+                        float* image_dst, double* plohi_dst, hipStream_t s, Gather gather, Solve solve, Latch latch) {
+    QD_HIP(h->line_dense.reserve((size_t)pc * n));
+    double* const dense = h->line_dense.p;
+    return qd_run_queries(h, h->line, QdSlotGeom{1, qd_line_side(n), n, pc, QD_FRONT_LINE}, o, nq, s, gather, solve, latch,
+        [&](int cnt, const QdEnvBufs& b) {
+            qd_k_line_pack<<<dim3((n + 255) / 256, cnt), dim3(256), 0, s>>>(n, b.P, b.zraw, dense);
+            return (const double*)dense;
+        },
+        [&](int base, int cnt, const QdEnvBufs& b, const double* rows) {
+            qd_launch_query_write(h, env_of_query, nullptr, base, cnt, n, n, b.P, rows, b, raw_dst, image_dst, plohi_dst, o.occ_dst, s);
+        });
 }
 
 extern "C" int qd_scan1d(qd_handle* h, const int32_t* env_of_query, int nq, int n_points, const double* dir, const double* range,
@@ -1040,86 +1102,54 @@ extern "C" int qd_scan1d(qd_handle* h, const int32_t* env_of_query, int nq, int 
                          double* plohi_dst, const qd_scan1d_opts* opts, void* stream) {
     static_assert(QD_LINE_MAX_SLOTS == QD_LINE_SLOTS, "qdsim.h states the bound");
     if (!h) return QD_ERR_ARG;
-    if (nq < 0) return qd_fail(h, QD_ERR_ARG, "qd_scan1d: nq < 0");
-    if (!env_of_query || !dir || !range) return qd_fail(h, QD_ERR_ARG, "qd_scan1d: env_of_query_dev, dir_dev or range_dev is NULL");
-    if (!gate_v || !barrier_v) return qd_fail(h, QD_ERR_ARG, "qd_scan1d: gate_v_dev or barrier_v_dev is NULL");
+    QdQueryOpts o;
+    if (int rc = qd_check_scan_arrays(h, "qd_scan1d", nq, env_of_query, dir, "dir_dev", range, gate_v, barrier_v)) return rc;
     if (n_points < 1 || n_points > h->P) return qd_fail(h, QD_ERR_ARG, "qd_scan1d: n_points must be in 1..P (P = resolution^2 of the handle)");
-    if (opts && opts->struct_size != (int32_t)sizeof(qd_scan1d_opts))
-        return qd_fail(h, QD_ERR_ARG, "qd_scan1d: opts->struct_size is not sizeof(qd_scan1d_opts)");
-    if (opts && opts->frame != QD_SCAN_VIRTUAL && opts->frame != QD_SCAN_PHYSICAL)
-        return qd_fail(h, QD_ERR_ARG, "qd_scan1d: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL");
-    if (opts && opts->frame == QD_SCAN_PHYSICAL && opts->vgm_dev)
-        return qd_fail(h, QD_ERR_ARG, "qd_scan1d: vgm_dev has no meaning in the physical frame");
-    if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_LATCH)))
-        return qd_fail(h, QD_ERR_ARG, "qd_scan1d: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
-                                      "centred on the env's own adjacent-pair observation)");
-    if (h->cfg.flags & QD_FLAG_VALIDATE)
-        return qd_fail(h, QD_ERR_STATE, "qd_scan1d: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
-                                        "B envs' last observe and renders no lines; use a handle without the flag");
-    if (h->full_m)
-        return qd_fail(h, QD_ERR_STATE, "qd_scan1d: the full charge-state space synthesises its own voltages "
-                                        "(qd_k_full_structure); a line front end for it is not built");
+    if (int rc = qd_check_scan(h, "qd_scan1d", "qd_scan1d_opts", "line", opts, false, o)) return rc;
     if (nq == 0) return QD_OK;
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
-    const int noise_flags = opts ? opts->noise_flags : 0;
-    const unsigned long long serial = opts ? opts->serial : 0;
-    const long long stream_base = opts ? opts->stream_base : 0;
-    double* const occ_dst = opts ? opts->occ_dst : nullptr;
-    const bool want_occ = (noise_flags & QD_NOISE_LATCH) || occ_dst, want_tel = (noise_flags & QD_NOISE_SENSOR) != 0;
-    const QdLineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, opts ? opts->vgm_dev : nullptr,
-                        opts ? opts->gamma_dev : nullptr, opts ? opts->frame : QD_SCAN_VIRTUAL};
-    // the slot of a line: side x side records, record p = point p, the tail inert
-    const int n = n_points, side = qd_line_side(n), SP = side * side, tel_words = (SP + 63) / 64;
-    const int cap = qd_line_slots(h, n), pc = nq < cap ? nq : cap;
-    QD_HIP(h->line.reserve(h->L, (size_t)SP, (size_t)pc, 2, want_occ ? (size_t)SP * h->N : 0, want_tel ? (size_t)tel_words : 0));
+    const QdAffineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, o.vgm, o.gamma, o.frame};
+    const int n = n_points, pc = qd_line_slots(h, n, nq);
     QD_HIP(h->line_axes.reserve((size_t)pc));
-    QD_HIP(h->line_dense.reserve((size_t)pc * n));
-    QdEnvBufs b = h->line.view(1, side, QD_FRONT_LINE);
-    b.occ = want_occ ? h->line.occ.p : nullptr;
-    b.noise_flags = noise_flags;
-    if (want_tel) { b.tel = h->line.tel.p; b.tel_words = tel_words; }
-    b.serial = serial;
     const QdLane& ln = h->lanes[0];
     QdLineAxes* const axes = h->line_axes.p;
-    double* const dense = h->line_dense.p;
-    // per launch, the stages of an observation in qd_observe's order on the slots alone; nothing of the envs is written
-    for (int base = 0; base < nq; base += pc) {
-        const int cnt = nq - base < pc ? nq - base : pc;
-        b.env_off = (uint32_t)(stream_base + base);          // slot k of the launch draws as global env stream_base + base + k
-        qd_k_line_gather<<<dim3(cnt), dim3(QD_LINE_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, b.params, b.state, axes);
-        QD_HIP(hipGetLastError());
-        if (want_tel) {
-            // (a chain of SP states per slot; the sensor stage reads the first n bits)
-            qd_k_telegraph<<<dim3((cnt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, 1, SP, h->L.size, h->L.noise, b.params, b.tel,
-                                                                      qd_noise_cfg(h, b));
+    return qd_run_lines(h, n, pc, o, env_of_query, nq, raw_dst, image_dst, plohi_dst, s,
+        [&](int base, int cnt, const QdEnvBufs& b) {
+            qd_k_line_gather<<<dim3(cnt), dim3(QD_LINE_BLOCK), 0, s>>>(Q, base, h->B, h->N, h->params.p, h->state.p, b.params, b.state, axes);
+        },
+        [&](int, int cnt, const QdEnvBufs& b) {
+            QD_DISPATCH_N(h->N, qd_k_line_front<NN><<<dim3((b.P + QD_LINE_BLOCK - 1) / QD_LINE_BLOCK, cnt), dim3(QD_LINE_BLOCK), 0, s>>>(
+                                    n, b.P, b.params, b.state, axes, ln.recs.p));
             QD_HIP(hipGetLastError());
-        }
-        QD_DISPATCH_N(h->N, qd_k_line_front<NN><<<dim3((SP + QD_LINE_BLOCK - 1) / QD_LINE_BLOCK, cnt), dim3(QD_LINE_BLOCK), 0, s>>>(
-                                n, SP, b.params, b.state, axes, ln.recs.p));
-        QD_HIP(hipGetLastError());
-        if (int rc = qd_launch_candidates(h, b, ln, nullptr, 0, cnt, s, true)) return rc;
-        if (int rc = qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND)) return rc;
-        if (noise_flags & QD_NOISE_LATCH) {
-            QD_DISPATCH_N(h->N, qd_k_latch_lines<NN><<<dim3((cnt + 63) / 64), dim3(64), 0, s>>>(cnt, n, SP, b.params, b.occ, b.zraw,
+            if (int rc = qd_launch_candidates(h, b, ln, nullptr, 0, cnt, s, true)) return rc;
+            return qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND);
+        },
+        [&](int cnt, const QdEnvBufs& b) {
+            QD_DISPATCH_N(h->N, qd_k_latch_lines<NN><<<dim3((cnt + 63) / 64), dim3(64), 0, s>>>(cnt, n, b.P, b.params, b.occ, b.zraw,
                                                                                               qd_noise_cfg(h, b)));
-            QD_HIP(hipGetLastError());
-        }
-        if (int rc = qd_launch_sensor(h, b, nullptr, cnt, s)) return rc;
-        qd_k_line_pack<<<dim3((n + 255) / 256, cnt), dim3(256), 0, s>>>(n, SP, b.zraw, dense);
-        qd_launch_percentile(nullptr, (unsigned)cnt, (long)n, dense, b.plohi, s);
-        QD_HIP(hipGetLastError());
-        if (raw_dst || image_dst || plohi_dst || occ_dst) {
-            qd_k_line_write<<<dim3((n + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, n, SP, dense, b.plohi, b.occ, raw_dst,
-                                                                             image_dst, plohi_dst, occ_dst);
-            QD_HIP(hipGetLastError());
-        }
-    }
-    return QD_OK;
+            return (int)QD_OK;
+        });
 }
 
-// qd_scan_grid (n_charge null) and qd_scan_grid_closed on one slot loop: the closed regime replaces the redo pass of the open
-// search by qd_k_closed at the queries' total charges and leaves every other launch as it is.  kT ([nq], device):
+// A range check that reads the device: one copy of the nq values of `dev` and a wait for the stream, then ok() of each.
+// copy_what and range_fmt: the texts of the two failures.
+template <class T, class Ok>
+static int qd_check_device_range(const qd_handle* h, const char* who, const T* dev, int nq, hipStream_t s, const char* copy_what,
+                                 const char* range_fmt, Ok ok) {
+    T* host = (T*)malloc(sizeof(T) * (size_t)nq);
+    if (!host) return qd_fail(h, QD_ERR_NOMEM, "malloc");
+    hipError_t e_ = hipMemcpyAsync(host, dev, sizeof(T) * (size_t)nq, hipMemcpyDeviceToHost, s);
+    if (e_ == hipSuccess) e_ = hipStreamSynchronize(s);
+    bool bad = false;
+    for (int q = 0; q < nq && e_ == hipSuccess; ++q) bad = bad || !ok(host[q]);
+    free(host);
+    if (e_ != hipSuccess) return qd_fail(h, QD_ERR_HIP, copy_what, e_);
+    return bad ? qd_failf(h, QD_ERR_ARG, range_fmt, who) : (int)QD_OK;
+}
+
+// qd_scan_grid (n_charge null) and qd_scan_grid_closed on the runner of the lines: the closed regime replaces the redo pass of
+// the open search by qd_k_closed at the queries' total charges and leaves every other launch as it is.  kT ([nq], device):
 // qd_scan_grid_thermal, the thermal kernel of qd_thermal_blocks.h in place of the ground-state stage, once, on the lists as the
 // search left them; the slots always carry occupations then.
 static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
@@ -1128,98 +1158,41 @@ static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_quer
                        const double* kT = nullptr, double* var_dst = nullptr, double* ztail_dst = nullptr) {
     static_assert(QD_GRID_MAX_SLOTS == QD_GRID_SLOTS, "qdsim.h states the bound");
     static_assert(QD_THG_BLOCKS <= QD_GRID_MAX_SLOTS, "a launch dimension");
-    if (nq < 0) return qd_failf(h, QD_ERR_ARG, "%s: nq < 0", who);
-    if (!env_of_query || !dir || !range) return qd_failf(h, QD_ERR_ARG, "%s: env_of_query_dev, dir_dev or range_dev is NULL", who);
-    if (!gate_v || !barrier_v) return qd_failf(h, QD_ERR_ARG, "%s: gate_v_dev or barrier_v_dev is NULL", who);
+    QdQueryOpts o;
+    if (int rc = qd_check_scan_arrays(h, who, nq, env_of_query, dir, "dir_dev", range, gate_v, barrier_v)) return rc;
     if (nx < 1 || ny < 1 || (long long)nx * ny > h->P)
         return qd_failf(h, QD_ERR_ARG, "%s: nx and ny must be >= 1 with nx*ny <= P (P = resolution^2 of the handle)", who);
-    if (opts && opts->struct_size != (int32_t)sizeof(qd_scan_grid_opts))
-        return qd_failf(h, QD_ERR_ARG, "%s: opts->struct_size is not sizeof(qd_scan_grid_opts)", who);
-    if (opts && opts->frame != QD_SCAN_VIRTUAL && opts->frame != QD_SCAN_PHYSICAL)
-        return qd_failf(h, QD_ERR_ARG, "%s: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL", who);
-    if (opts && opts->frame == QD_SCAN_PHYSICAL && opts->vgm_dev)
-        return qd_failf(h, QD_ERR_ARG, "%s: vgm_dev has no meaning in the physical frame", who);
-    if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_LATCH)))
-        return qd_failf(h, QD_ERR_ARG, "%s: noise_flags takes QD_NOISE_SENSOR and QD_NOISE_LATCH only (the radial stage is "
-                                      "centred on the env's own adjacent-pair observation)", who);
-    if (kT && opts && (opts->noise_flags & QD_NOISE_LATCH))
-        return qd_failf(h, QD_ERR_ARG, "%s: QD_NOISE_LATCH has no thermal form: the latching model holds an integer "
-                                      "configuration, a thermal mean has none", who);
-    if (h->cfg.flags & QD_FLAG_VALIDATE)
-        return qd_failf(h, QD_ERR_STATE, "%s: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
-                                        "B envs' last observe and renders no grids; use a handle without the flag", who);
-    if (h->full_m)
-        return qd_failf(h, QD_ERR_STATE, "%s: the full charge-state space synthesises its own voltages "
-                                        "(qd_k_full_structure); a grid front end for it is not built", who);
-    if (n_charge && opts && opts->noise_flags)
+    if (int rc = qd_check_scan(h, who, "qd_scan_grid_opts", "grid", opts, kT != nullptr, o)) return rc;
+    if (n_charge && o.noise_flags)
         return qd_failf(h, QD_ERR_ARG, "%s: the closed regime has no noise stages: noise_flags must be 0", who);
     if (nq == 0) return QD_OK;
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
-    if (n_charge) {
-        // the range check reads the device: one copy of nq int32 and a wait for the stream
-        int32_t* qh = (int32_t*)malloc(sizeof(int32_t) * (size_t)nq);
-        if (!qh) return qd_fail(h, QD_ERR_NOMEM, "malloc");
-        hipError_t e_ = hipMemcpyAsync(qh, n_charge, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s);
-        if (e_ == hipSuccess) e_ = hipStreamSynchronize(s);
-        bool bad = false;
-        for (int q = 0; q < nq && e_ == hipSuccess; ++q) bad = bad || qh[q] < 0 || qh[q] > QD_CLOSED_QMAX;
-        free(qh);
-        if (e_ != hipSuccess) return qd_fail(h, QD_ERR_HIP, "hipMemcpyAsync(n_charge)", e_);
-        if (bad) return qd_failf(h, QD_ERR_ARG, "%s: n_charge must be in 0..32767", who);
-    }
-    if (kT) {
-        // as n_charge: one copy of nq doubles and a wait for the stream
-        double* th = (double*)malloc(sizeof(double) * (size_t)nq);
-        if (!th) return qd_fail(h, QD_ERR_NOMEM, "malloc");
-        hipError_t e_ = hipMemcpyAsync(th, kT, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, s);
-        if (e_ == hipSuccess) e_ = hipStreamSynchronize(s);
-        bool bad = false;
-        for (int q = 0; q < nq && e_ == hipSuccess; ++q) bad = bad || !(th[q] > 0.0) || !(th[q] < INFINITY);
-        free(th);
-        if (e_ != hipSuccess) return qd_fail(h, QD_ERR_HIP, "hipMemcpyAsync(kT)", e_);
-        if (bad) return qd_failf(h, QD_ERR_ARG, "%s: kT must be finite and > 0", who);
-    }
-    const int noise_flags = opts ? opts->noise_flags : 0;
-    const unsigned long long serial = opts ? opts->serial : 0;
-    const long long stream_base = opts ? opts->stream_base : 0;
-    double* const occ_dst = opts ? opts->occ_dst : nullptr;
-    const bool want_occ = (noise_flags & QD_NOISE_LATCH) || occ_dst || kT, want_tel = (noise_flags & QD_NOISE_SENSOR) != 0;
-    const QdAffineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, opts ? opts->vgm_dev : nullptr,
-                          opts ? opts->gamma_dev : nullptr, opts ? opts->frame : QD_SCAN_VIRTUAL};
-    // the slot of a grid is that of a line of nx*ny points: side x side records, record p = y*nx + x, the tail inert
-    const int n = nx * ny, side = qd_line_side(n), SP = side * side, tel_words = (SP + 63) / 64;
-    const int cap = qd_line_slots(h, n), pc = nq < cap ? nq : cap;
-    QD_HIP(h->line.reserve(h->L, (size_t)SP, (size_t)pc, 2, want_occ ? (size_t)SP * h->N : 0, want_tel ? (size_t)tel_words : 0));
+    if (n_charge)
+        if (int rc = qd_check_device_range(h, who, n_charge, nq, s, "hipMemcpyAsync(n_charge)", "%s: n_charge must be in 0..32767",
+                                           [](int32_t v) { return v >= 0 && v <= QD_CLOSED_QMAX; })) return rc;
+    if (kT)
+        if (int rc = qd_check_device_range(h, who, kT, nq, s, "hipMemcpyAsync(kT)", "%s: kT must be finite and > 0",
+                                           [](double v) { return v > 0.0 && v < INFINITY; })) return rc;
+    const QdAffineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, o.vgm, o.gamma, o.frame};
+    // the slot of a grid is that of a line of nx*ny points, record p = y*nx + x
+    const int n = nx * ny, pc = qd_line_slots(h, n, nq);
     QD_HIP(h->grid_axes.reserve((size_t)pc));
-    QD_HIP(h->line_dense.reserve((size_t)pc * n));
-    QdEnvBufs b = h->line.view(1, side, QD_FRONT_LINE);
-    b.occ = want_occ ? h->line.occ.p : nullptr;
-    b.noise_flags = noise_flags;
-    if (want_tel) { b.tel = h->line.tel.p; b.tel_words = tel_words; }
-    b.serial = serial;
     const QdLane& ln = h->lanes[0];
     QdGridAxes* const axes = h->grid_axes.p;
-    double* const dense = h->line_dense.p;
-    // per launch, the stages of an observation in qd_observe's order on the slots alone; nothing of the envs is written
-    for (int base = 0; base < nq; base += pc) {
-        const int cnt = nq - base < pc ? nq - base : pc;
-        b.env_off = (uint32_t)(stream_base + base);          // slot k of the launch draws as global env stream_base + base + k
-        qd_k_grid_gather<<<dim3(cnt), dim3(QD_GRID_BLOCK), 0, s>>>(Q, base, h->B, h->N, nx, ny, h->params.p, h->state.p, b.params, b.state,
-                                                                   axes);
-        QD_HIP(hipGetLastError());
-        if (want_tel) {
-            // (a chain of SP states per slot; the sensor stage reads the first n bits)
-            qd_k_telegraph<<<dim3((cnt + 63) / 64), dim3(64), 0, s>>>(nullptr, cnt, 1, SP, h->L.size, h->L.noise, b.params, b.tel,
-                                                                      qd_noise_cfg(h, b));
+    return qd_run_lines(h, n, pc, o, env_of_query, nq, raw_dst, image_dst, plohi_dst, s,
+        [&](int base, int cnt, const QdEnvBufs& b) {
+            qd_k_grid_gather<<<dim3(cnt), dim3(QD_GRID_BLOCK), 0, s>>>(Q, base, h->B, h->N, nx, ny, h->params.p, h->state.p, b.params, b.state,
+                                                                       axes);
+        },
+        [&](int base, int cnt, const QdEnvBufs& b) {
+            const int SP = b.P;
+            QD_DISPATCH_N(h->N, qd_k_grid_front<NN><<<dim3((SP + QD_GRID_BLOCK - 1) / QD_GRID_BLOCK, cnt), dim3(QD_GRID_BLOCK), 0, s>>>(
+                                    SP, b.params, b.state, axes, ln.recs.p));
             QD_HIP(hipGetLastError());
-        }
-        QD_DISPATCH_N(h->N, qd_k_grid_front<NN><<<dim3((SP + QD_GRID_BLOCK - 1) / QD_GRID_BLOCK, cnt), dim3(QD_GRID_BLOCK), 0, s>>>(
-                                SP, b.params, b.state, axes, ln.recs.p));
-        QD_HIP(hipGetLastError());
-        if (n_charge) { if (int rc = qd_launch_closed(h, b, ln, SP, n_charge + base, cnt, s)) return rc; }
-        else if (int rc = qd_launch_candidates(h, b, ln, nullptr, 0, cnt, s, true)) return rc;
-        if (kT) {
+            if (n_charge) { if (int rc = qd_launch_closed(h, b, ln, SP, n_charge + base, cnt, s)) return rc; }
+            else if (int rc = qd_launch_candidates(h, b, ln, nullptr, 0, cnt, s, true)) return rc;
+            if (!kT) return qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND);
             // the thermal state instead of the ground state: c0 and <n> into the slots' zraw and occ, then the unchanged stages
             const dim3 tgrid((unsigned)(n < QD_THG_BLOCKS ? n : QD_THG_BLOCKS), cnt);
             // (a closed list is one hop component: the whole-block core, see qd_k_thermal_grid)
@@ -1232,24 +1205,14 @@ static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_quer
                                                                                                       var_dst, ztail_dst));
             }
             QD_HIP(hipGetLastError());
-        } else if (int rc = qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND)) return rc;
-        if (noise_flags & QD_NOISE_LATCH) {
+            return (int)QD_OK;
+        },
+        [&](int cnt, const QdEnvBufs& b) {
             const long rows = (long)cnt * ny;
-            QD_DISPATCH_N(h->N, qd_k_latch_grid<NN><<<dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s>>>(cnt, nx, ny, SP, b.params, b.occ,
+            QD_DISPATCH_N(h->N, qd_k_latch_grid<NN><<<dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s>>>(cnt, nx, ny, b.P, b.params, b.occ,
                                                                                                           b.zraw, qd_noise_cfg(h, b)));
-            QD_HIP(hipGetLastError());
-        }
-        if (int rc = qd_launch_sensor(h, b, nullptr, cnt, s)) return rc;
-        qd_k_line_pack<<<dim3((n + 255) / 256, cnt), dim3(256), 0, s>>>(n, SP, b.zraw, dense);
-        qd_launch_percentile(nullptr, (unsigned)cnt, (long)n, dense, b.plohi, s);
-        QD_HIP(hipGetLastError());
-        if (raw_dst || image_dst || plohi_dst || occ_dst) {
-            qd_k_grid_write<<<dim3((n + 255) / 256, cnt), dim3(256), 0, s>>>(Q, base, h->B, h->N, n, SP, dense, b.plohi, b.occ, raw_dst,
-                                                                             image_dst, plohi_dst, occ_dst);
-            QD_HIP(hipGetLastError());
-        }
-    }
-    return QD_OK;
+            return (int)QD_OK;
+        });
 }
 
 extern "C" int qd_scan_grid(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir, const double* range,

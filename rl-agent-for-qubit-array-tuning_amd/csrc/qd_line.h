@@ -1,12 +1,12 @@
 // qd_line.h -- dense 1-D sweeps along a DIRECTION VECTOR over the 2N controls (qd_scan1d): the reference model layer's
 // do1d_open(gate, min, max, points) over GateVoltageComposer.do1d (GateVoltageComposer.py:35-84, 213-222).  A line of n points
 // occupies a slot of its OWN size: Rl x Rl records with Rl = ceil(sqrt(n)), record p = point p, the Rl*Rl - n tail records
-// the inert all-zero record of qd_k_points_front.  The front kernel here fills the records in the hand-over form of the tile
+// the inert all-zero record (qd_inert_record, qd_query.h).  The front kernel here fills the records in the hand-over form of the tile
 // search, and the redo instantiation of the per-pixel search, the ground-state kernels, the telegraph chain, the sensor stage
 // and the percentile kernel then run on the slot with the geometry (Rl, Rl*Rl) as DATA: none of them is changed.  What a line
-// needs of its own is small: gather, front, the latching walk over ONE row of n points, a pack of the n leading values of a
-// slot into a dense row for the percentile kernel, and the write.  qd_line_voltages and the slot arithmetic are
-// __host__ __device__, so the CPU tier checks them (tests/hosttest_line).
+// needs of its own is small: gather (around qd_slot_copy, qd_query.h), front, the latching walk over ONE row of n points and
+// a pack of the n leading values of a slot into a dense row for the percentile kernel and for qd_k_query_write (qd_query.h).
+// qd_line_voltages and the slot arithmetic are __host__ __device__, so the CPU tier checks them (tests/hosttest_line).
 #pragma once
 #include "qd_points.h"
 
@@ -33,16 +33,15 @@ QD_HD int qd_line_batches(int n, int ppb) { const int r = qd_line_side(n); retur
 
 // ---------------------------------------------------------------------------
 // Front end of point t of a line of n: s = linspace(lo, hi, n)[t] and, with W0[2N] = [gate_v, sensor_v, barrier_v] of the state
-// block,  W[i] = fma(s, d[i], W0[i]);  then the frame, vpp and tc exactly as the tail of qd_affine_voltages: same operations,
-// same order, same fences.  With dx = d, dy = 0 and R = n, row 0 of an affine scan computes fma(sy, 0, fma(sx, d[i], W0[i])),
+// block,  W[i] = fma(s, d[i], W0[i]);  then the frame, vpp and tc by qd_control_voltages (qd_query.h), the tail of
+// qd_affine_voltages.  With dx = d, dy = 0 and R = n, row 0 of an affine scan computes fma(sy, 0, fma(sx, d[i], W0[i])),
 // which is the inner fma for finite sy (a sum with +0 changes no bits but those of -0): the bits of this function.
 // ---------------------------------------------------------------------------
 template <int N>
 QD_HD void qd_line_voltages(const double* par, const double* st, const QdLineAxes* axes, int n, int t,
                             double* v_ext, double* vpp, double* tc) {
-    constexpr int G = N + 1, NB = N - 1, V = 2 * N;
+    constexpr int G = N + 1, V = 2 * N;
     const QdLayout L = qd_layout(N);
-    const double* vgm = st + L.s_vgm;
     const double s = qd_linspace(axes->lo, axes->hi, n, t);
     double W[V];
 #pragma unroll
@@ -50,50 +49,35 @@ QD_HD void qd_line_voltages(const double* par, const double* st, const QdLineAxe
         const double w0 = i < N ? st[L.s_gate_v + i] : (i == N ? st[L.s_sensor_gt] : st[L.s_barrier_v + (i - G)]);
         W[i] = fma(s, axes->d[i], w0);
     }
-    if (axes->frame == QD_SCAN_PHYSICAL) {
-#pragma unroll
-        for (int i = 0; i < V; ++i) v_ext[i] = W[i];
-    } else {
-#pragma unroll
-        for (int i = 0; i < G; ++i) { v_ext[i] = qd_dotN<G>(vgm + i * G, W) + par[L.origin + i]; QD_ROW_FENCE(); }
-#pragma unroll
-        for (int b = 0; b < NB; ++b) v_ext[G + b] = W[G + b];
-    }
-#pragma unroll
-    for (int i = 0; i < G; ++i) { vpp[i] = qd_dotN<V>(par + L.cgd + i * V, v_ext); QD_ROW_FENCE(); }
-    const double tc_base = par[L.scal + 0];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        double vb_eff = v_ext[G + b] + qd_dotN<G>(par + L.cbg + b * G, v_ext);
-        tc[b] = tc_base * exp(-par[L.alpha + b] * vb_eff);
-        QD_ROW_FENCE();
-    }
+    qd_control_voltages<N>(par, st, axes->frame, W, v_ext, vpp, tc);
 }
 
 // ---------------------------------------------------------------------------
-// Record j of a slot: point j of the line (true: vpp and tc are in the record, vd, ncont and isa come back for the hand-over),
-// or, from n on, the inert record (false: all zero -- nvalid = 0, K copies of |0..0> without a coupling; the redo pass skips
-// it, the structure kernel finds every state isolated and emits no task).
+// Record of a slot that a front kernel fills before the search.  live: the point whose control voltages `voltages(v_ext, vpp,
+// tc)` computes (true: vpp and tc are in the record, vd, ncont and isa come back for the hand-over); else the inert record
+// (false; qd_inert_record).
 // ---------------------------------------------------------------------------
-template <int N>
-QD_HD bool qd_line_record(const double* par, const double* st, const QdLineAxes* axes, int n, int j, QdPixelRec* rec,
-                          double* v_ext, double* vd, double* ncont, double* isa) {
+template <int N, class Voltages>
+QD_HD bool qd_slot_record(const double* par, bool live, QdPixelRec* rec, double* v_ext, double* vd, double* ncont, double* isa,
+                          Voltages voltages) {
     constexpr int G = N + 1, NB = N - 1;
-    if (j >= n) {
-        static_assert(sizeof(QdPixelRec) % 8 == 0, "the inert record is written in 64-bit words");
-        unsigned long long* w = reinterpret_cast<unsigned long long*>(rec);
-#pragma unroll
-        for (int i = 0; i < (int)(sizeof(QdPixelRec) / 8); ++i) w[i] = 0ull;
-        return false;
-    }
+    if (!live) { qd_inert_record(rec); return false; }
     double vpp[G], tc[NB];
-    qd_line_voltages<N>(par, st, axes, n, j, v_ext, vpp, tc);
+    voltages(v_ext, vpp, tc);
     qd_point_front<N>(par, v_ext, vpp, tc, vd, ncont, isa);
 #pragma unroll
     for (int i = 0; i < G; ++i) rec->vpp[i] = vpp[i];
 #pragma unroll
     for (int b = 0; b < NB; ++b) rec->tc[b] = tc[b];
     return true;
+}
+
+// record j of a line's slot: point j of the line, or, from n on, the inert record
+template <int N>
+QD_HD bool qd_line_record(const double* par, const double* st, const QdLineAxes* axes, int n, int j, QdPixelRec* rec,
+                          double* v_ext, double* vd, double* ncont, double* isa) {
+    return qd_slot_record<N>(par, j < n, rec, v_ext, vd, ncont, isa,
+                             [&](double* ve, double* vpp, double* tc) { qd_line_voltages<N>(par, st, axes, n, j, ve, vpp, tc); });
 }
 
 #if defined(__HIPCC__)
@@ -105,52 +89,20 @@ QD_HD bool qd_line_record(const double* par, const double* st, const QdLineAxes*
 // in their z dimension (< 65536)
 #define QD_LINE_MAX_SLOTS 4096
 
-struct QdLineQuery {
-    const int* env_of_query;                                   // [nq]
-    const double* dir;                                         // [nq][2N]
-    const double *range, *gate_v, *barrier_v, *sensor_v;       // [nq][2], [nq][N], [nq][N-1], [nq] or null
-    const double *vgm, *gamma;                                 // [nq][G][G] or null, [nq] or null
-    int frame;
-};
-
-// a query renders when its env id is in [0, B): any direction is legal, the zero vector too (a repeated point)
-__device__ __forceinline__ bool qd_line_live(const QdLineQuery& Q, int q, int B) {
-    const int e = Q.env_of_query[q];
-    return e >= 0 && e < B;
-}
-
 // ---------------------------------------------------------------------------
-// gather: slot k (query base + k) <- parameter and state block of env env_of_query[base + k], with the base point, the
-// virtual gate matrix and the peak width of the query applied as qd_k_affine_gather applies them (constant width: scal[1] =
-// the query's gamma or the env's constant, scal[3] = -1); axes[k] <- range, direction and frame.  The Kalman block is copied
-// as it is: no kernel behind a line reads it.  A query that is not live renders a clamped env (the write kernel skips it).
-// grid = cnt, block = QD_LINE_BLOCK.
+// gather: slot k (query base + k) <- parameter and state block of env env_of_query[base + k] with the query applied
+// (qd_slot_copy, qd_query.h: the base point, the virtual gate matrix, the constant peak width); axes[k] <- range, direction
+// and frame.  The Kalman block is copied as it is: no kernel behind a line reads it.  A query that is not live renders a
+// clamped env (the write kernel skips it).  grid = cnt, block = QD_LINE_BLOCK.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(QD_LINE_BLOCK)
-qd_k_line_gather(QdLineQuery Q, int base, int B, int N, const double* __restrict__ params, const double* __restrict__ state,
+qd_k_line_gather(QdAffineQuery Q, int base, int B, int N, const double* __restrict__ params, const double* __restrict__ state,
                  double* __restrict__ sparams, double* __restrict__ sstate, QdLineAxes* __restrict__ axes) {
-    const QdLayout L = qd_layout(N);
-    const int k = blockIdx.x, q = base + k, nb = N - 1, G = N + 1, V = 2 * N;
-    int e = Q.env_of_query[q];
-    e = e < 0 ? 0 : (e >= B ? B - 1 : e);
-    const double* par = params + (size_t)e * L.size;
-    const double* st = state + (size_t)e * L.s_size;
-    double* dp = sparams + (size_t)k * L.size;
-    double* ds = sstate + (size_t)k * L.s_size;
+    const int k = blockIdx.x, q = base + k, V = 2 * N;
+    qd_slot_copy<QD_LINE_BLOCK>(Q, q, k, B, qd_layout(N), params, state, sparams, sstate, 0);
     QdLineAxes* A = axes + k;
-    for (int i = threadIdx.x; i < L.s_size; i += QD_LINE_BLOCK) {
-        double v = st[i];
-        if (i >= L.s_vgm && i < L.s_vgm + G * G) { if (Q.vgm) v = Q.vgm[(size_t)q * G * G + (i - L.s_vgm)]; }
-        else if (i >= L.s_gate_v && i < L.s_gate_v + N) v = Q.gate_v[(size_t)q * N + (i - L.s_gate_v)];
-        else if (i >= L.s_barrier_v && i < L.s_barrier_v + nb) v = Q.barrier_v[(size_t)q * nb + (i - L.s_barrier_v)];
-        else if (i == L.s_sensor_gt) v = Q.sensor_v ? Q.sensor_v[q] : 0.0;      // sensor_voltage=None -> 0.0
-        ds[i] = v;
-    }
-    for (int i = threadIdx.x; i < L.size; i += QD_LINE_BLOCK) if (i != L.scal + 1 && i != L.scal + 3) dp[i] = par[i];
     for (int i = threadIdx.x; i < 2 * QD_MAXN; i += QD_LINE_BLOCK) A->d[i] = i < V ? Q.dir[(size_t)q * V + i] : 0.0;
     if (threadIdx.x == 0) {
-        dp[L.scal + 1] = Q.gamma ? Q.gamma[q] : par[L.scal + 1];
-        dp[L.scal + 3] = -1.0;
         A->lo = Q.range[2 * (size_t)q]; A->hi = Q.range[2 * (size_t)q + 1];
         A->frame = Q.frame; A->pad = 0;
     }
@@ -191,31 +143,10 @@ qd_k_latch_lines(int n_slots, int n, int SP, const double* __restrict__ sparams,
 }
 
 // pack: the n leading values of each slot's SP into a dense [slots][n] buffer (the percentile kernel reads rows whose
-// stride equals their count).  grid = (ceil(n / 256), slots).
+// stride equals their count; qd_k_query_write then reads the same rows).  grid = (ceil(n / 256), slots).
 __global__ void qd_k_line_pack(int n, int SP, const double* __restrict__ sz, double* __restrict__ dense) {
     const int k = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p < n) dense[(size_t)k * n + p] = sz[(size_t)k * SP + p];
-}
-
-// ---------------------------------------------------------------------------
-// write: slot k -> the caller's slot base + k.  raw [nq][n] float64, image [nq][n] float32 normalised with the line's own
-// percentiles (qd_norm), plohi [nq][2], occupations [nq][n][N] float64; each may be null.  Queries that are not live leave
-// their slots untouched.  grid = (ceil(n / 256), cnt).
-// ---------------------------------------------------------------------------
-__global__ void qd_k_line_write(QdLineQuery Q, int base, int B, int N, int n, int SP, const double* __restrict__ dense,
-                                const double* __restrict__ splohi, const double* __restrict__ socc, double* __restrict__ raw_dst,
-                                float* __restrict__ image_dst, double* __restrict__ plohi_dst, double* __restrict__ occ_dst) {
-    const int k = blockIdx.y, q = base + k;
-    if (!qd_line_live(Q, q, B)) return;
-    const double lo = splohi[2 * k], hi = splohi[2 * k + 1];
-    if (plohi_dst && blockIdx.x == 0 && threadIdx.x < 2) plohi_dst[2 * (size_t)q + threadIdx.x] = threadIdx.x ? hi : lo;
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const double z = dense[(size_t)k * n + p];
-    if (raw_dst) raw_dst[(size_t)q * n + p] = z;
-    if (image_dst) image_dst[(size_t)q * n + p] = qd_norm(z, lo, hi);
-    if (occ_dst)
-        for (int i = 0; i < N; ++i) occ_dst[((size_t)q * n + p) * N + i] = socc[((size_t)k * SP + p) * N + i];
 }
 
 #endif  // __HIPCC__

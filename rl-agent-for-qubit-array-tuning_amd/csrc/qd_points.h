@@ -6,7 +6,7 @@
 // signal.  qd_point_front is __host__ __device__ like the rest of the pixel front end, so the CPU tier checks it against
 // qd_pixel_voltages (tests/hosttest_points).
 #pragma once
-#include "qd_pixel.h"
+#include "qd_query.h"
 
 // ---------------------------------------------------------------------------
 // a10 + a8 front end of one point.  par: env parameter block; v_ext[2N] = [physical gate voltages (G), barrier voltages (nb)].
@@ -61,9 +61,8 @@ qd_k_points_gather(QdPointSlots T, int N, const double* __restrict__ params, con
 
 // ---------------------------------------------------------------------------
 // front end, one point per lane: record j of slot k (channel j / P, pixel j % P of the slot's C*P records) <- point
-// T.start[k] + j in hand-over form, nvalid = QD_T_REDO: the redo pass searches it.  Past the slot's points an INERT record
-// (all zero: nvalid = 0, i.e. K copies of |0..0> without a coupling): the redo pass skips it, the structure kernel finds
-// every state isolated and emits no task.  grid = (ceil(C P / block), slots).
+// T.start[k] + j in hand-over form, nvalid = QD_T_REDO: the redo pass searches it.  Past the slot's points the inert record
+// (qd_inert_record, qd_query.h).  grid = (ceil(C P / block), slots).
 // ---------------------------------------------------------------------------
 template <int N>
 __global__ void __launch_bounds__(QD_POINTS_BLOCK)
@@ -75,13 +74,7 @@ qd_k_points_front(QdPointSlots T, int CP, const double* __restrict__ vg, const d
     const int j = blockIdx.x * QD_POINTS_BLOCK + threadIdx.x;
     if (j >= CP) return;
     QdPixelRec* rec = recs + (size_t)k * CP + j;
-    if (j >= T.cnt[k]) {
-        static_assert(sizeof(QdPixelRec) % 8 == 0, "the inert record is written in 64-bit words");
-        unsigned long long* w = reinterpret_cast<unsigned long long*>(rec);
-#pragma unroll
-        for (int i = 0; i < (int)(sizeof(QdPixelRec) / 8); ++i) w[i] = 0ull;
-        return;
-    }
+    if (j >= T.cnt[k]) { qd_inert_record(rec); return; }
     const double* par = qparams + (size_t)k * L.size;
     const size_t q = (size_t)(T.start[k] + j);
     double v_ext[V], vpp[G], tc[NB], vd[N], ncont[N], isa;

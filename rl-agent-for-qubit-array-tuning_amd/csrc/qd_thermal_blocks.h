@@ -288,7 +288,7 @@ QD_HD int qd_thermal_blocks_solve(QdThermalBlocksWs& W, int s, double kT) {
 }
 
 #if defined(__HIPCC__)
-#include "qd_grid.h"            // QdAffineQuery, qd_affine_live
+#include "qd_grid.h"            // QdAffineQuery, qd_query_live (qd_query.h)
 
 #define QD_THG_BLOCKS 4096      // blocks per slot at the most; the blocks of a slot stride over its points
 
@@ -306,9 +306,9 @@ __device__ __forceinline__ int qd_thg_solve(QdThermalWs& W, int s, double kT) { 
 // of blocks per CU cost 20 to 40 % there (measured).  Point p < n = nx*ny of slot k (query base + k, SP records per slot):
 // reads the record and the slot's parameter copy, runs qd_levels_record -> the core -> qd_thermal_moments and
 // writes the sensor constant to the slot's zraw and the occupations to the slot's occ, where the sensor stage and
-// qd_k_grid_write find them (c0 by the operations of qd_k_thermal), and var_dst[(q n + p) N + d], ztail_dst[q n + p] (either
+// qd_k_query_write find them (c0 by the operations of qd_k_thermal), and var_dst[(q n + p) N + d], ztail_dst[q n + p] (either
 // may be null) of the caller's rows; a query that is not live is rendered like any other and writes no caller's row
-// (qd_k_grid_write).  The inert records n .. SP-1 are not touched.  A record without a valid state counts as |0..0>.
+// (qd_k_query_write).  The inert records n .. SP-1 are not touched.  A record without a valid state counts as |0..0>.
 // ---------------------------------------------------------------------------------------------------------------
 template <int N, class WS>
 __global__ void __launch_bounds__(64)
@@ -320,7 +320,7 @@ qd_k_thermal_grid(QdAffineQuery Q, int base, int B, int n, int SP, int kept, con
     QdThermalWs& T = qd_thg_state(W);
     const QdLayout L = qd_layout(N);
     const int k = blockIdx.y, q = base + k;
-    const bool live = qd_affine_live(Q, q, B);
+    const bool live = qd_query_live(Q.env_of_query, nullptr, q, B, N);
     const double kT = kT_dev[q];
     const double* par = sparams + (size_t)k * L.size;
     for (int p = blockIdx.x; p < n; p += gridDim.x) {
