@@ -620,8 +620,8 @@ int qd_scan_grid_closed(qd_handle* h, const int32_t* env_of_query_dev, int nq, i
  * ground-state stage is not launched at all.  Stateless and stream-ordered as its siblings.
  * QD_ERR_ARG: what the siblings refuse; opts->struct_size != sizeof(qd_points_opts); n_levels outside 0..QD_LEVELS_MAX;
  * n_levels > 0 with levels_dst NULL; states_dst without n_charge_host.  QD_ERR_STATE: QD_FLAG_VALIDATE handles and handles in
- * the full charge-state space, as the siblings.  Eigenvectors of excited levels, noisy or latched points and levels inside
- * qd_step, probes, scans, lines and grids are not built. */
+ * the full charge-state space, as the siblings.  Levels over a grid are qd_scan_grid_levels below.  Eigenvectors of excited
+ * levels, noisy or latched points and levels inside qd_step, probes, scans and lines are not built. */
 #define QD_LEVELS_MAX 8
 typedef struct qd_points_opts {
     int32_t struct_size;            /* = sizeof(qd_points_opts) */
@@ -700,7 +700,7 @@ int qd_eval_points_thermal(qd_handle* h, const int32_t* group_env_host, const in
  * sizeof(qd_grid_thermal_opts); QD_NOISE_LATCH; any noise flag together with n_charge_dev; an n_charge outside 0..32767.
  * QD_ERR_STATE: QD_FLAG_VALIDATE handles and handles in the full charge-state space.  Stateless and stream-ordered as its
  * siblings, on their scratch; nothing any other call can see changes.  Temperature in qd_scan1d, qd_scan2d, qd_scan_affine,
- * probes and qd_step, levels over a grid and latched thermal points are not built. */
+ * probes and qd_step and latched thermal points are not built.  Levels over a grid are qd_scan_grid_levels below. */
 typedef struct qd_grid_thermal_opts {
     int32_t struct_size;            /* = sizeof(qd_grid_thermal_opts) */
     int32_t reserved;               /* 0 */
@@ -712,6 +712,45 @@ int qd_scan_grid_thermal(qd_handle* h, const int32_t* env_of_query_dev, int nq, 
                          const double* range_dev, const double* gate_v_dev, const double* barrier_v_dev,
                          const double* sensor_v_dev, const double* kT_dev, double* raw_dst, float* image_dst,
                          double* plohi_dst, const qd_scan_grid_opts* opts, const qd_grid_thermal_opts* topts, void* stream);
+
+/* ENERGY LEVELS on a grid: qd_scan_grid_levels is qd_scan_grid / qd_scan_grid_closed that also hands out the lowest eigenvalues
+ * and ||H||_inf of qd_eval_points_ex at every point -- the gap map levels[1] - levels[0] over, say, detuning x barrier, and
+ * rel_gap = gap / hnorm, the validity mask of the T = 0 diagram.  It takes the arguments of qd_scan_grid and
+ *   lopts          required.  n_levels in 1..QD_LEVELS_MAX.  n_charge_dev [nq] DEVICE int32 or NULL: the closed regime of
+ *                  qd_scan_grid_closed.  levels_dst [nq][ny][nx][n_levels] DEVICE float64, required; hnorm_dst [nq][ny][nx]
+ *                  DEVICE float64 or NULL.
+ * Hamiltonian, levels (+inf from nv on, non-decreasing, equal eigenvalues bitwise equal), norm, truncation and the accuracy
+ * of 1e-12 ||H||_inf are those of qd_eval_points_ex.
+ * The call runs qd_scan_grid's slot loop with ONE kernel added: the levels grid kernel of csrc/qd_levels_blocks.h, one point
+ * per wavefront, right behind the search and BEFORE the ground-state stage, on the list as the search left it.  Every other
+ * launch is that of qd_scan_grid or qd_scan_grid_closed, so raw, image, plohi and opts->occ_dst equal those calls bit for bit
+ * under the same arguments, sensor noise and latching in the open regime included; the levels do not depend on the noise
+ * flags.  raw_dst, image_dst and plohi_dst may be NULL where qd_scan_grid allows it.
+ * Open regime: the solver is not the one of qd_eval_points_ex.  The Householder tridiagonalisation runs inside the connected
+ * components of the coupling pattern, all components at once (states of different components never couple; exact zeros do
+ * not link), and the multisection runs on the components' tridiagonals laid side by side.  The two calls agree within the
+ * sum of their bars, 2e-12 hnorm, at the same voltages and are NOT bitwise equal.  A closed list is one total-charge sector,
+ * which hops connect: one component, so the closed regime runs the kernel on the whole-block solver of qd_eval_points_ex, and
+ * a closed levels grid in the physical frame equals that call at the grid's voltages bit for bit.  (Measured ahead of the
+ * whole-block solver in the open regime: 4 and 8 dots at K = 8 and 32; other N and K are unmeasured.)  Results do
+ * not depend on how queries fall into launches, and repeated calls give the same bits.  A query with an env id outside
+ * 0..B-1 writes no row.
+ * QD_ERR_ARG: what qd_scan_grid or (with n_charge_dev) qd_scan_grid_closed refuse; lopts NULL; lopts->struct_size !=
+ * sizeof(qd_grid_levels_opts); n_levels outside 1..QD_LEVELS_MAX; levels_dst NULL.  QD_ERR_STATE: QD_FLAG_VALIDATE handles
+ * and handles in the full charge-state space.  Stateless and stream-ordered as its siblings, on their scratch; nothing any
+ * other call can see changes.  Eigenvectors or occupations of excited levels and levels in qd_scan1d, qd_scan2d,
+ * qd_scan_affine, probes and qd_step are not built. */
+typedef struct qd_grid_levels_opts {
+    int32_t struct_size;            /* = sizeof(qd_grid_levels_opts) */
+    int32_t n_levels;               /* 1 .. QD_LEVELS_MAX */
+    const int32_t* n_charge_dev;    /* NULL: open regime; else [nq], the closed regime, as qd_scan_grid_closed */
+    double* levels_dst;             /* [nq][ny][nx][n_levels], device, required */
+    double* hnorm_dst;              /* [nq][ny][nx], device, may be NULL */
+} qd_grid_levels_opts;
+int qd_scan_grid_levels(qd_handle* h, const int32_t* env_of_query_dev, int nq, int nx, int ny, const double* dir_dev,
+                        const double* range_dev, const double* gate_v_dev, const double* barrier_v_dev,
+                        const double* sensor_v_dev, double* raw_dst, float* image_dst, double* plohi_dst,
+                        const qd_scan_grid_opts* opts, const qd_grid_levels_opts* lopts, void* stream);
 
 /* Stitches one channel of nx*ny probe signals into one composite image on the device (map_device_range.py:134-170,
  * map_full_device_range.py:168-194).  raw_dev [nx*ny][C][P] as qd_probe wrote it, query index i*ny + j for scan (i, j);

@@ -20,6 +20,7 @@
 #include "qd_levels.h"
 #include "qd_thermal.h"
 #include "qd_thermal_blocks.h"
+#include "qd_levels_blocks.h"
 #include "qd_scratch.h"
 
 // The owners of a stream and of an event.  With the two memory policies of qd_scratch.h these are the only places that
@@ -1148,16 +1149,29 @@ static int qd_check_device_range(const qd_handle* h, const char* who, const T* d
     return bad ? qd_failf(h, QD_ERR_ARG, range_fmt, who) : (int)QD_OK;
 }
 
+// Which core the levels kernel of a grid runs on: the whole-block one in the closed regime (one component per list), the
+// per-component one in the open regime.  MEASURED ahead of the whole-block core there by more than the run-to-run spread are 4
+// and 8 dots at K = 8 and K = 32 (19 to 58 % at K = 32, 10 to 13 % at 4 dots and K = 8, 1.3 to 1.7 % at 8 dots and K = 8, the
+// narrowest cell: DESIGN 7); every other N and K is unmeasured.  Under the measurement-only build macro QD_LVG_FORCE_WHOLE
+// (scripts/levels_grid_rate.py, route c) every grid runs the whole-block core.
+#ifdef QD_LVG_FORCE_WHOLE
+#define QD_LVG_WHOLE(n_charge) true
+#else
+#define QD_LVG_WHOLE(n_charge) ((n_charge) != nullptr)
+#endif
+
 // qd_scan_grid (n_charge null) and qd_scan_grid_closed on the runner of the lines: the closed regime replaces the redo pass of
 // the open search by qd_k_closed at the queries' total charges and leaves every other launch as it is.  kT ([nq], device):
 // qd_scan_grid_thermal, the thermal kernel of qd_thermal_blocks.h in place of the ground-state stage, once, on the lists as the
-// search left them; the slots always carry occupations then.
+// search left them; the slots always carry occupations then.  n_levels > 0: qd_scan_grid_levels, the levels kernel of
+// qd_levels_blocks.h behind the search and before the ground-state stage, which reads the records and writes the caller's rows.
 static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
                        const double* range, const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst,
                        float* image_dst, double* plohi_dst, const qd_scan_grid_opts* opts, const int32_t* n_charge, void* stream,
-                       const double* kT = nullptr, double* var_dst = nullptr, double* ztail_dst = nullptr) {
+                       const double* kT = nullptr, double* var_dst = nullptr, double* ztail_dst = nullptr, int n_levels = 0,
+                       double* levels_dst = nullptr, double* hnorm_dst = nullptr) {
     static_assert(QD_GRID_MAX_SLOTS == QD_GRID_SLOTS, "qdsim.h states the bound");
-    static_assert(QD_THG_BLOCKS <= QD_GRID_MAX_SLOTS, "a launch dimension");
+    static_assert(QD_THG_BLOCKS <= QD_GRID_MAX_SLOTS && QD_LVG_BLOCKS <= QD_GRID_MAX_SLOTS, "a launch dimension");
     QdQueryOpts o;
     if (int rc = qd_check_scan_arrays(h, who, nq, env_of_query, dir, "dir_dev", range, gate_v, barrier_v)) return rc;
     if (nx < 1 || ny < 1 || (long long)nx * ny > h->P)
@@ -1192,6 +1206,19 @@ static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_quer
             QD_HIP(hipGetLastError());
             if (n_charge) { if (int rc = qd_launch_closed(h, b, ln, SP, n_charge + base, cnt, s)) return rc; }
             else if (int rc = qd_launch_candidates(h, b, ln, nullptr, 0, cnt, s, true)) return rc;
+            if (n_levels > 0) {
+                // the levels of the list as the search left it (a closed list is one hop component: the whole-block core)
+                const dim3 lgrid((unsigned)(n < QD_LVG_BLOCKS ? n : QD_LVG_BLOCKS), cnt);
+                if (QD_LVG_WHOLE(n_charge)) {
+                    QD_DISPATCH_N(h->N, qd_k_levels_grid<NN, QdLevelsWs><<<lgrid, dim3(64), 0, s>>>(env_of_query, base, h->B, n, SP, h->kept,
+                                                                                                  n_levels, ln.recs.p, levels_dst, hnorm_dst));
+                } else {
+                    QD_DISPATCH_N(h->N, qd_k_levels_grid<NN, QdLevelsBlocksWs><<<lgrid, dim3(64), 0, s>>>(env_of_query, base, h->B, n, SP,
+                                                                                                        h->kept, n_levels, ln.recs.p,
+                                                                                                        levels_dst, hnorm_dst));
+                }
+                QD_HIP(hipGetLastError());
+            }
             if (!kT) return qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND);
             // the thermal state instead of the ground state: c0 and <n> into the slots' zraw and occ, then the unchanged stages
             const dim3 tgrid((unsigned)(n < QD_THG_BLOCKS ? n : QD_THG_BLOCKS), cnt);
@@ -1244,6 +1271,22 @@ extern "C" int qd_scan_grid_thermal(qd_handle* h, const int32_t* env_of_query, i
     return qd_grid_run(h, "qd_scan_grid_thermal", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
                        plohi_dst, opts, topts ? topts->n_charge_dev : nullptr, stream, kT, topts ? topts->var_dst : nullptr,
                        topts ? topts->ztail_dst : nullptr);
+}
+
+extern "C" int qd_scan_grid_levels(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
+                                   const double* range, const double* gate_v, const double* barrier_v, const double* sensor_v,
+                                   double* raw_dst, float* image_dst, double* plohi_dst, const qd_scan_grid_opts* opts,
+                                   const qd_grid_levels_opts* lopts, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    if (!lopts) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_levels: lopts is NULL");
+    if (lopts->struct_size != (int32_t)sizeof(qd_grid_levels_opts))
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_levels: lopts->struct_size is not sizeof(qd_grid_levels_opts)");
+    if (lopts->n_levels < 1 || lopts->n_levels > QD_LEVELS_MAX)
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_levels: n_levels must be in 1..QD_LEVELS_MAX (8)");
+    if (!lopts->levels_dst) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_levels: levels_dst is NULL");
+    return qd_grid_run(h, "qd_scan_grid_levels", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
+                       plohi_dst, opts, lopts->n_charge_dev, stream, nullptr, nullptr, nullptr, lopts->n_levels, lopts->levels_dst,
+                       lopts->hnorm_dst);
 }
 
 // slots in flight of qd_eval_points: one launch chunk of lane 0's records, at most QD_POINTS_SLOTS

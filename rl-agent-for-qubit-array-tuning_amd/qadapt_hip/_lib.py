@@ -32,7 +32,7 @@ EXPORTS = [
     "qd_time_ground_kernel", "qd_time_candidates_kernel", "qd_time_kernels", "qd_timed_kernel_name", "qd_chunk_envs",
     "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex", "qd_scan_affine",
     "qd_scan_grid", "qd_eval_points_closed", "qd_scan_grid_closed", "qd_eval_points_ex",
-    "qd_eval_points_thermal", "qd_scan_grid_thermal",
+    "qd_eval_points_thermal", "qd_scan_grid_thermal", "qd_scan_grid_levels",
 ]
 # exported too, kept apart: names with a digit, which a scan of qdsim.h for `qd_[a-z_]+(` does not find
 EXPORTS_WITH_DIGITS = ["qd_scan2d", "qd_scan1d"]
@@ -118,6 +118,15 @@ class QdGridThermalOpts(ctypes.Structure):
     _fields_ = [
         ("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_charge_dev", ctypes.c_void_p),
         ("var_dst", ctypes.c_void_p), ("ztail_dst", ctypes.c_void_p),
+    ]
+
+
+class QdGridLevelsOpts(ctypes.Structure):
+    """qd_grid_levels_opts of include/qdsim.h: the number of energy levels per point of a qd_scan_grid_levels call, the (closed
+    regime) total charges of its queries and the destinations of the levels and the norms, all on the device."""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("n_levels", ctypes.c_int32), ("n_charge_dev", ctypes.c_void_p),
+        ("levels_dst", ctypes.c_void_p), ("hnorm_dst", ctypes.c_void_p),
     ]
 
 
@@ -220,6 +229,9 @@ def lib():
     L.qd_scan_grid_thermal.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, dp, dp, fp, dp,
                                        ctypes.POINTER(QdScanGridOpts), ctypes.POINTER(QdGridThermalOpts), vp]
     L.qd_scan_grid_thermal.restype = ctypes.c_int
+    L.qd_scan_grid_levels.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, dp, fp, dp,
+                                      ctypes.POINTER(QdScanGridOpts), ctypes.POINTER(QdGridLevelsOpts), vp]
+    L.qd_scan_grid_levels.restype = ctypes.c_int
     _LIB = L
     return L
 

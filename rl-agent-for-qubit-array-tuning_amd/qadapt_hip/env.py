@@ -270,6 +270,34 @@ class ModelFacade:
         return (host(out["raw"]).astype(np.float64)[0, 0][:, None], host(out["occupations"]).astype(np.float64)[0, 0],
                 host(out["variance"]).astype(np.float64)[0, 0])
 
+    def do2d_levels(self, x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points, n_levels=2, n_charge=None):
+        """The energy levels over do2d_open's grid (n_charge None) or do2d_closed's: the grid of energy_levels_open /
+        energy_levels_closed, rendered by the backend's scan_grid_levels in one call -- levels[..., 1] - levels[..., 0] is the gap
+        map.  Gate grammar, base point, frames and the one-frame rule are do2d_open's.  Returns (levels (y_points, x_points,
+        n_levels), hnorm (y_points, x_points)) float64."""
+        N = self.n_dot
+        (x_axis, x_frame), (y_axis, y_frame) = self._gate_axis(x_gate), self._gate_axis(y_gate)
+        if x_frame != y_frame:
+            raise NotImplementedError(f"do2d_levels({x_gate!r}, ..., {y_gate!r}, ...): one call has one frame, and {x_gate!r} is "
+                                      f"{x_frame} while {y_gate!r} is {y_frame}; sweep two physical gates or two virtual axes")
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        args = ([0], x_axis, y_axis, (float(x_min), float(x_max)), (float(y_min), float(y_max)), int(x_points), int(y_points),
+                np.zeros((1, N)), np.zeros((1, N - 1)))
+        out = self._b.scan_grid_levels(*args, 0.0, levels=int(n_levels), n_charge=n_charge, frame=x_frame, gamma=gamma)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return host(out["levels"]).astype(np.float64)[0], host(out["hnorm"]).astype(np.float64)[0]
+
+    def do1d_levels(self, gate, min, max, points, n_levels=2, n_charge=None):
+        """The energy levels over do1d_open's sweep (n_charge None) or do1d_closed's, rendered as a one-row levels grid.  Returns
+        (levels (points, n_levels), hnorm (points,)) float64."""
+        N = self.n_dot
+        axis, frame = self._gate_axis(gate)
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        args = ([0], axis, np.zeros(2 * N), (float(min), float(max)), (0.0, 0.0), int(points), 1, np.zeros((1, N)), np.zeros((1, N - 1)))
+        out = self._b.scan_grid_levels(*args, 0.0, levels=int(n_levels), n_charge=n_charge, frame=frame, gamma=gamma)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return host(out["levels"]).astype(np.float64)[0, 0], host(out["hnorm"]).astype(np.float64)[0, 0]
+
 
 class ArrayFacade:
     """`env.array` of the reference (a QarrayBaseClass) as far as its users outside step() need it: `model.cgd_full`,
@@ -384,6 +412,16 @@ class ArrayFacade:
         out = self._b.scan_grid_thermal([0], x, y, x_range, y_range, nx, ny, np.asarray(gate_voltages, np.float64)[None, :],
                                         np.asarray(barrier_voltages, np.float64)[None, :], kT,
                                         sensor_voltage=None if sensor_voltage is None else float(sensor_voltage), **kw)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return {k: host(v)[0] for k, v in out.items()}
+
+    def scan_grid_levels(self, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage=None, **kw):
+        """The backend's scan_grid_levels for this env (scan_grid with the energy levels of every point, open or with n_charge=
+        closed): one query, numpy results without the query axis, "levels" (ny, nx, L) and "hnorm" (ny, nx) and, for L >= 2,
+        "gap" and "rel_gap" (ny, nx) among them."""
+        out = self._b.scan_grid_levels([0], x, y, x_range, y_range, nx, ny, np.asarray(gate_voltages, np.float64)[None, :],
+                                       np.asarray(barrier_voltages, np.float64)[None, :],
+                                       sensor_voltage=None if sensor_voltage is None else float(sensor_voltage), **kw)
         host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
         return {k: host(v)[0] for k, v in out.items()}
 

@@ -685,7 +685,7 @@ class VecQuantumDeviceEnv:
         noise included).  Returns device tensors {"raw": (nq, ny, nx) float64, "image": (nq, ny, nx) float32 normalised per
         grid with its own 0.5 / 99.5 percentiles, "plohi": (nq, 2)}, plus, with occupations=True, {"occupations":
         (nq, ny, nx, N) float64}.  scan_grid_closed is the same grid at a fixed total charge, scan_grid_thermal the same grid
-        at a temperature."""
+        at a temperature, scan_grid_levels the same grid with the energy levels of every point."""
         return self._scan_grid(env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm,
                                gamma, noise, serial, stream_base, occupations, None)
 
@@ -725,9 +725,36 @@ class VecQuantumDeviceEnv:
         return self._scan_grid(env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm,
                                gamma, noise, serial, stream_base, occupations, n_charge, kT, variance, ztail)
 
+    def scan_grid_levels(self, env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage=None, *,
+                         levels=2, n_charge=None, frame="virtual", vgm=None, gamma=None, noise=(), serial=None, stream_base=None,
+                         occupations=False):
+        """scan_grid (n_charge None) or scan_grid_closed that also hands out the ENERGY LEVELS of every point
+        (qd_scan_grid_levels): the `levels` lowest eigenvalues and ||H||_inf of the point's truncated Hamiltonian, as
+        eval_points(levels=) defines them -- the gap map levels[1] - levels[0] over, say, detuning x barrier, from which a tunnel
+        coupling is read off the anticrossing sqrt(eps^2 + 4 t^2), and rel_gap, the validity mask of the T = 0 diagram (below
+        about 1e-9 float64 does not resolve the ground vector, and the point's occupations are round-off).  Arguments, frames
+        and results are scan_grid's, and
+          levels            1..8, the number of levels per point
+          n_charge          None: the open regime.  A scalar or (nq,) integers in 0..32767: the closed regime of scan_grid_closed
+          noise             as in scan_grid, open regime only; the levels do not depend on it
+        Returns scan_grid's dict -- "raw", "image", "plohi" and "occupations" equal scan_grid / scan_grid_closed bit for bit under
+        the same arguments -- plus {"levels": (nq, ny, nx, levels) float64, +inf from the point's number of valid kept states
+        on, "hnorm": (nq, ny, nx)} and, for levels >= 2, {"gap": levels[..., 1] - levels[..., 0] (+inf where levels[..., 1]
+        is), "rel_gap": gap / hnorm}.
+        In the open regime the kernel tridiagonalises each hop component of a point by itself; it agrees with
+        eval_points(levels=) at the same voltages within 2e-12 hnorm, not bit for bit.  A closed list is one hop component, so
+        the whole-block solver of eval_points runs, and in the physical frame the levels equal
+        eval_points(..., n_charge=, levels=) at the grid's voltages bit for bit."""
+        L = int(levels)
+        if L != levels or L < 1 or L > _lib.QD_LEVELS_MAX:
+            raise ValueError(f"levels must be an integer in 1..{_lib.QD_LEVELS_MAX}, got {levels!r}")
+        return self._scan_grid(env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm,
+                               gamma, noise, serial, stream_base, occupations, n_charge, levels=L)
+
     def _scan_grid(self, env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm, gamma,
-                   noise, serial, stream_base, occupations, n_charge, kT=None, variance=False, ztail=False):
-        """scan_grid (n_charge None) and scan_grid_closed; with kT, scan_grid_thermal in either regime"""
+                   noise, serial, stream_base, occupations, n_charge, kT=None, variance=False, ztail=False, levels=0):
+        """scan_grid (n_charge None) and scan_grid_closed; with kT, scan_grid_thermal in either regime; with levels,
+        scan_grid_levels in either regime"""
         N = self.N
         if frame not in ("virtual", "physical"):
             raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
@@ -783,6 +810,22 @@ class VecQuantumDeviceEnv:
                                                 _ptr(kd), _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]),
                                                 ctypes.byref(opts), ctypes.byref(topts), self._stream())
             _lib.check(self._h, rc, "qd_scan_grid_thermal")
+            return out
+        if levels:
+            out["levels"] = torch.zeros((nq, cy, cx, levels), dtype=torch.float64, device=self.device)
+            out["hnorm"] = torch.zeros((nq, cy, cx), dtype=torch.float64, device=self.device)
+            lopts = _lib.QdGridLevelsOpts(struct_size=ctypes.sizeof(_lib.QdGridLevelsOpts), n_levels=int(levels), n_charge_dev=addr(qd),
+                                          levels_dst=addr(out["levels"]), hnorm_dst=addr(out["hnorm"]))
+            rc = self._lib.qd_scan_grid_levels(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
+                                               _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]), ctypes.byref(opts),
+                                               ctypes.byref(lopts), self._stream())
+            _lib.check(self._h, rc, "qd_scan_grid_levels")
+            if levels >= 2:
+                # (+inf wherever the second level is: a point with one valid state, and one with none, where inf - inf would be nan
+                # and hnorm is 0)
+                l0, l1 = out["levels"][..., 0], out["levels"][..., 1]
+                out["gap"] = torch.where(torch.isinf(l1), l1, l1 - l0)
+                out["rel_gap"] = out["gap"] / out["hnorm"]
             return out
         if qd is not None:
             rc = self._lib.qd_scan_grid_closed(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
