@@ -409,7 +409,13 @@ QD_HD double qd_peak_width_pair(const double* par, const double* st, const QdLay
 // ---------------------------------------------------------------------------
 // KC (8, 16 or 32) is the size of the kept set: the handle runs the smallest KC >= num_charge_states, and the
 // first K entries of the (E, idx)-sorted KC list are the K lowest.
-template <int N, int KC = QD_K>
+// PACKED selects the form of the insert path (qd_search_insert and what it calls); the default comes from QD_SEARCH_PACKED
+// (scripts/ab_build.sh NAME -DQD_SEARCH_PACKED=0 builds the earlier form).  Both forms make the same comparisons in the
+// same order and leave the same buffer, maxima, slots and lim (tests/hosttest_insert runs one against the other).
+#ifndef QD_SEARCH_PACKED
+#define QD_SEARCH_PACKED 1          // insert: group slots packed in one word, rescan energies in one LDS trip
+#endif
+template <int N, int KC = QD_K, bool PACKED = (QD_SEARCH_PACKED != 0)>
 struct QdSearch {
     static_assert(KC == 8 || KC == 16 || KC == 32, "kept sets come in groups of 8");
     static constexpr int NG = KC / 8;
@@ -423,50 +429,103 @@ struct QdSearch {
     double* e; int es;               // energies, stride
     uint16_t* id; int is;            // indices, stride
     int count;
-    double gE[NG]; unsigned gI[NG]; int gS[NG];  // per-group maxima of the kept buffer
+    double gE[NG]; unsigned gI[NG];  // per-group maxima of the kept buffer
+    int gS[NG];                      // their slots (!PACKED)
+    unsigned gSp = 0;                // their slots, group j in bits 8j..8j+7 (PACKED: no array under a run-time index)
     double maxE; unsigned maxI; int maxS, maxG;  // overall maximum (the KC-th best)
     double lim;                      // prune when (partial + tail) > lim   (relative to Em)
     unsigned idx;
     unsigned long long nodes, leaves, inserts, shifts;   // statistics (host harness only)
+    QD_HD int group_slot(int j) const { return PACKED ? (int)((gSp >> (8 * j)) & 0xFFu) : gS[j]; }
 };
 
 // The kept set lives in caller-provided strided storage (LDS on the GPU) as an UNSORTED buffer
 // split into KC / 8 groups of 8 slots; the lexicographic (E, idx) maximum of each group is cached in
-// registers.  Replacing the overall maximum costs one write + an 8-slot rescan (independent
-// reads) instead of a chain of dependent compare-and-shift steps.  qd_search_sort() orders the
-// final list when the caller wants the reference order.
+// registers.  Replacing the overall maximum costs one write + an 8-slot rescan instead of a chain of
+// dependent compare-and-shift steps.  qd_search_sort() orders the final list when the caller wants
+// the reference order.
 template <int N>
 QD_HD bool qd_lex_less(double ea, unsigned ia, double eb, unsigned ib) {
     // bitwise on purpose: short-circuit operators become divergent branches in the leaf loop
     return (bool)((int)(ea < eb) | ((int)(ea == eb) & (int)(ia < ib)));
 }
 
-template <int N, int KC>
-QD_HD void qd_search_rescan_group(QdSearch<N, KC>& S, int g) {
-    double me = -INFINITY; unsigned mi = 0; int ms = g * 8;
+// The (E, idx) maximum of group g, first slot first, a later slot taking over only when strictly greater.
+// !PACKED reads (E, id) of a slot, compares, then reads the next slot: on the device each pair waits for its own LDS
+// round trip, eight in series.
+// PACKED reads the eight energies first (on the device back to back, one round trip: the barrier keeps the compares behind
+// the loads) and takes the first slot of the largest E with strict <.  An id decides only between slots of EQUAL E, so
+// with one slot at the largest E the answer is that slot and its id is the one further read; with several (rare: exact
+// ties in float64) the largest id among them wins, first slot first with strict <, which is what the serial chain of
+// lexicographic compares arrives at.  Kept energies are never NaN (qd_search_insert), so == and < are a total order here.
+template <int N, int KC, bool PACKED>
+QD_HD void qd_search_rescan_group(QdSearch<N, KC, PACKED>& S, int g) {
+    double me; unsigned mi; int ms;
+    if constexpr (PACKED) {
+        double e[8];
 #pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const int sl = g * 8 + t;
-        const double e = S.e[sl * S.es]; const unsigned i = S.id[sl * S.is];
-        if (t == 0 || qd_lex_less<N>(me, mi, e, i)) { me = e; mi = i; ms = sl; }
+        for (int t = 0; t < 8; ++t) e[t] = S.e[(g * 8 + t) * S.es];
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+        me = e[0]; int mt = 0, ntie = 1;                  // ntie: slots at the running maximum
+#pragma unroll
+        for (int t = 1; t < 8; ++t) {
+            const bool up = me < e[t], eq = me == e[t];
+            me = up ? e[t] : me; mt = up ? t : mt; ntie = up ? 1 : ntie + (int)eq;
+        }
+        ms = g * 8 + mt;
+        mi = S.id[ms * S.is];
+        if (ntie > 1) {
+#pragma unroll 1
+            for (int t = mt + 1; t < 8; ++t) {
+                const int sl = g * 8 + t;
+                const unsigned i = S.id[sl * S.is];
+                if ((int)(S.e[sl * S.es] == me) & (int)(mi < i)) { mi = i; ms = sl; }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < QdSearch<N, KC, PACKED>::NG; ++j) {
+            const bool here = j == g;
+            S.gE[j] = here ? me : S.gE[j]; S.gI[j] = here ? mi : S.gI[j];
+        }
+        S.gSp = (S.gSp & ~(0xFFu << (8 * g))) | ((unsigned)ms << (8 * g));
+    } else {
+        me = -INFINITY; mi = 0; ms = g * 8;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const int sl = g * 8 + t;
+            const double e = S.e[sl * S.es]; const unsigned i = S.id[sl * S.is];
+            if (t == 0 || qd_lex_less<N>(me, mi, e, i)) { me = e; mi = i; ms = sl; }
+        }
+#pragma unroll
+        for (int j = 0; j < QdSearch<N, KC, PACKED>::NG; ++j) if (j == g) { S.gE[j] = me; S.gI[j] = mi; S.gS[j] = ms; }
     }
-#pragma unroll
-    for (int j = 0; j < QdSearch<N, KC>::NG; ++j) if (j == g) { S.gE[j] = me; S.gI[j] = mi; S.gS[j] = ms; }
 }
 
-template <int N, int KC>
-QD_HD void qd_search_set_bound(QdSearch<N, KC>& S) {
+template <int N, int KC, bool PACKED>
+QD_HD void qd_search_set_bound(QdSearch<N, KC, PACKED>& S) {
     // overall maximum = lexicographic max of the group maxima
-    int g = 0; double bound = S.gE[0]; unsigned bi = S.gI[0]; int bs = S.gS[0];
+    int g = 0; double bound = S.gE[0]; unsigned bi = S.gI[0]; int bs;
+    if constexpr (PACKED) {
 #pragma unroll
-    for (int j = 1; j < QdSearch<N, KC>::NG; ++j)
-        if (qd_lex_less<N>(bound, bi, S.gE[j], S.gI[j])) { bound = S.gE[j]; bi = S.gI[j]; bs = S.gS[j]; g = j; }
+        for (int j = 1; j < QdSearch<N, KC, PACKED>::NG; ++j) {
+            const bool up = qd_lex_less<N>(bound, bi, S.gE[j], S.gI[j]);
+            bound = up ? S.gE[j] : bound; bi = up ? S.gI[j] : bi; g = up ? j : g;
+        }
+        bs = S.group_slot(g);
+    } else {
+        bs = S.gS[0];
+#pragma unroll
+        for (int j = 1; j < QdSearch<N, KC, PACKED>::NG; ++j)
+            if (qd_lex_less<N>(bound, bi, S.gE[j], S.gI[j])) { bound = S.gE[j]; bi = S.gI[j]; bs = S.gS[j]; g = j; }
+    }
     S.maxE = bound; S.maxI = bi; S.maxS = bs; S.maxG = g;
     S.lim = (bound - S.Em) + ((fabs(bound) + fabs(S.Em)) * 1e-11 + 1e-300);
 }
 
-template <int N, int KC>
-QD_HD void qd_search_insert(QdSearch<N, KC>& S, double E, unsigned idx) {
+template <int N, int KC, bool PACKED>
+QD_HD void qd_search_insert(QdSearch<N, KC, PACKED>& S, double E, unsigned idx) {
     if (!(E < INFINITY)) return;                          // inf / NaN: treated as invalid
 #ifndef __HIP_DEVICE_COMPILE__
     S.inserts++;
@@ -476,7 +535,7 @@ QD_HD void qd_search_insert(QdSearch<N, KC>& S, double E, unsigned idx) {
         S.count++;
         if (S.count == KC) {
 #pragma unroll
-            for (int g = 0; g < QdSearch<N, KC>::NG; ++g) qd_search_rescan_group(S, g);
+            for (int g = 0; g < QdSearch<N, KC, PACKED>::NG; ++g) qd_search_rescan_group(S, g);
             qd_search_set_bound(S);
         }
         return;
@@ -488,8 +547,8 @@ QD_HD void qd_search_insert(QdSearch<N, KC>& S, double E, unsigned idx) {
 }
 
 // in-place insertion sort of the kept entries by (E, idx)
-template <int N, int KC>
-QD_HD void qd_search_sort(QdSearch<N, KC>& S) {
+template <int N, int KC, bool PACKED>
+QD_HD void qd_search_sort(QdSearch<N, KC, PACKED>& S) {
     for (int i = 1; i < S.count; ++i) {
         const double E = S.e[i * S.es]; const unsigned idx = S.id[i * S.is];
         int pos = i;
@@ -510,9 +569,9 @@ struct QdSplit {
     static constexpr int A = (B - 3 >= 0) ? B - 3 : -1;
 };
 
-template <int N, int L, int KC>
+template <int N, int L, int KC, bool PACKED = (QD_SEARCH_PACKED != 0)>
 struct QdLevel {
-    static QD_HD void run(QdSearch<N, KC>& S, double partial) {
+    static QD_HD void run(QdSearch<N, KC, PACKED>& S, double partial) {
 #ifndef __HIP_DEVICE_COMPILE__
         S.nodes++;
 #endif
@@ -565,7 +624,7 @@ struct QdLevel {
                     S.pre2[i] = acc;
                 }
             }
-            QdLevel<N, L + 1, KC>::run(S, pn);
+            QdLevel<N, L + 1, KC, PACKED>::run(S, pn);
             const bool can_lo = lo >= kmin, can_hi = hi <= 3;
             if (!((int)can_lo | (int)can_hi)) return;
             const bool take_lo = (bool)((int)can_lo & ((int)!can_hi | (int)((kstar - (double)lo) <= ((double)hi - kstar))));
@@ -576,9 +635,9 @@ struct QdLevel {
     }
 };
 
-template <int N, int KC>
-struct QdLevel<N, N, KC> {
-    static QD_HD void run(QdSearch<N, KC>& S, double) {
+template <int N, int KC, bool PACKED>
+struct QdLevel<N, N, KC, PACKED> {
+    static QD_HD void run(QdSearch<N, KC, PACKED>& S, double) {
 #ifndef __HIP_DEVICE_COMPILE__
         S.leaves++;
 #endif
@@ -607,12 +666,12 @@ struct QdLevel<N, N, KC> {
 
 // Returns the number of valid candidates found (<= KC).  With sort_output the list is in the
 // reference order (increasing (E, idx)); otherwise it is the same SET in search order.
-template <int N, int KC = QD_K>
+template <int N, int KC = QD_K, bool PACKED = (QD_SEARCH_PACKED != 0)>
 QD_HD int qd_candidates(const double* par, const double* vpp, const double* ncont,
                         double* e, int es, uint16_t* id, int is, int32_t* fl_out, bool sort_output,
                         unsigned long long* stats = nullptr) {
     const QdLayout L = qd_layout(N);
-    QdSearch<N, KC> S;
+    QdSearch<N, KC, PACKED> S;
     S.A = par + L.cdd_inv; S.lda = N + 1; S.U = par + L.ufac; S.uinv = par + L.uinv;
     bool shifted = false;
 #pragma unroll
@@ -649,7 +708,7 @@ QD_HD int qd_candidates(const double* par, const double* vpp, const double* ncon
     S.count = 0; S.lim = INFINITY; S.idx = 0;
     S.nodes = S.leaves = S.inserts = S.shifts = 0;
 #if !(defined(QD_CAND_ABLATE) && QD_CAND_ABLATE == 2)
-    QdLevel<N, 0, KC>::run(S, 0.0);                            // (ablate 2: diagnostic, front end only)
+    QdLevel<N, 0, KC, PACKED>::run(S, 0.0);                            // (ablate 2: diagnostic, front end only)
 #endif
     if (sort_output) qd_search_sort(S);
 #ifndef __HIP_DEVICE_COMPILE__

@@ -50,7 +50,13 @@ QD_HD void qd_fl_unpack(uint32_t w, int& mn, int& mx) { mn = (int)(w & 0xFFFFu);
 // 0..KC-1 are then written from states 0..KC-1 in a straight line, the group maxima tracked on the way with strict > in
 // ascending slot order (the tie rule of the rescan), and the loop goes on from state KC without the validity test up to
 // nSfront.  Without FILL, or with nSfront < KC, the general loop runs: same slots, ids, energies, eout and count.
-template <int KC, bool FILL>
+// RESCAN8: a replacing step reads the eight slots of its group before the compare chain starts (on the device one LDS round
+// trip; the barrier keeps the compares behind the loads); without it the compiler reads them in two batches of four.  Same
+// comparisons in the same order.  scripts/ab_build.sh NAME -DQD_TILE_RESCAN8=0 builds the earlier form.
+#ifndef QD_TILE_RESCAN8
+#define QD_TILE_RESCAN8 1
+#endif
+template <int KC, bool FILL, bool RESCAN8 = (QD_TILE_RESCAN8 != 0)>
 QD_HD void qd_tile_select(int nS, int nSfront, int scap, const uint32_t* scode, const double* sD, const double* sa, const double* sb,
                           double xs, double ys, uint32_t blo, uint32_t bhi, double* ke, uint16_t* kid,
                           double& maxE_out, int& maxS_out, int& maxG_out, int& count_out, double& eout_out) {
@@ -105,8 +111,19 @@ QD_HD void qd_tile_select(int nS, int nSfront, int scap, const uint32_t* scode, 
             ke[maxS * 64] = en; kid[maxS * 64] = (uint16_t)s;
             {
                 double me = -INFINITY; int ms = maxG * 8;
+                if constexpr (RESCAN8) {
+                    double v[8];
 #pragma unroll
-                for (int t = 0; t < 8; ++t) { const double v = ke[(maxG * 8 + t) * 64]; if (v > me) { me = v; ms = maxG * 8 + t; } }
+                    for (int t = 0; t < 8; ++t) v[t] = ke[(maxG * 8 + t) * 64];
+#if defined(__HIP_DEVICE_COMPILE__)
+                    __builtin_amdgcn_sched_barrier(0);
+#endif
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) if (v[t] > me) { me = v[t]; ms = maxG * 8 + t; }
+                } else {
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) { const double v = ke[(maxG * 8 + t) * 64]; if (v > me) { me = v; ms = maxG * 8 + t; } }
+                }
 #pragma unroll
                 for (int g = 0; g < NG; ++g) if (g == maxG) { gE[g] = me; gS[g] = ms; }
             }
