@@ -675,6 +675,42 @@ int qd_eval_points_thermal(qd_handle* h, const int32_t* group_env_host, const in
                            const double* vg_dev, const double* vb_dev, const double* kT_host,
                            double* signal_dst, double* occ_dst, const qd_thermal_opts* opts, void* stream);
 
+/* CHARGE RESPONSE per point: qd_eval_points_response is qd_eval_points_thermal plus the derivatives of the thermal
+ * occupations and of the signal at the point (csrc/qd_response.h, an epilogue of the thermal kernel in a kernel of its own).
+ *   Model.         The H, kT and populations of qd_eval_points_thermal.  The kept list is held FIXED: the response is the
+ *                  derivative of the TRUNCATED K-state model at this point, not of the infinite system (see Truncation above);
+ *                  across a voltage where the kept set changes it is the derivative of the model on this side.
+ *   chi_dst        [points][N][2N-1].  Columns 0..N-1: d<n_i>/d(eps_k) for H + eps_k n_k; symmetric, negative semidefinite,
+ *                  -cov(n_i, n_k) / kT exactly when every tc is zero.  Columns N..2N-2: d<n_i>/d(ln tc_d); a pair with
+ *                  tc_d == 0 gives an exact zero column.  A point with one valid state gives zeros.
+ *   jac_dst        [points][N][2N]: d<n_i>/dv_j over v = (vg[0..N], vb[0..N-2]) = sum_k chi[i][k] Lam[k][j] +
+ *                  sum_d chi[i][N+d] Gam[d][j], Lam = -2 cdd_inv[:N,:N] cgd[:N], Gam[d][j] = -alpha_d d(vb_eff_d)/dv_j.
+ *   dsignal_dst    [points][2N]: dS/dv_j = S'(c0) dc0/dv_j with the c0 and S of qd_eval_points_thermal,
+ *                  dc0/dv_j = 2 sum_i A[N][i] (jac[i][j] - cgd[i][j]) - 2 A[N][N] cgd[N][j].  Ns = rint(v''_s) is piecewise
+ *                  constant and its jumps are not differentiated; the peak width gamma is taken as constant.
+ *   Accuracy.      tests/response_helpers.py: chi within 8 n_max^2 (1e-12 hs + 1e-13 hn) min(1/kT, 1/g)^2 + 1e-12 n_max^2 / kT.
+ * Any of the three may be NULL; with all three NULL (or opts NULL) the call launches exactly what qd_eval_points_thermal
+ * launches, with the same bits.  signal_dst, occ_dst, var_dst and ztail_dst have the bits of qd_eval_points_thermal in
+ * every case.  Open and closed regime, the slot loop, checks and scratch of the siblings.
+ * QD_ERR_ARG and QD_ERR_STATE: what qd_eval_points_thermal refuses, and, when a response destination is given, QD_ERR_STATE
+ * when a named env carries the voltage-dependent capacitance model (its per-point scale factors make Lam depend on v; that chain rule is not built).
+ * Not built: the response on grids (the per-component core of qd_thermal_blocks.h gets this epilogue next), on lines, scans,
+ * probes and in qd_step, and a separate T = 0 path (the ground-state response is the kT -> 0 limit of this one). */
+typedef struct qd_response_opts {
+    int32_t struct_size;            /* = sizeof(qd_response_opts) */
+    int32_t reserved;               /* 0 */
+    const double*  gamma_host;      /* as qd_eval_points' gamma */
+    const int32_t* n_charge_host;   /* NULL: open regime; else the closed regime, as qd_eval_points_closed */
+    double* var_dst;                /* [points][N], device, may be NULL */
+    double* ztail_dst;              /* [points], device, may be NULL */
+    double* chi_dst;                /* [points][N][2N-1], device, may be NULL */
+    double* jac_dst;                /* [points][N][2N], device, may be NULL */
+    double* dsignal_dst;            /* [points][2N], device, may be NULL */
+} qd_response_opts;
+int qd_eval_points_response(qd_handle* h, const int32_t* group_env_host, const int64_t* group_start_host, int ng,
+                            const double* vg_dev, const double* vb_dev, const double* kT_host,
+                            double* signal_dst, double* occ_dst, const qd_response_opts* opts, void* stream);
+
 /* FINITE TEMPERATURE on a grid: qd_scan_grid_thermal is qd_scan_grid / qd_scan_grid_closed with the thermal state of
  * qd_eval_points_thermal at every point in place of the ground state -- the thermally broadened charge-stability diagram.
  * It takes the arguments of qd_scan_grid and

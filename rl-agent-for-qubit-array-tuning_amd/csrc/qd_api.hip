@@ -20,6 +20,7 @@
 #include "qd_levels.h"
 #include "qd_thermal.h"
 #include "qd_thermal_blocks.h"
+#include "qd_response.h"
 #include "qd_levels_blocks.h"
 #include "qd_scratch.h"
 
@@ -170,6 +171,10 @@ struct qd_handle {
     QdDev<QdGridAxes> grid_axes;
     // the closed regime (qd_eval_points_closed): the total charge of every slot in flight, allocated by the first call
     QdDev<int32_t> closed_q;
+    // per env (B bytes, calloc in qd_create, freed in qd_destroy): the parameter block of its last qd_load_episodes switches the
+    // voltage-dependent capacitance model on (scal[4]); qd_eval_points_response refuses such envs on the host.  qd_load_episodes
+    // is the only path that uploads parameter blocks, so the note cannot go stale.
+    unsigned char* vc_on;
     mutable char err[512];                  // (the launchers take the handle const and still report through it)
 };
 
@@ -306,6 +311,8 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
     if (!h) return QD_ERR_NOMEM;
     h->cfg = *cfg; h->device = device;
     h->N = cfg->n_dot; h->R = cfg->resolution; h->B = cfg->batch;
+    h->vc_on = (unsigned char*)calloc((size_t)cfg->batch, 1);
+    if (!h->vc_on) { delete h; return QD_ERR_NOMEM; }
     h->C = h->N - 1; h->P = h->R * h->R; h->L = qd_layout(h->N);
     // K kept states; the candidate stage runs the smallest kept-set size >= K and hands over its first K
     h->kept = cfg->num_charge_states > 0 ? cfg->num_charge_states : QD_K;
@@ -433,6 +440,7 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
 extern "C" int qd_destroy(qd_handle* h) {
     if (!h) return QD_ERR_ARG;
     QdDeviceGuard guard_(h->device);
+    free(h->vc_on);
     delete h;
     return QD_OK;
 }
@@ -467,6 +475,7 @@ extern "C" int qd_load_episodes(qd_handle* h, const int32_t* env_ids, int n, con
     double* sp = h->stage.slot[slot].p;
     double* ss = sp + (size_t)n * prow;
     memcpy(sp, params, sizeof(double) * (size_t)n * prow);
+    for (int k = 0; k < n; ++k) h->vc_on[(size_t)env_ids[k]] = params[(size_t)k * prow + L.scal + 4] != 0.0 ? 1 : 0;
     memcpy(ss, state, sizeof(double) * (size_t)n * srow);
     // the state rows uploaded are the first `pre` doubles, or the whole row with fresh Kalman priors
     size_t width = pre;
@@ -1299,7 +1308,8 @@ static int qd_points_slots(const qd_handle* h) { return h->chunk < QD_POINTS_MAX
 static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
                          const double* vb, const double* gamma, const int32_t* n_charge, double* signal_dst, double* occ_dst,
                          int32_t* states_dst, void* stream, int n_levels = 0, double* levels_dst = nullptr, double* hnorm_dst = nullptr,
-                         const double* kT = nullptr, double* var_dst = nullptr, double* ztail_dst = nullptr) {
+                         const double* kT = nullptr, double* var_dst = nullptr, double* ztail_dst = nullptr, double* chi_dst = nullptr,
+                         double* jac_dst = nullptr, double* dsignal_dst = nullptr) {
     static_assert(QD_POINTS_MAX_SLOTS == QD_POINTS_SLOTS, "qdsim.h states the bound");
     if (ng < 0) return qd_failf(h, QD_ERR_ARG, "%s: ng < 0", who);
     if (!group_env || !group_start) return qd_failf(h, QD_ERR_ARG, "%s: group_env_host or group_start_host is NULL", who);
@@ -1364,12 +1374,23 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
         if (kT) {
             // the thermal state instead of the ground state: c0 and <n> into the slots' zraw and occ, then the unchanged write
             const dim3 tgrid((unsigned)(CP < 4096 ? CP : 4096), n);
-            QD_DISPATCH_N(h->N, qd_k_thermal<NN><<<tgrid, dim3(64), 0, s>>>(T, TK, (int)CP, h->kept, qb.params, ln.recs.p, qb.zraw, qb.occ,
-                                                                           var_dst, ztail_dst));
+            if (chi_dst || jac_dst || dsignal_dst) {
+                // qd_eval_points_response: the thermal kernel with the response epilogue (qd_response.h); dc0/dv into dsignal_dst
+                QD_DISPATCH_N(h->N, qd_k_thermal_response<NN><<<tgrid, dim3(64), 0, s>>>(T, TK, (int)CP, h->kept, qb.params, ln.recs.p,
+                                                                                        qb.zraw, qb.occ, var_dst, ztail_dst, chi_dst,
+                                                                                        jac_dst, dsignal_dst));
+            } else {
+                QD_DISPATCH_N(h->N, qd_k_thermal<NN><<<tgrid, dim3(64), 0, s>>>(T, TK, (int)CP, h->kept, qb.params, ln.recs.p, qb.zraw,
+                                                                               qb.occ, var_dst, ztail_dst));
+            }
             QD_HIP(hipGetLastError());
             if (signal_dst || occ_dst) {
                 QD_DISPATCH_N(h->N, qd_k_points_write<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, qb.params, qb.zraw, qb.occ,
                                                                                                signal_dst, occ_dst));
+                QD_HIP(hipGetLastError());
+            }
+            if (dsignal_dst) {
+                QD_DISPATCH_N(h->N, qd_k_points_dsignal<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, qb.params, qb.zraw, dsignal_dst));
                 QD_HIP(hipGetLastError());
             }
             n = 0;
@@ -1458,6 +1479,28 @@ extern "C" int qd_eval_points_thermal(qd_handle* h, const int32_t* group_env, co
     return qd_points_run(h, "qd_eval_points_thermal", group_env, group_start, ng, vg, vb, opts ? opts->gamma_host : nullptr,
                          opts ? opts->n_charge_host : nullptr, signal_dst, occ_dst, nullptr, stream, 0, nullptr, nullptr, kT,
                          opts ? opts->var_dst : nullptr, opts ? opts->ztail_dst : nullptr);
+}
+
+extern "C" int qd_eval_points_response(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
+                                       const double* vb, const double* kT, double* signal_dst, double* occ_dst,
+                                       const qd_response_opts* opts, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    if (!kT) return qd_fail(h, QD_ERR_ARG, "qd_eval_points_response: kT_host is NULL");
+    for (int g = 0; g < ng; ++g)
+        if (!(kT[g] > 0.0) || !(kT[g] < INFINITY))
+            return qd_fail(h, QD_ERR_ARG, "qd_eval_points_response: kT must be finite and > 0");
+    if (opts && opts->struct_size != (int32_t)sizeof(qd_response_opts))
+        return qd_fail(h, QD_ERR_ARG, "qd_eval_points_response: opts->struct_size is not sizeof(qd_response_opts)");
+    // (with no response destination the call is qd_eval_points_thermal, which takes such envs)
+    if (group_env && opts && (opts->chi_dst || opts->jac_dst || opts->dsignal_dst))
+        for (int g = 0; g < ng; ++g)
+            if (group_env[g] >= 0 && group_env[g] < h->B && h->vc_on[(size_t)group_env[g]])
+                return qd_fail(h, QD_ERR_STATE, "qd_eval_points_response: the env carries the voltage-dependent capacitance model, whose "
+                                                "per-point scale factors make d F / d v depend on v; that chain rule is not built");
+    return qd_points_run(h, "qd_eval_points_response", group_env, group_start, ng, vg, vb, opts ? opts->gamma_host : nullptr,
+                         opts ? opts->n_charge_host : nullptr, signal_dst, occ_dst, nullptr, stream, 0, nullptr, nullptr, kT,
+                         opts ? opts->var_dst : nullptr, opts ? opts->ztail_dst : nullptr, opts ? opts->chi_dst : nullptr,
+                         opts ? opts->jac_dst : nullptr, opts ? opts->dsignal_dst : nullptr);
 }
 
 // numpy 'linear' percentile ranks of n values, as qd_k_percentile takes them

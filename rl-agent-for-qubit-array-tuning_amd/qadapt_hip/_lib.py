@@ -32,7 +32,7 @@ EXPORTS = [
     "qd_time_ground_kernel", "qd_time_candidates_kernel", "qd_time_kernels", "qd_timed_kernel_name", "qd_chunk_envs",
     "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex", "qd_scan_affine",
     "qd_scan_grid", "qd_eval_points_closed", "qd_scan_grid_closed", "qd_eval_points_ex",
-    "qd_eval_points_thermal", "qd_scan_grid_thermal", "qd_scan_grid_levels",
+    "qd_eval_points_thermal", "qd_scan_grid_thermal", "qd_scan_grid_levels", "qd_eval_points_response",
 ]
 # exported too, kept apart: names with a digit, which a scan of qdsim.h for `qd_[a-z_]+(` does not find
 EXPORTS_WITH_DIGITS = ["qd_scan2d", "qd_scan1d"]
@@ -110,6 +110,12 @@ class QdThermalOpts(ctypes.Structure):
         ("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("gamma_host", ctypes.POINTER(ctypes.c_double)),
         ("n_charge_host", ctypes.POINTER(ctypes.c_int32)), ("var_dst", ctypes.c_void_p), ("ztail_dst", ctypes.c_void_p),
     ]
+
+
+class QdResponseOpts(ctypes.Structure):
+    """qd_response_opts of include/qdsim.h: the fields of qd_thermal_opts for a qd_eval_points_response call, and the device
+    destinations of chi [points][N][2N-1], the jacobian [points][N][2N] and dS/dv [points][2N]."""
+    _fields_ = list(QdThermalOpts._fields_) + [("chi_dst", ctypes.c_void_p), ("jac_dst", ctypes.c_void_p), ("dsignal_dst", ctypes.c_void_p)]
 
 
 class QdGridThermalOpts(ctypes.Structure):
@@ -226,6 +232,9 @@ def lib():
     L.qd_eval_points_thermal.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, dp, dp, ctypes.POINTER(ctypes.c_double),
                                          dp, dp, ctypes.POINTER(QdThermalOpts), vp]
     L.qd_eval_points_thermal.restype = ctypes.c_int
+    L.qd_eval_points_response.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, dp, dp, ctypes.POINTER(ctypes.c_double),
+                                          dp, dp, ctypes.POINTER(QdResponseOpts), vp]
+    L.qd_eval_points_response.restype = ctypes.c_int
     L.qd_scan_grid_thermal.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, dp, dp, fp, dp,
                                        ctypes.POINTER(QdScanGridOpts), ctypes.POINTER(QdGridThermalOpts), vp]
     L.qd_scan_grid_thermal.restype = ctypes.c_int

@@ -144,6 +144,44 @@ class ModelFacade:
         """thermal_state_open on the closed list: the kept states of the total-charge sector `n_charge`; every n sums to it."""
         return self._thermal(vg, vb, T, n_charge=n_charge)
 
+    def _response(self, vg, vb, T, n_charge=None):
+        if vb is None:
+            raise NotImplementedError("the charge response without barrier voltages: as charge_sensor_open, pass vb")
+        N = self.n_dot
+        vg, vb = np.asarray(vg, np.float64), np.asarray(vb, np.float64)
+        if vg.shape[-1:] != (N + 1,) or vb.shape[-1:] != (N - 1,) or vg.shape[:-1] != vb.shape[:-1]:
+            raise ValueError(f"vg must be (..., {N + 1}) and vb (..., {N - 1}) with equal leading shapes; "
+                             f"got {vg.shape} and {vb.shape}")
+        if T is None:
+            T = self.T
+            if T is None or not np.isfinite(T):
+                raise ValueError("T=None needs the device's own sampled temperature, and this device was loaded from raw "
+                                 "parameter blocks, which carry none; pass T")
+        kT = 8.617333262145e-5 * float(T)
+        lead = vg.shape[:-1]
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        kw = {} if n_charge is None else {"n_charge": n_charge}
+        out = self._b.eval_points([0], vg.reshape(1, -1, N + 1), vb.reshape(1, -1, N - 1), gamma=gamma,
+                                  outputs=("signal", "occupations"), kT=kT, response=True, **kw)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        return (host(out["chi"]).astype(np.float64).reshape(lead + (N, 2 * N - 1)),
+                host(out["jacobian"]).astype(np.float64).reshape(lead + (N, 2 * N)),
+                host(out["dsignal"]).astype(np.float64).reshape(lead + (2 * N,)))
+
+    def charge_response_open(self, vg, vb=None, T=None):
+        """(chi (..., N, 2N-1), jacobian (..., N, 2N), dsignal (..., 2N)) float64 of the thermal state of `thermal_state_open`
+        at the point: chi[..., i, k] = d<n_i>/d(eps_k) for H + eps_k n_k (k < N) and d<n_i>/d(ln tc_d) (k = N + d),
+        jacobian[..., i, j] = d<n_i>/dv_j over v = (vg, vb) -- the local slopes the capacitance virtualisation estimates --
+        and dsignal[..., j] = dS/dv_j, the lock-in transconductance.  The kept list is held fixed (the derivative of the
+        truncated K-state model), the jumps of the sensor's rint are not differentiated and the peak width is a constant.
+        `T` as in `thermal_state_open`."""
+        return self._response(vg, vb, T)
+
+    def charge_response_closed(self, vg, n_charge, T=None, vb=None):
+        """charge_response_open on the closed list of the total-charge sector `n_charge`: every column of chi and of the
+        jacobian sums to zero over the dots."""
+        return self._response(vg, vb, T, n_charge=n_charge)
+
     def _gate_axis(self, gate):
         """(axis, frame) of one gate of the composer's grammar, as the backend's scans take them"""
         N = self.n_dot

@@ -840,7 +840,7 @@ class VecQuantumDeviceEnv:
 
     # ------------------------------------------------------------------ point evaluation
     def eval_points(self, env_ids, vg, vb, gamma=None, outputs=("signal", "occupations"), n_charge=None, states=False, *, kT=None,
-                    levels=0):
+                    response=False, levels=0):
         """The reference model's point function (qd_eval_points): `charge_sensor_open(vg, vb)` and `ground_state_open(vg, vb)`
         (TunnelCoupledChargeSensed.py:312-380) at arbitrary PHYSICAL voltages, on the devices of the listed envs.  Nothing of
         the episodes changes and no noise stage runs; an env may be named many times.
@@ -874,10 +874,22 @@ class VecQuantumDeviceEnv:
                     this kT.  Defined at exact degeneracies (the equal mixture): no point needs the rel_gap exemption.  With
                     n_charge: the closed list.  Not together with levels or states=True: ask for those in a second call.
                     (keyword only, as `levels` is from here on)
+          response  True (with kT; qd_eval_points_response) adds the derivatives of that thermal state at the point:
+                    "chi" (n, m, N, 2N-1): columns 0..N-1 d<n_i>/d(eps_k) for H + eps_k n_k (symmetric, negative
+                    semidefinite, -cov / kT when every tc is zero), columns N..2N-2 d<n_i>/d(ln tc_d);  "jacobian"
+                    (n, m, N, 2N): d<n_i>/dv_j over v = (vg, vb);  "dsignal" (n, m, 2N): dS/dv_j.  The kept list is held
+                    FIXED: this is the derivative of the truncated K-state model at the point (see `levels`), exact on
+                    the transition lines, where it is the finite peak a measurement shows.  Ns = rint(v''_s) is piecewise
+                    constant and its jumps are not differentiated; gamma is taken as constant.  The other outputs keep
+                    the bits of the call without it.  Envs with the voltage-dependent capacitance model are refused
         Returns device tensors {"signal": (n, m) float64, "occupations": (n, m, N) float64[, "states": (n, m, K, N) int32]
-        [, "levels": (n, m, L) float64, "hnorm": (n, m) float64][, "variance": (n, m, N), "ztail": (n, m) float64]}; for list
-        input, lists of n tensors (m_i,), (m_i, N), (m_i, K, N), (m_i, L), (m_i,), (m_i, N) and (m_i,)."""
+        [, "levels": (n, m, L) float64, "hnorm": (n, m) float64][, "variance": (n, m, N), "ztail": (n, m) float64]
+        [, "chi", "jacobian", "dsignal"]}; for list input, lists of n tensors (m_i,), (m_i, N), (m_i, K, N), (m_i, L), (m_i,),
+        (m_i, N), (m_i,), (m_i, N, 2N-1), (m_i, N, 2N) and (m_i, 2N)."""
         outputs = tuple(outputs)
+        if response and kT is None:
+            raise ValueError("response=True needs kT: the response is that of the thermal state (at T = 0 it is round-off on the "
+                             "transition lines and zero elsewhere); pass the temperature the derivative is wanted at")
         levels = int(levels)
         if not 0 <= levels <= _lib.QD_LEVELS_MAX:
             raise ValueError(f"levels must be in 0..{_lib.QD_LEVELS_MAX}, got {levels}")
@@ -944,7 +956,28 @@ class VecQuantumDeviceEnv:
         hn = torch.empty((total,), dtype=torch.float64, device=self.device) if levels else None
         var = torch.empty((total, N), dtype=torch.float64, device=self.device) if "variance" in outputs else None
         zt = torch.empty((total,), dtype=torch.float64, device=self.device) if "ztail" in outputs else None
-        if kth is not None:
+        chi = jac = dsig = None
+        if response:
+            chi = torch.empty((total, N, 2 * N - 1), dtype=torch.float64, device=self.device)
+            jac = torch.empty((total, N, 2 * N), dtype=torch.float64, device=self.device)
+            dsig = torch.empty((total, 2 * N), dtype=torch.float64, device=self.device)
+        if kth is not None and response:
+            opts = _lib.QdResponseOpts(struct_size=ctypes.sizeof(_lib.QdResponseOpts))
+            if gam is not None:
+                opts.gamma_host = gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+            if qh is not None:
+                opts.n_charge_host = qh.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            opts.var_dst = None if var is None else var.data_ptr()
+            opts.ztail_dst = None if zt is None else zt.data_ptr()
+            opts.chi_dst, opts.jac_dst, opts.dsignal_dst = chi.data_ptr(), jac.data_ptr(), dsig.data_ptr()
+            rc = 0 if total == 0 else self._lib.qd_eval_points_response(
+                self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
+                ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
+                kth.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                None if signal is None else ctypes.c_void_p(signal.data_ptr()),
+                None if occ is None else ctypes.c_void_p(occ.data_ptr()), ctypes.byref(opts), self._stream())
+            _lib.check(self._h, rc, "qd_eval_points_response")
+        elif kth is not None:
             opts = _lib.QdThermalOpts(struct_size=ctypes.sizeof(_lib.QdThermalOpts))
             if gam is not None:
                 opts.gamma_host = gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
@@ -1006,6 +1039,10 @@ class VecQuantumDeviceEnv:
             out["variance"] = [var[start[i]:start[i + 1]] for i in range(n)] if ragged else var.reshape(n, m, N)
         if zt is not None:
             out["ztail"] = [zt[start[i]:start[i + 1]] for i in range(n)] if ragged else zt.reshape(n, m)
+        if response:
+            out["chi"] = [chi[start[i]:start[i + 1]] for i in range(n)] if ragged else chi.reshape(n, m, N, 2 * N - 1)
+            out["jacobian"] = [jac[start[i]:start[i + 1]] for i in range(n)] if ragged else jac.reshape(n, m, N, 2 * N)
+            out["dsignal"] = [dsig[start[i]:start[i + 1]] for i in range(n)] if ragged else dsig.reshape(n, m, 2 * N)
         return out
 
     # ------------------------------------------------------------------ reset
