@@ -694,8 +694,8 @@ int qd_eval_points_thermal(qd_handle* h, const int32_t* group_env_host, const in
  * every case.  Open and closed regime, the slot loop, checks and scratch of the siblings.
  * QD_ERR_ARG and QD_ERR_STATE: what qd_eval_points_thermal refuses, and, when a response destination is given, QD_ERR_STATE
  * when a named env carries the voltage-dependent capacitance model (its per-point scale factors make Lam depend on v; that chain rule is not built).
- * Not built: the response on grids (the per-component core of qd_thermal_blocks.h gets this epilogue next), on lines, scans,
- * probes and in qd_step, and a separate T = 0 path (the ground-state response is the kT -> 0 limit of this one). */
+ * Grids are qd_scan_grid_response below.  Not built: the response on lines, scans, probes and in qd_step, and a separate
+ * T = 0 path (the ground-state response is the kT -> 0 limit of this one). */
 typedef struct qd_response_opts {
     int32_t struct_size;            /* = sizeof(qd_response_opts) */
     int32_t reserved;               /* 0 */
@@ -748,6 +748,48 @@ int qd_scan_grid_thermal(qd_handle* h, const int32_t* env_of_query_dev, int nq, 
                          const double* range_dev, const double* gate_v_dev, const double* barrier_v_dev,
                          const double* sensor_v_dev, const double* kT_dev, double* raw_dst, float* image_dst,
                          double* plohi_dst, const qd_scan_grid_opts* opts, const qd_grid_thermal_opts* topts, void* stream);
+
+/* CHARGE RESPONSE on a grid: qd_scan_grid_response is qd_scan_grid_thermal plus, at every point, the derivatives of
+ * qd_eval_points_response -- the lock-in charge-stability diagram dS/dV along the sweep axis, and the slopes d<n_i>/dV_j along a
+ * transition line.  It takes the arguments of qd_scan_grid_thermal, with ropts in place of topts:
+ *   n_charge_dev, var_dst, ztail_dst   as in qd_grid_thermal_opts
+ *   chi_dst        [nq][ny][nx][N][2N-1], jac_dst [nq][ny][nx][N][2N], dsignal_dst [nq][ny][nx][2N]: chi, the jacobian and dS/dv
+ *                  as qd_eval_points_response defines them, over the PHYSICAL voltages v = (vg[0..N], vb[0..N-2]), in either frame
+ *   docc_axes_dst  [nq][ny][nx][N][2] = jacobian . (u_x, u_y);  dsignal_axes_dst [nq][ny][nx][2] = dsignal . (u_x, u_y):
+ *                  the derivatives along the two axes of the grid, per unit of the axis scalars sx, sy (not per pixel).
+ *                  u = dv/ds is the physical direction of one step of the scalar: the direction vector itself in the physical
+ *                  frame; in the virtual frame u[:G] = vgm u_dir[:G] with the slot's virtual gate matrix (the query's vgm_dev
+ *                  if given, else the env's) and u[G:] = dir[G:].  All sums run over j = 0 .. 2N-1 in index order with fma.
+ * DEVICE float64, any subset may be NULL.  With all five NULL (or ropts NULL) the call launches exactly what
+ * qd_scan_grid_thermal launches.  raw, image, plohi, opts->occ_dst, var_dst and ztail_dst have the bits of
+ * qd_scan_grid_thermal under the same arguments in every case.  The slope S'(c0) is taken at the c0 of the thermal state with
+ * the slot's constant peak width (opts->gamma_dev if given); QD_NOISE_SENSOR is allowed in the open regime as in
+ * qd_scan_grid_thermal, and the response is that of the NOISELESS expression: its bits do not depend on noise_flags.
+ * The call runs qd_scan_grid_thermal's launches with the thermal kernel exchanged for the one of csrc/qd_response_blocks.h.  Open
+ * regime: the epilogue runs inside the hop components that the per-component thermal solver found (G = V^T X V and D o G are
+ * block diagonal over them; only Z and <X> are global); it agrees with qd_eval_points_response at the same voltages within the
+ * sum of both tolerances, not bit for bit.  Closed regime: one component, the whole-block solver and epilogue of
+ * qd_eval_points_response, and in the physical frame chi, jac and dsignal equal that call at the grid's voltages bit for bit.
+ * QD_ERR_ARG and QD_ERR_STATE: what qd_scan_grid_thermal refuses (QD_NOISE_LATCH included); ropts->struct_size !=
+ * sizeof(qd_grid_response_opts); and, when a response destination is given, QD_ERR_STATE for a live query whose env carries the
+ * voltage-dependent capacitance model (the call reads env_of_query_dev back for this check).  Not built: the response in
+ * qd_scan1d, qd_scan2d, qd_scan_affine, probes and qd_step, and latched thermal points. */
+typedef struct qd_grid_response_opts {
+    int32_t struct_size;            /* = sizeof(qd_grid_response_opts) */
+    int32_t reserved;               /* 0 */
+    const int32_t* n_charge_dev;    /* NULL: open regime; else [nq], the closed regime, as qd_scan_grid_closed */
+    double* var_dst;                /* [nq][ny][nx][N], device, may be NULL */
+    double* ztail_dst;              /* [nq][ny][nx], device, may be NULL */
+    double* chi_dst;                /* [nq][ny][nx][N][2N-1], device, may be NULL */
+    double* jac_dst;                /* [nq][ny][nx][N][2N], device, may be NULL */
+    double* dsignal_dst;            /* [nq][ny][nx][2N], device, may be NULL */
+    double* docc_axes_dst;          /* [nq][ny][nx][N][2], device, may be NULL */
+    double* dsignal_axes_dst;       /* [nq][ny][nx][2], device, may be NULL */
+} qd_grid_response_opts;
+int qd_scan_grid_response(qd_handle* h, const int32_t* env_of_query_dev, int nq, int nx, int ny, const double* dir_dev,
+                          const double* range_dev, const double* gate_v_dev, const double* barrier_v_dev,
+                          const double* sensor_v_dev, const double* kT_dev, double* raw_dst, float* image_dst,
+                          double* plohi_dst, const qd_scan_grid_opts* opts, const qd_grid_response_opts* ropts, void* stream);
 
 /* ENERGY LEVELS on a grid: qd_scan_grid_levels is qd_scan_grid / qd_scan_grid_closed that also hands out the lowest eigenvalues
  * and ||H||_inf of qd_eval_points_ex at every point -- the gap map levels[1] - levels[0] over, say, detuning x barrier, and

@@ -20,6 +20,7 @@
 #include "qd_levels.h"
 #include "qd_thermal.h"
 #include "qd_thermal_blocks.h"
+#include "qd_response_grid.h"
 #include "qd_response.h"
 #include "qd_levels_blocks.h"
 #include "qd_scratch.h"
@@ -1169,16 +1170,29 @@ static int qd_check_device_range(const qd_handle* h, const char* who, const T* d
 #define QD_LVG_WHOLE(n_charge) ((n_charge) != nullptr)
 #endif
 
+// Which core and epilogue the response kernel of a grid runs: qd_thermal_solve and qd_response_solve on the whole block in the
+// closed regime (one component per list), the per-component pair of qd_thermal_blocks.h and qd_response_blocks.h in the open
+// regime.  MEASURED ahead of the whole-block pair there by more than the run-to-run spread are 4 and 8 dots at K = 32 (2.93 and
+// 1.65 times the rate of the whole call, spread 0.5 %; both the core and the epilogue are exchanged, so the figure includes what
+// the per-component thermal core gains: DESIGN 7); every other N and K is unmeasured.  Under the measurement-only build macro
+// QD_RSG_FORCE_WHOLE (scripts/response_grid_rate.py, route e) every grid runs the whole-block core and epilogue.
+#ifdef QD_RSG_FORCE_WHOLE
+#define QD_RSG_WHOLE(n_charge) true
+#else
+#define QD_RSG_WHOLE(n_charge) ((n_charge) != nullptr)
+#endif
+
 // qd_scan_grid (n_charge null) and qd_scan_grid_closed on the runner of the lines: the closed regime replaces the redo pass of
 // the open search by qd_k_closed at the queries' total charges and leaves every other launch as it is.  kT ([nq], device):
 // qd_scan_grid_thermal, the thermal kernel of qd_thermal_blocks.h in place of the ground-state stage, once, on the lists as the
 // search left them; the slots always carry occupations then.  n_levels > 0: qd_scan_grid_levels, the levels kernel of
 // qd_levels_blocks.h behind the search and before the ground-state stage, which reads the records and writes the caller's rows.
+// rd (with kT): qd_scan_grid_response, the thermal kernel with the response epilogue of qd_response_blocks.h in its place.
 static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
                        const double* range, const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst,
                        float* image_dst, double* plohi_dst, const qd_scan_grid_opts* opts, const int32_t* n_charge, void* stream,
                        const double* kT = nullptr, double* var_dst = nullptr, double* ztail_dst = nullptr, int n_levels = 0,
-                       double* levels_dst = nullptr, double* hnorm_dst = nullptr) {
+                       double* levels_dst = nullptr, double* hnorm_dst = nullptr, const QdGridResponseDst* rd = nullptr) {
     static_assert(QD_GRID_MAX_SLOTS == QD_GRID_SLOTS, "qdsim.h states the bound");
     static_assert(QD_THG_BLOCKS <= QD_GRID_MAX_SLOTS && QD_LVG_BLOCKS <= QD_GRID_MAX_SLOTS, "a launch dimension");
     QdQueryOpts o;
@@ -1197,6 +1211,15 @@ static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_quer
     if (kT)
         if (int rc = qd_check_device_range(h, who, kT, nq, s, "hipMemcpyAsync(kT)", "%s: kT must be finite and > 0",
                                            [](double v) { return v > 0.0 && v < INFINITY; })) return rc;
+    if (rd) {
+        // (with no response destination the call is qd_scan_grid_thermal, which takes such envs)
+        bool vc = false;
+        if (int rc = qd_check_device_range(h, who, env_of_query, nq, s, "hipMemcpyAsync(env_of_query)", "%s: env_of_query",
+                                           [&](int32_t e) { vc = vc || (e >= 0 && e < h->B && h->vc_on[(size_t)e]); return true; })) return rc;
+        if (vc)
+            return qd_failf(h, QD_ERR_STATE, "%s: the env carries the voltage-dependent capacitance model, whose per-point scale "
+                                            "factors make d F / d v depend on v; that chain rule is not built", who);
+    }
     const QdAffineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, o.vgm, o.gamma, o.frame};
     // the slot of a grid is that of a line of nx*ny points, record p = y*nx + x
     const int n = nx * ny, pc = qd_line_slots(h, n, nq);
@@ -1231,6 +1254,15 @@ static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_quer
             if (!kT) return qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND);
             // the thermal state instead of the ground state: c0 and <n> into the slots' zraw and occ, then the unchanged stages
             const dim3 tgrid((unsigned)(n < QD_THG_BLOCKS ? n : QD_THG_BLOCKS), cnt);
+            if (rd) {
+                // qd_scan_grid_response: the thermal kernel with the response epilogue (qd_response_blocks.h), whose instances are
+                // compiled in qd_response_grid.hip
+                if (!qd_launch_thermal_grid_response(h->N, QD_RSG_WHOLE(n_charge), tgrid, s, &Q, sizeof(Q), base, h->B, n, SP, h->kept, kT,
+                                                     b.params, b.state, axes, ln.recs.p, b.zraw, b.occ, var_dst, ztail_dst, *rd))
+                    return qd_fail(h, QD_ERR_ARG, "n_dot must be in 2..8");
+                QD_HIP(hipGetLastError());
+                return (int)QD_OK;
+            }
             // (a closed list is one hop component: the whole-block core, see qd_k_thermal_grid)
             if (n_charge) {
                 QD_DISPATCH_N(h->N, qd_k_thermal_grid<NN, QdThermalWs><<<tgrid, dim3(64), 0, s>>>(Q, base, h->B, n, SP, h->kept, kT, b.params,
@@ -1280,6 +1312,23 @@ extern "C" int qd_scan_grid_thermal(qd_handle* h, const int32_t* env_of_query, i
     return qd_grid_run(h, "qd_scan_grid_thermal", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
                        plohi_dst, opts, topts ? topts->n_charge_dev : nullptr, stream, kT, topts ? topts->var_dst : nullptr,
                        topts ? topts->ztail_dst : nullptr);
+}
+
+extern "C" int qd_scan_grid_response(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
+                                     const double* range, const double* gate_v, const double* barrier_v, const double* sensor_v,
+                                     const double* kT, double* raw_dst, float* image_dst, double* plohi_dst,
+                                     const qd_scan_grid_opts* opts, const qd_grid_response_opts* ropts, void* stream) {
+    if (!h) return QD_ERR_ARG;
+    if (!kT) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_response: kT_dev is NULL");
+    if (ropts && ropts->struct_size != (int32_t)sizeof(qd_grid_response_opts))
+        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_response: ropts->struct_size is not sizeof(qd_grid_response_opts)");
+    QdGridResponseDst rd{};
+    if (ropts) rd = QdGridResponseDst{ropts->chi_dst, ropts->jac_dst, ropts->dsignal_dst, ropts->docc_axes_dst, ropts->dsignal_axes_dst};
+    // (with all five null the call launches qd_k_thermal_grid itself)
+    const bool any = rd.chi || rd.jac || rd.dsignal || rd.docc_axes || rd.dsignal_axes;
+    return qd_grid_run(h, "qd_scan_grid_response", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
+                       plohi_dst, opts, ropts ? ropts->n_charge_dev : nullptr, stream, kT, ropts ? ropts->var_dst : nullptr,
+                       ropts ? ropts->ztail_dst : nullptr, 0, nullptr, nullptr, any ? &rd : nullptr);
 }
 
 extern "C" int qd_scan_grid_levels(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,

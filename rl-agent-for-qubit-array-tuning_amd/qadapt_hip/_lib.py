@@ -33,6 +33,7 @@ EXPORTS = [
     "qd_probe", "qd_probe_compose", "qd_time_select", "qd_eval_points", "qd_probe_ex", "qd_scan_affine",
     "qd_scan_grid", "qd_eval_points_closed", "qd_scan_grid_closed", "qd_eval_points_ex",
     "qd_eval_points_thermal", "qd_scan_grid_thermal", "qd_scan_grid_levels", "qd_eval_points_response",
+    "qd_scan_grid_response",
 ]
 # exported too, kept apart: names with a digit, which a scan of qdsim.h for `qd_[a-z_]+(` does not find
 EXPORTS_WITH_DIGITS = ["qd_scan2d", "qd_scan1d"]
@@ -124,6 +125,16 @@ class QdGridThermalOpts(ctypes.Structure):
     _fields_ = [
         ("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_charge_dev", ctypes.c_void_p),
         ("var_dst", ctypes.c_void_p), ("ztail_dst", ctypes.c_void_p),
+    ]
+
+
+class QdGridResponseOpts(ctypes.Structure):
+    """qd_grid_response_opts of include/qdsim.h: the fields of qd_grid_thermal_opts for a qd_scan_grid_response call, and the
+    device destinations of chi [nq][ny][nx][N][2N-1], the jacobian [..][N][2N], dS/dv [..][2N] and of the two derivatives along
+    the axes of the grid, d<n>/d(sx, sy) [..][N][2] and dS/d(sx, sy) [..][2]."""
+    _fields_ = list(QdGridThermalOpts._fields_) + [
+        ("chi_dst", ctypes.c_void_p), ("jac_dst", ctypes.c_void_p), ("dsignal_dst", ctypes.c_void_p),
+        ("docc_axes_dst", ctypes.c_void_p), ("dsignal_axes_dst", ctypes.c_void_p),
     ]
 
 
@@ -238,6 +249,9 @@ def lib():
     L.qd_scan_grid_thermal.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, dp, dp, fp, dp,
                                        ctypes.POINTER(QdScanGridOpts), ctypes.POINTER(QdGridThermalOpts), vp]
     L.qd_scan_grid_thermal.restype = ctypes.c_int
+    L.qd_scan_grid_response.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, dp, dp, fp, dp,
+                                        ctypes.POINTER(QdScanGridOpts), ctypes.POINTER(QdGridResponseOpts), vp]
+    L.qd_scan_grid_response.restype = ctypes.c_int
     L.qd_scan_grid_levels.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp, dp, fp, dp,
                                       ctypes.POINTER(QdScanGridOpts), ctypes.POINTER(QdGridLevelsOpts), vp]
     L.qd_scan_grid_levels.restype = ctypes.c_int

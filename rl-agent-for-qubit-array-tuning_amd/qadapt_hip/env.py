@@ -308,6 +308,42 @@ class ModelFacade:
         return (host(out["raw"]).astype(np.float64)[0, 0][:, None], host(out["occupations"]).astype(np.float64)[0, 0],
                 host(out["variance"]).astype(np.float64)[0, 0])
 
+    def do2d_response(self, x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points, T=None, n_charge=None):
+        """do2d_thermal with the charge response along the two axes of the grid, rendered by the backend's scan_grid_response in
+        one call: the lock-in diagram dS/dx, dS/dy and the slopes of the occupations, per unit of the swept gate values.  Gate
+        grammar, base point, frames, the one-frame rule and `T` are do2d_thermal's.  Returns (signal (y_points, x_points, 1),
+        dS/dx (y_points, x_points), dS/dy (y_points, x_points), d<n>/dx (y_points, x_points, N), d<n>/dy (y_points, x_points, N))
+        float64."""
+        N = self.n_dot
+        (x_axis, x_frame), (y_axis, y_frame) = self._gate_axis(x_gate), self._gate_axis(y_gate)
+        if x_frame != y_frame:
+            raise NotImplementedError(f"do2d_response({x_gate!r}, ..., {y_gate!r}, ...): one call has one frame, and {x_gate!r} is "
+                                      f"{x_frame} while {y_gate!r} is {y_frame}; sweep two physical gates or two virtual axes")
+        kT = self._grid_kT(T)
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        args = ([0], x_axis, y_axis, (float(x_min), float(x_max)), (float(y_min), float(y_max)), int(x_points), int(y_points),
+                np.zeros((1, N)), np.zeros((1, N - 1)))
+        out = self._b.scan_grid_response(*args, kT, 0.0, n_charge=n_charge, frame=x_frame, gamma=gamma,
+                                         response=("dsignal_axes", "docc_axes"))
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        ds, dn = host(out["dsignal_axes"]).astype(np.float64)[0], host(out["docc_axes"]).astype(np.float64)[0]
+        return (host(out["raw"]).astype(np.float64)[0][:, :, None], ds[..., 0], ds[..., 1], dn[..., 0], dn[..., 1])
+
+    def do1d_response(self, gate, min, max, points, T=None, n_charge=None):
+        """do1d_thermal with the charge response along the sweep, rendered as a one-row response grid.  Returns (signal
+        (points, 1), dS/dx (points,), dS/dy (points,), d<n>/dx (points, N), d<n>/dy (points, N)) float64; the y axis of a sweep
+        is the zero direction, so its derivatives are zero; `T` as in do2d_thermal."""
+        N = self.n_dot
+        axis, frame = self._gate_axis(gate)
+        kT = self._grid_kT(T)
+        gamma = None if self.coulomb_peak_width is None else float(self.coulomb_peak_width)
+        args = ([0], axis, np.zeros(2 * N), (float(min), float(max)), (0.0, 0.0), int(points), 1, np.zeros((1, N)), np.zeros((1, N - 1)))
+        out = self._b.scan_grid_response(*args, kT, 0.0, n_charge=n_charge, frame=frame, gamma=gamma,
+                                         response=("dsignal_axes", "docc_axes"))
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)    # noqa: E731
+        ds, dn = host(out["dsignal_axes"]).astype(np.float64)[0, 0], host(out["docc_axes"]).astype(np.float64)[0, 0]
+        return (host(out["raw"]).astype(np.float64)[0, 0][:, None], ds[..., 0], ds[..., 1], dn[..., 0], dn[..., 1])
+
     def do2d_levels(self, x_gate, x_min, x_max, x_points, y_gate, y_min, y_max, y_points, n_levels=2, n_charge=None):
         """The energy levels over do2d_open's grid (n_charge None) or do2d_closed's: the grid of energy_levels_open /
         energy_levels_closed, rendered by the backend's scan_grid_levels in one call -- levels[..., 1] - levels[..., 0] is the gap

@@ -725,6 +725,39 @@ class VecQuantumDeviceEnv:
         return self._scan_grid(env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm,
                                gamma, noise, serial, stream_base, occupations, n_charge, kT, variance, ztail)
 
+    RESPONSE_OUTPUTS = ("chi", "jacobian", "dsignal", "docc_axes", "dsignal_axes")
+
+    def scan_grid_response(self, env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, kT, sensor_voltage=None, *,
+                           n_charge=None, frame="virtual", vgm=None, gamma=None, noise=(), serial=None, stream_base=None,
+                           occupations=False, variance=False, ztail=False, response=("dsignal_axes", "docc_axes")):
+        """scan_grid_thermal plus the CHARGE RESPONSE of the thermal state at every point of the grid (qd_scan_grid_response): the
+        derivatives of eval_points(kT=, response=True), and the two a grid is plotted with -- the lock-in charge-stability diagram
+        dS/dV along a sweep axis, and the slopes of the occupations along a transition line.  Arguments, frames and results are
+        scan_grid_thermal's, and
+          response   any non-empty subset of
+                       "chi"           (nq, ny, nx, N, 2N-1)  d<n_i>/d(eps_k) and d<n_i>/d(ln tc_d), as eval_points defines them
+                       "jacobian"      (nq, ny, nx, N, 2N)    d<n_i>/dv_j over the PHYSICAL voltages v = (vg, vb), in either frame
+                       "dsignal"       (nq, ny, nx, 2N)       dS/dv_j, the slope of the sensor expression at the thermal c0
+                       "docc_axes"     (nq, ny, nx, N, 2)     d<n_i>/d(sx), d<n_i>/d(sy) = jacobian . (u_x, u_y)
+                       "dsignal_axes"  (nq, ny, nx, 2)        dS/d(sx), dS/d(sy) = dsignal . (u_x, u_y)
+                     per unit of the axis scalars (the units of x_range / y_range), not per pixel.  u = dv/ds is the physical
+                     direction of one step of the scalar: the axis vector itself in the physical frame; in the virtual frame
+                     u[:N+1] = vgm @ axis[:N+1] with the query's `vgm` if given, else the env's matrix, and the barriers pass
+                     through
+        The kept list is held FIXED, Ns = rint(v''_s) is not differentiated and gamma is taken as constant, as in eval_points.
+        "raw", "image", "plohi", "occupations", "variance" and "ztail" equal scan_grid_thermal bit for bit under the same
+        arguments; the response is that of the noiseless sensor expression and does not depend on `noise`.  Open regime: the
+        epilogue runs inside the hop components of a point and agrees with eval_points(kT=, response=True) at the same voltages
+        within the sum of both tolerances.  With n_charge (closed): in the physical frame "chi", "jacobian" and "dsignal" equal
+        that call bit for bit.  Envs with the voltage-dependent capacitance model are refused."""
+        if kT is None:
+            raise ValueError("scan_grid_response needs kT: the response is that of the thermal state")
+        names = (response,) if isinstance(response, str) else tuple(response)
+        if not names or any(r not in self.RESPONSE_OUTPUTS for r in names):
+            raise ValueError(f"response must name a non-empty subset of {self.RESPONSE_OUTPUTS}, got {response!r}")
+        return self._scan_grid(env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm,
+                               gamma, noise, serial, stream_base, occupations, n_charge, kT, variance, ztail, response=names)
+
     def scan_grid_levels(self, env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage=None, *,
                          levels=2, n_charge=None, frame="virtual", vgm=None, gamma=None, noise=(), serial=None, stream_base=None,
                          occupations=False):
@@ -752,9 +785,9 @@ class VecQuantumDeviceEnv:
                                gamma, noise, serial, stream_base, occupations, n_charge, levels=L)
 
     def _scan_grid(self, env_ids, x, y, x_range, y_range, nx, ny, gate_voltages, barrier_voltages, sensor_voltage, frame, vgm, gamma,
-                   noise, serial, stream_base, occupations, n_charge, kT=None, variance=False, ztail=False, levels=0):
-        """scan_grid (n_charge None) and scan_grid_closed; with kT, scan_grid_thermal in either regime; with levels,
-        scan_grid_levels in either regime"""
+                   noise, serial, stream_base, occupations, n_charge, kT=None, variance=False, ztail=False, levels=0, response=()):
+        """scan_grid (n_charge None) and scan_grid_closed; with kT, scan_grid_thermal in either regime, and with `response`
+        scan_grid_response; with levels, scan_grid_levels in either regime"""
         N = self.N
         if frame not in ("virtual", "physical"):
             raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
@@ -804,6 +837,20 @@ class VecQuantumDeviceEnv:
                 out["variance"] = torch.zeros((nq, cy, cx, N), dtype=torch.float64, device=self.device)
             if ztail:
                 out["ztail"] = torch.zeros((nq, cy, cx), dtype=torch.float64, device=self.device)
+            if response:
+                shapes = {"chi": (N, 2 * N - 1), "jacobian": (N, 2 * N), "dsignal": (2 * N,), "docc_axes": (N, 2), "dsignal_axes": (2,)}
+                for r in response:
+                    out[r] = torch.zeros((nq, cy, cx) + shapes[r], dtype=torch.float64, device=self.device)
+                ropts = _lib.QdGridResponseOpts(struct_size=ctypes.sizeof(_lib.QdGridResponseOpts), reserved=0, n_charge_dev=addr(qd),
+                                                var_dst=addr(out.get("variance")), ztail_dst=addr(out.get("ztail")),
+                                                chi_dst=addr(out.get("chi")), jac_dst=addr(out.get("jacobian")),
+                                                dsignal_dst=addr(out.get("dsignal")), docc_axes_dst=addr(out.get("docc_axes")),
+                                                dsignal_axes_dst=addr(out.get("dsignal_axes")))
+                rc = self._lib.qd_scan_grid_response(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
+                                                     _ptr(kd), _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]),
+                                                     ctypes.byref(opts), ctypes.byref(ropts), self._stream())
+                _lib.check(self._h, rc, "qd_scan_grid_response")
+                return out
             topts = _lib.QdGridThermalOpts(struct_size=ctypes.sizeof(_lib.QdGridThermalOpts), reserved=0, n_charge_dev=addr(qd),
                                            var_dst=addr(out.get("variance")), ztail_dst=addr(out.get("ztail")))
             rc = self._lib.qd_scan_grid_thermal(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),

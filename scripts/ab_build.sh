@@ -5,5 +5,5 @@ cd "$(dirname "$0")/.."
 mkdir -p ab
 name=$1; shift
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -ffp-contract=off -fno-fast-math -Iinclude -Irl-agent-for-qubit-array-tuning_amd/csrc "$@" \
-    -o ab/libqdsim_$name.so rl-agent-for-qubit-array-tuning_amd/csrc/qd_api.hip
+    -o ab/libqdsim_$name.so rl-agent-for-qubit-array-tuning_amd/csrc/qd_api.hip rl-agent-for-qubit-array-tuning_amd/csrc/qd_response_grid.hip
 echo built ab/libqdsim_$name.so

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """scripts/co_diff.py A.so B.so: do two builds of the library (scripts/ab_build.sh) hold the same device code?  Unbundles the
-gfx950 code object of each and compares, kernel by kernel whatever their order in the file: the set of kernel symbols, the
+gfx950 code objects of each (one per translation unit) and compares, kernel by kernel whatever their order in the file: the set of kernel symbols, the
 code size of each and its resource metadata (VGPRs, AGPRs, SGPRs, spills, LDS, scratch, kernarg size, workgroup size).
 Prints the differences and one summary line; exit status 1 if there are any.  A host-only change must print none."""
 import os
@@ -16,10 +16,24 @@ FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_sp
 
 def kernels(lib, tmp):
     """{kernel symbol: {"size": code bytes, field: value}} of the gfx950 code object in `lib`"""
-    fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co")
+    fat = os.path.join(tmp, "fatbin")
     subprocess.check_call([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-    subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                           f"--input={fat}", f"--output={co}", "--unbundle"])
+    # one bundle per translation unit of the library, side by side in the section
+    blob = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(b"__CLANG_OFFLOAD_BUNDLE__"), blob)]
+    out = {}
+    for k, a in enumerate(starts):
+        part, co = os.path.join(tmp, f"fatbin{k}"), os.path.join(tmp, f"co{k}")
+        with open(part, "wb") as f:
+            f.write(blob[a:starts[k + 1] if k + 1 < len(starts) else len(blob)])
+        subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                               f"--input={part}", f"--output={co}", "--unbundle"])
+        out.update(code_object(co))
+    return out
+
+
+def code_object(co):
+    """{kernel symbol: ...} of one unbundled code object"""
     out = {}
     entry = None
     for line in subprocess.check_output([f"{LLVM}/llvm-readelf", "--notes", co], text=True).splitlines():
