@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <new>
+#include <type_traits>
 
 #include "qdsim.h"
 #include "qd_kernels.h"
@@ -35,7 +36,7 @@ struct QdStream : QdNoCopy {
 struct QdEvent : QdNoCopy {
     hipEvent_t e = nullptr;
     ~QdEvent() { if (e) (void)hipEventDestroy(e); }
-    hipError_t create(unsigned flags = hipEventDisableTiming) { return hipEventCreateWithFlags(&e, flags); }
+    hipError_t create(unsigned flags) { return hipEventCreateWithFlags(&e, flags); }
 };
 
 // Scratch + streams of one launch chunk in flight.  Product mode keeps TWO: consecutive chunks alternate between them on
@@ -68,7 +69,7 @@ struct QdStageRing {
         if (need <= slot[0].cap) return hipSuccess;
         for (int k = 0; k < 2; ++k) {
             if (hipError_t e = wait(k)) return e;
-            if (!ev[k].e) if (hipError_t e = ev[k].create()) return e;
+            if (!ev[k].e) if (hipError_t e = ev[k].create(hipEventDisableTiming)) return e;
         }
         QdBuf<double, QdPinned>* const both[] = {&slot[0], &slot[1]};
         const size_t n[] = {need, need};
@@ -103,8 +104,7 @@ struct QdEnvBufs {
 struct QdScratchSet {
     QdDev<double> params, state, z, plohi, occ;
     QdDev<unsigned long long> tel;
-    hipError_t reserve(const QdLayout& L, size_t CP, size_t slots, size_t plohi_per_slot, size_t occ_per_slot,
-                       size_t tel_per_slot = 0) {
+    hipError_t reserve(const QdLayout& L, size_t CP, size_t slots, size_t plohi_per_slot, size_t occ_per_slot, size_t tel_per_slot) {
         QdDev<double>* const all[] = {&params, &state, &z, &plohi, &occ};
         const size_t n[] = {slots * L.size, slots * L.s_size, slots * CP, slots * plohi_per_slot, slots * occ_per_slot};
         hipError_t e = qd_reserve_group(all, n);
@@ -114,7 +114,7 @@ struct QdScratchSet {
         return e;
     }
     // without noise, eigenvalues or telegraph words
-    QdEnvBufs view(int channels, int R, QdFront front = QD_FRONT_ENV) const {
+    QdEnvBufs view(int channels, int R, QdFront front) const {
         QdEnvBufs b{};
         b.params = params.p; b.state = state.p; b.zraw = z.p; b.plohi = plohi.p; b.occ = occ.p;
         b.channels = channels; b.R = R; b.P = R * R; b.front = front;
@@ -192,17 +192,34 @@ static QdEnvBufs qd_env_bufs(const qd_handle* h) {
     return b;
 }
 
-static int qd_fail(const qd_handle* h, int code, const char* what, hipError_t e = hipSuccess) {
-    if (h) {
-        if (e != hipSuccess) snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
-        else snprintf(h->err, sizeof(h->err), "%s", what);
-    }
+static int qd_fail(const qd_handle* h, int code, const char* what) { if (h) snprintf(h->err, sizeof(h->err), "%s", what); return code; }
+static int qd_fail(const qd_handle* h, int code, const char* what, hipError_t e) {      // e: the failure of a HIP call
+    if (h) snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
     return code;
 }
 // a message that names the entry point: `fmt` has one %s for `who`, and may have a second one for `what`
-static int qd_failf(const qd_handle* h, int code, const char* fmt, const char* who, const char* what = "") {
+static int qd_failf(const qd_handle* h, int code, const char* fmt, const char* who, const char* what) {
     if (h) snprintf(h->err, sizeof(h->err), fmt, who, what);
     return code;
+}
+static int qd_failf(const qd_handle* h, int code, const char* fmt, const char* who) { return qd_failf(h, code, fmt, who, ""); }
+// the struct_size (first field) of any option struct; `opts` null is a call without options; `what` is the whole message
+static int qd_check_struct_size(const qd_handle* h, const void* opts, size_t size, const char* what) {
+    int32_t got = (int32_t)size;
+    if (opts) memcpy(&got, opts, sizeof(got));
+    return got == (int32_t)size ? (int)QD_OK : qd_fail(h, QD_ERR_ARG, what);
+}
+// the temperatures of a points call, one per group on the host
+static int qd_check_kT_host(const qd_handle* h, const char* who, const double* kT, int ng) {
+    if (!kT) return qd_failf(h, QD_ERR_ARG, "%s: kT_host is NULL", who);
+    for (int g = 0; g < ng; ++g)
+        if (!(kT[g] > 0.0) || !(kT[g] < INFINITY)) return qd_failf(h, QD_ERR_ARG, "%s: kT must be finite and > 0", who);
+    return QD_OK;
+}
+// the refusal of the response calls, points and grids, for an env with the voltage-dependent capacitance model (h->vc_on)
+static int qd_fail_vc(const qd_handle* h, const char* who) {
+    return qd_failf(h, QD_ERR_STATE, "%s: the env carries the voltage-dependent capacitance model, whose per-point scale "
+                                    "factors make d F / d v depend on v; that chain rule is not built", who);
 }
 #define QD_HIP(call)                                                              \
     do { hipError_t e_ = (call); if (e_ != hipSuccess) return qd_fail(h, QD_ERR_HIP, #call, e_); } while (0)
@@ -388,12 +405,12 @@ extern "C" int qd_create(const qd_config* cfg, int device, qd_handle** out) {
     QD_HIP(h->steps.reserve((size_t)h->B));
     QD_HIP(h->zraw.reserve((size_t)h->B * h->C * h->P));
     QD_HIP(h->plohi.reserve(2 * (size_t)h->B));
-    QD_HIP(h->ev_start.create());
+    QD_HIP(h->ev_start.create(hipEventDisableTiming));
     for (int k = 0; k < h->nlanes; ++k) {
         QdLane& ln = h->lanes[k];
         QD_HIP(ln.recs.reserve(per_env_rec / sizeof(QdPixelRec) * (size_t)h->chunk));
         for (QdStream* q : {&ln.run, &ln.side, &ln.side2}) QD_HIP(q->create());
-        for (QdEvent* ev : {&ln.ev_fork, &ln.ev_join, &ln.ev_join2, &ln.ev_done}) QD_HIP(ev->create());
+        for (QdEvent* ev : {&ln.ev_fork, &ln.ev_join, &ln.ev_join2, &ln.ev_done}) QD_HIP(ev->create(hipEventDisableTiming));
     }
     h->tel_words = (h->P + 63) / 64;
     if (cfg->noise_flags & QD_NOISE_SENSOR) {
@@ -938,8 +955,7 @@ extern "C" int qd_probe_ex(qd_handle* h, const int32_t* env_of_query, int nq, co
     if (nq < 0) return qd_fail(h, QD_ERR_ARG, "qd_probe: nq < 0");
     if (!env_of_query) return qd_fail(h, QD_ERR_ARG, "qd_probe: env_of_query_dev is NULL");
     if (!gate_v || !barrier_v) return qd_fail(h, QD_ERR_ARG, "qd_probe: gate_v_dev or barrier_v_dev is NULL");
-    if (opts && opts->struct_size != (int32_t)sizeof(qd_probe_opts))
-        return qd_fail(h, QD_ERR_ARG, "qd_probe_ex: opts->struct_size is not sizeof(qd_probe_opts)");
+    if (int rc = qd_check_struct_size(h, opts, sizeof(qd_probe_opts), "qd_probe_ex: opts->struct_size is not sizeof(qd_probe_opts)")) return rc;
     if (opts && (opts->noise_flags & ~(QD_NOISE_SENSOR | QD_NOISE_RADIAL | QD_NOISE_LATCH)))
         return qd_fail(h, QD_ERR_ARG, "qd_probe_ex: opts->noise_flags has a bit that is no QD_NOISE_* stage");
     if (h->cfg.flags & QD_FLAG_VALIDATE)
@@ -998,12 +1014,10 @@ static int qd_check_scan_arrays(const qd_handle* h, const char* who, int nq, con
 static int qd_check_scan(const qd_handle* h, const char* who, const char* opts_type, const char* what, const void* opts, bool thermal,
                          QdQueryOpts& o) {
     qd_scan_opts so{};
-    if (opts) {
-        memcpy(&so.struct_size, opts, sizeof(so.struct_size));
-        if (so.struct_size != (int32_t)sizeof(qd_scan_opts))
-            return qd_failf(h, QD_ERR_ARG, "%s: opts->struct_size is not sizeof(%s)", who, opts_type);
-        memcpy(&so, opts, sizeof(so));
-    }
+    char size_msg[128];
+    snprintf(size_msg, sizeof(size_msg), "%s: opts->struct_size is not sizeof(%s)", who, opts_type);
+    if (int rc = qd_check_struct_size(h, opts, sizeof(qd_scan_opts), size_msg)) return rc;
+    if (opts) memcpy(&so, opts, sizeof(so));
     if (so.frame != QD_SCAN_VIRTUAL && so.frame != QD_SCAN_PHYSICAL)
         return qd_failf(h, QD_ERR_ARG, "%s: opts->frame is neither QD_SCAN_VIRTUAL nor QD_SCAN_PHYSICAL", who);
     if (so.frame == QD_SCAN_PHYSICAL && so.vgm_dev) return qd_failf(h, QD_ERR_ARG, "%s: vgm_dev has no meaning in the physical frame", who);
@@ -1182,43 +1196,51 @@ static int qd_check_device_range(const qd_handle* h, const char* who, const T* d
 #define QD_RSG_WHOLE(n_charge) ((n_charge) != nullptr)
 #endif
 
-// qd_scan_grid (n_charge null) and qd_scan_grid_closed on the runner of the lines: the closed regime replaces the redo pass of
-// the open search by qd_k_closed at the queries' total charges and leaves every other launch as it is.  kT ([nq], device):
-// qd_scan_grid_thermal, the thermal kernel of qd_thermal_blocks.h in place of the ground-state stage, once, on the lists as the
-// search left them; the slots always carry occupations then.  n_levels > 0: qd_scan_grid_levels, the levels kernel of
-// qd_levels_blocks.h behind the search and before the ground-state stage, which reads the records and writes the caller's rows.
-// rd (with kT): qd_scan_grid_response, the thermal kernel with the response epilogue of qd_response_blocks.h in its place.
+// What runs behind the search of a grid (qd_grid_run) or of points (qd_points_run).  All off, as a value starts, is qd_scan_grid /
+// qd_eval_points; every other entry point sets by name what it adds.  Per query on the device (grids), per group on the host (points).
+struct QdBehindSearch {
+    // qd_*_closed: qd_k_closed at these total charges replaces the redo pass of the open search; states_dst (points): the kept states
+    const int32_t* n_charge = nullptr; int32_t* states_dst = nullptr;
+    // qd_*_thermal (a host kT is checked by the caller): the thermal kernel (qd_thermal_blocks.h, qd_thermal.h) in place of the
+    // ground-state stage, once, on the lists as the search left them; a grid's slots always carry occupations then
+    const double* kT = nullptr; double *var_dst = nullptr, *ztail_dst = nullptr;
+    // n_levels > 0 (qd_scan_grid_levels, qd_eval_points_ex): the levels kernel (qd_levels_blocks.h, qd_levels.h) behind the search and
+    // before the ground-state stage; it reads the records and writes the caller's rows
+    int n_levels = 0; double *levels_dst = nullptr, *hnorm_dst = nullptr;
+    // any row, with kT (qd_*_response; points: chi, jac, dsignal): the thermal kernel with the response epilogue in its place
+    QdGridResponseDst rd{};
+    bool response() const { return rd.chi || rd.jac || rd.dsignal || rd.docc_axes || rd.dsignal_axes; }
+    const double* gamma = nullptr;                      // points: the peak width of every group; null: each env's own
+};
+
+// qd_scan_grid and its four siblings on the runner of the lines; x: what runs behind the search
 static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
                        const double* range, const double* gate_v, const double* barrier_v, const double* sensor_v, double* raw_dst,
-                       float* image_dst, double* plohi_dst, const qd_scan_grid_opts* opts, const int32_t* n_charge, void* stream,
-                       const double* kT = nullptr, double* var_dst = nullptr, double* ztail_dst = nullptr, int n_levels = 0,
-                       double* levels_dst = nullptr, double* hnorm_dst = nullptr, const QdGridResponseDst* rd = nullptr) {
+                       float* image_dst, double* plohi_dst, const qd_scan_grid_opts* opts, const QdBehindSearch& x, void* stream) {
     static_assert(QD_GRID_MAX_SLOTS == QD_GRID_SLOTS, "qdsim.h states the bound");
     static_assert(QD_THG_BLOCKS <= QD_GRID_MAX_SLOTS && QD_LVG_BLOCKS <= QD_GRID_MAX_SLOTS, "a launch dimension");
     QdQueryOpts o;
     if (int rc = qd_check_scan_arrays(h, who, nq, env_of_query, dir, "dir_dev", range, gate_v, barrier_v)) return rc;
     if (nx < 1 || ny < 1 || (long long)nx * ny > h->P)
         return qd_failf(h, QD_ERR_ARG, "%s: nx and ny must be >= 1 with nx*ny <= P (P = resolution^2 of the handle)", who);
-    if (int rc = qd_check_scan(h, who, "qd_scan_grid_opts", "grid", opts, kT != nullptr, o)) return rc;
-    if (n_charge && o.noise_flags)
+    if (int rc = qd_check_scan(h, who, "qd_scan_grid_opts", "grid", opts, x.kT != nullptr, o)) return rc;
+    if (x.n_charge && o.noise_flags)
         return qd_failf(h, QD_ERR_ARG, "%s: the closed regime has no noise stages: noise_flags must be 0", who);
     if (nq == 0) return QD_OK;
     hipStream_t s = (hipStream_t)stream;
     QD_ON_DEVICE(h);
-    if (n_charge)
-        if (int rc = qd_check_device_range(h, who, n_charge, nq, s, "hipMemcpyAsync(n_charge)", "%s: n_charge must be in 0..32767",
+    if (x.n_charge)
+        if (int rc = qd_check_device_range(h, who, x.n_charge, nq, s, "hipMemcpyAsync(n_charge)", "%s: n_charge must be in 0..32767",
                                            [](int32_t v) { return v >= 0 && v <= QD_CLOSED_QMAX; })) return rc;
-    if (kT)
-        if (int rc = qd_check_device_range(h, who, kT, nq, s, "hipMemcpyAsync(kT)", "%s: kT must be finite and > 0",
+    if (x.kT)
+        if (int rc = qd_check_device_range(h, who, x.kT, nq, s, "hipMemcpyAsync(kT)", "%s: kT must be finite and > 0",
                                            [](double v) { return v > 0.0 && v < INFINITY; })) return rc;
-    if (rd) {
+    if (x.response()) {
         // (with no response destination the call is qd_scan_grid_thermal, which takes such envs)
         bool vc = false;
         if (int rc = qd_check_device_range(h, who, env_of_query, nq, s, "hipMemcpyAsync(env_of_query)", "%s: env_of_query",
                                            [&](int32_t e) { vc = vc || (e >= 0 && e < h->B && h->vc_on[(size_t)e]); return true; })) return rc;
-        if (vc)
-            return qd_failf(h, QD_ERR_STATE, "%s: the env carries the voltage-dependent capacitance model, whose per-point scale "
-                                            "factors make d F / d v depend on v; that chain rule is not built", who);
+        if (vc) return qd_fail_vc(h, who);
     }
     const QdAffineQuery Q{env_of_query, dir, range, gate_v, barrier_v, sensor_v, o.vgm, o.gamma, o.frame};
     // the slot of a grid is that of a line of nx*ny points, record p = y*nx + x
@@ -1236,42 +1258,32 @@ static int qd_grid_run(qd_handle* h, const char* who, const int32_t* env_of_quer
             QD_DISPATCH_N(h->N, qd_k_grid_front<NN><<<dim3((SP + QD_GRID_BLOCK - 1) / QD_GRID_BLOCK, cnt), dim3(QD_GRID_BLOCK), 0, s>>>(
                                     SP, b.params, b.state, axes, ln.recs.p));
             QD_HIP(hipGetLastError());
-            if (n_charge) { if (int rc = qd_launch_closed(h, b, ln, SP, n_charge + base, cnt, s)) return rc; }
+            if (x.n_charge) { if (int rc = qd_launch_closed(h, b, ln, SP, x.n_charge + base, cnt, s)) return rc; }
             else if (int rc = qd_launch_candidates(h, b, ln, nullptr, 0, cnt, s, true)) return rc;
-            if (n_levels > 0) {
+            if (x.n_levels > 0) {
                 // the levels of the list as the search left it (a closed list is one hop component: the whole-block core)
                 const dim3 lgrid((unsigned)(n < QD_LVG_BLOCKS ? n : QD_LVG_BLOCKS), cnt);
-                if (QD_LVG_WHOLE(n_charge)) {
-                    QD_DISPATCH_N(h->N, qd_k_levels_grid<NN, QdLevelsWs><<<lgrid, dim3(64), 0, s>>>(env_of_query, base, h->B, n, SP, h->kept,
-                                                                                                  n_levels, ln.recs.p, levels_dst, hnorm_dst));
-                } else {
-                    QD_DISPATCH_N(h->N, qd_k_levels_grid<NN, QdLevelsBlocksWs><<<lgrid, dim3(64), 0, s>>>(env_of_query, base, h->B, n, SP,
-                                                                                                        h->kept, n_levels, ln.recs.p,
-                                                                                                        levels_dst, hnorm_dst));
-                }
+                QD_DISPATCH_BOOL(QD_LVG_WHOLE(x.n_charge), WHOLE, QD_DISPATCH_N(h->N,
+                    qd_k_levels_grid<NN, std::conditional_t<WHOLE, QdLevelsWs, QdLevelsBlocksWs>><<<lgrid, dim3(64), 0, s>>>(
+                        env_of_query, base, h->B, n, SP, h->kept, x.n_levels, ln.recs.p, x.levels_dst, x.hnorm_dst)));
                 QD_HIP(hipGetLastError());
             }
-            if (!kT) return qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND);
+            if (!x.kT) return qd_launch_ground(h, b, ln, nullptr, 0, cnt, s, QD_ST_GROUND);
             // the thermal state instead of the ground state: c0 and <n> into the slots' zraw and occ, then the unchanged stages
             const dim3 tgrid((unsigned)(n < QD_THG_BLOCKS ? n : QD_THG_BLOCKS), cnt);
-            if (rd) {
+            if (x.response()) {
                 // qd_scan_grid_response: the thermal kernel with the response epilogue (qd_response_blocks.h), whose instances are
                 // compiled in qd_response_grid.hip
-                if (!qd_launch_thermal_grid_response(h->N, QD_RSG_WHOLE(n_charge), tgrid, s, &Q, sizeof(Q), base, h->B, n, SP, h->kept, kT,
-                                                     b.params, b.state, axes, ln.recs.p, b.zraw, b.occ, var_dst, ztail_dst, *rd))
+                if (!qd_launch_thermal_grid_response(h->N, QD_RSG_WHOLE(x.n_charge), tgrid, s, &Q, sizeof(Q), base, h->B, n, SP, h->kept, x.kT,
+                                                     b.params, b.state, axes, ln.recs.p, b.zraw, b.occ, x.var_dst, x.ztail_dst, x.rd))
                     return qd_fail(h, QD_ERR_ARG, "n_dot must be in 2..8");
                 QD_HIP(hipGetLastError());
                 return (int)QD_OK;
             }
             // (a closed list is one hop component: the whole-block core, see qd_k_thermal_grid)
-            if (n_charge) {
-                QD_DISPATCH_N(h->N, qd_k_thermal_grid<NN, QdThermalWs><<<tgrid, dim3(64), 0, s>>>(Q, base, h->B, n, SP, h->kept, kT, b.params,
-                                                                                                ln.recs.p, b.zraw, b.occ, var_dst, ztail_dst));
-            } else {
-                QD_DISPATCH_N(h->N, qd_k_thermal_grid<NN, QdThermalBlocksWs><<<tgrid, dim3(64), 0, s>>>(Q, base, h->B, n, SP, h->kept, kT,
-                                                                                                      b.params, ln.recs.p, b.zraw, b.occ,
-                                                                                                      var_dst, ztail_dst));
-            }
+            QD_DISPATCH_BOOL(x.n_charge != nullptr, WHOLE, QD_DISPATCH_N(h->N,
+                qd_k_thermal_grid<NN, std::conditional_t<WHOLE, QdThermalWs, QdThermalBlocksWs>><<<tgrid, dim3(64), 0, s>>>(
+                    Q, base, h->B, n, SP, h->kept, x.kT, b.params, ln.recs.p, b.zraw, b.occ, x.var_dst, x.ztail_dst)));
             QD_HIP(hipGetLastError());
             return (int)QD_OK;
         },
@@ -1288,7 +1300,7 @@ extern "C" int qd_scan_grid(qd_handle* h, const int32_t* env_of_query, int nq, i
                             double* plohi_dst, const qd_scan_grid_opts* opts, void* stream) {
     if (!h) return QD_ERR_ARG;
     return qd_grid_run(h, "qd_scan_grid", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
-                       plohi_dst, opts, nullptr, stream);
+                       plohi_dst, opts, QdBehindSearch{}, stream);
 }
 
 extern "C" int qd_scan_grid_closed(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
@@ -1297,8 +1309,9 @@ extern "C" int qd_scan_grid_closed(qd_handle* h, const int32_t* env_of_query, in
                                    const qd_scan_grid_opts* opts, void* stream) {
     if (!h) return QD_ERR_ARG;
     if (!n_charge) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_closed: n_charge_dev is NULL");
+    QdBehindSearch x; x.n_charge = n_charge;
     return qd_grid_run(h, "qd_scan_grid_closed", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
-                       plohi_dst, opts, n_charge, stream);
+                       plohi_dst, opts, x, stream);
 }
 
 extern "C" int qd_scan_grid_thermal(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
@@ -1307,11 +1320,12 @@ extern "C" int qd_scan_grid_thermal(qd_handle* h, const int32_t* env_of_query, i
                                     const qd_scan_grid_opts* opts, const qd_grid_thermal_opts* topts, void* stream) {
     if (!h) return QD_ERR_ARG;
     if (!kT) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_thermal: kT_dev is NULL");
-    if (topts && topts->struct_size != (int32_t)sizeof(qd_grid_thermal_opts))
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_thermal: topts->struct_size is not sizeof(qd_grid_thermal_opts)");
+    if (int rc = qd_check_struct_size(h, topts, sizeof(qd_grid_thermal_opts),
+                                      "qd_scan_grid_thermal: topts->struct_size is not sizeof(qd_grid_thermal_opts)")) return rc;
+    QdBehindSearch x; x.kT = kT;
+    if (topts) { x.n_charge = topts->n_charge_dev; x.var_dst = topts->var_dst; x.ztail_dst = topts->ztail_dst; }
     return qd_grid_run(h, "qd_scan_grid_thermal", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
-                       plohi_dst, opts, topts ? topts->n_charge_dev : nullptr, stream, kT, topts ? topts->var_dst : nullptr,
-                       topts ? topts->ztail_dst : nullptr);
+                       plohi_dst, opts, x, stream);
 }
 
 extern "C" int qd_scan_grid_response(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
@@ -1320,15 +1334,14 @@ extern "C" int qd_scan_grid_response(qd_handle* h, const int32_t* env_of_query, 
                                      const qd_scan_grid_opts* opts, const qd_grid_response_opts* ropts, void* stream) {
     if (!h) return QD_ERR_ARG;
     if (!kT) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_response: kT_dev is NULL");
-    if (ropts && ropts->struct_size != (int32_t)sizeof(qd_grid_response_opts))
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_response: ropts->struct_size is not sizeof(qd_grid_response_opts)");
-    QdGridResponseDst rd{};
-    if (ropts) rd = QdGridResponseDst{ropts->chi_dst, ropts->jac_dst, ropts->dsignal_dst, ropts->docc_axes_dst, ropts->dsignal_axes_dst};
+    if (int rc = qd_check_struct_size(h, ropts, sizeof(qd_grid_response_opts),
+                                      "qd_scan_grid_response: ropts->struct_size is not sizeof(qd_grid_response_opts)")) return rc;
+    QdBehindSearch x; x.kT = kT;
+    if (ropts) { x.n_charge = ropts->n_charge_dev; x.var_dst = ropts->var_dst; x.ztail_dst = ropts->ztail_dst; }
     // (with all five null the call launches qd_k_thermal_grid itself)
-    const bool any = rd.chi || rd.jac || rd.dsignal || rd.docc_axes || rd.dsignal_axes;
+    if (ropts) x.rd = QdGridResponseDst{ropts->chi_dst, ropts->jac_dst, ropts->dsignal_dst, ropts->docc_axes_dst, ropts->dsignal_axes_dst};
     return qd_grid_run(h, "qd_scan_grid_response", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
-                       plohi_dst, opts, ropts ? ropts->n_charge_dev : nullptr, stream, kT, ropts ? ropts->var_dst : nullptr,
-                       ropts ? ropts->ztail_dst : nullptr, 0, nullptr, nullptr, any ? &rd : nullptr);
+                       plohi_dst, opts, x, stream);
 }
 
 extern "C" int qd_scan_grid_levels(qd_handle* h, const int32_t* env_of_query, int nq, int nx, int ny, const double* dir,
@@ -1337,28 +1350,23 @@ extern "C" int qd_scan_grid_levels(qd_handle* h, const int32_t* env_of_query, in
                                    const qd_grid_levels_opts* lopts, void* stream) {
     if (!h) return QD_ERR_ARG;
     if (!lopts) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_levels: lopts is NULL");
-    if (lopts->struct_size != (int32_t)sizeof(qd_grid_levels_opts))
-        return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_levels: lopts->struct_size is not sizeof(qd_grid_levels_opts)");
+    if (int rc = qd_check_struct_size(h, lopts, sizeof(qd_grid_levels_opts),
+                                      "qd_scan_grid_levels: lopts->struct_size is not sizeof(qd_grid_levels_opts)")) return rc;
     if (lopts->n_levels < 1 || lopts->n_levels > QD_LEVELS_MAX)
         return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_levels: n_levels must be in 1..QD_LEVELS_MAX (8)");
     if (!lopts->levels_dst) return qd_fail(h, QD_ERR_ARG, "qd_scan_grid_levels: levels_dst is NULL");
+    QdBehindSearch x; x.n_charge = lopts->n_charge_dev;
+    x.n_levels = lopts->n_levels; x.levels_dst = lopts->levels_dst; x.hnorm_dst = lopts->hnorm_dst;
     return qd_grid_run(h, "qd_scan_grid_levels", env_of_query, nq, nx, ny, dir, range, gate_v, barrier_v, sensor_v, raw_dst, image_dst,
-                       plohi_dst, opts, lopts->n_charge_dev, stream, nullptr, nullptr, nullptr, lopts->n_levels, lopts->levels_dst,
-                       lopts->hnorm_dst);
+                       plohi_dst, opts, x, stream);
 }
 
 // slots in flight of qd_eval_points: one launch chunk of lane 0's records, at most QD_POINTS_SLOTS
 static int qd_points_slots(const qd_handle* h) { return h->chunk < QD_POINTS_MAX_SLOTS ? h->chunk : QD_POINTS_MAX_SLOTS; }
 
-// qd_eval_points (n_charge null), qd_eval_points_closed and qd_eval_points_ex on one slot loop, as qd_grid_run.  n_levels > 0: the
-// levels kernel (qd_levels.h) behind the search of every flush; n_levels == 0 launches what the first two always launched.
-// kT (one per group, checked by the caller): qd_eval_points_thermal, the thermal kernel (qd_thermal.h) in place of the
-// ground-state stage, once, on the list as the search left it.
+// qd_eval_points and its four siblings on one slot loop, as qd_grid_run; x: what runs behind the search of every flush.
 static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
-                         const double* vb, const double* gamma, const int32_t* n_charge, double* signal_dst, double* occ_dst,
-                         int32_t* states_dst, void* stream, int n_levels = 0, double* levels_dst = nullptr, double* hnorm_dst = nullptr,
-                         const double* kT = nullptr, double* var_dst = nullptr, double* ztail_dst = nullptr, double* chi_dst = nullptr,
-                         double* jac_dst = nullptr, double* dsignal_dst = nullptr) {
+                         const double* vb, double* signal_dst, double* occ_dst, const QdBehindSearch& x, void* stream) {
     static_assert(QD_POINTS_MAX_SLOTS == QD_POINTS_SLOTS, "qdsim.h states the bound");
     if (ng < 0) return qd_failf(h, QD_ERR_ARG, "%s: ng < 0", who);
     if (!group_env || !group_start) return qd_failf(h, QD_ERR_ARG, "%s: group_env_host or group_start_host is NULL", who);
@@ -1367,7 +1375,7 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
     for (int g = 0; g < ng; ++g) {
         if (group_start[g + 1] < group_start[g]) return qd_failf(h, QD_ERR_ARG, "%s: group_start is not non-decreasing", who);
         if (group_env[g] < 0 || group_env[g] >= h->B) return qd_failf(h, QD_ERR_ARG, "%s: env id out of range", who);
-        if (n_charge && (n_charge[g] < 0 || n_charge[g] > QD_CLOSED_QMAX)) return qd_failf(h, QD_ERR_ARG, "%s: n_charge must be in 0..32767", who);
+        if (x.n_charge && (x.n_charge[g] < 0 || x.n_charge[g] > QD_CLOSED_QMAX)) return qd_failf(h, QD_ERR_ARG, "%s: n_charge must be in 0..32767", who);
     }
     if (h->cfg.flags & QD_FLAG_VALIDATE)
         return qd_failf(h, QD_ERR_STATE, "%s: a QD_FLAG_VALIDATE handle keeps records, occupations and eigenvalues of its "
@@ -1380,18 +1388,18 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
     QD_ON_DEVICE(h);
     const int ps = qd_points_slots(h);
     const long long CP = (long long)h->C * h->P;
-    QD_HIP(h->points.reserve(h->L, (size_t)CP, (size_t)ps, 0, (size_t)CP * h->N));
+    QD_HIP(h->points.reserve(h->L, (size_t)CP, (size_t)ps, 0, (size_t)CP * h->N, 0));      // (neither percentiles nor telegraph words)
     // the ground-state launcher runs on the point buffers, without noise or eigenvalues; nothing of the envs is written
-    const QdEnvBufs qb = h->points.view(h->C, h->R);
+    const QdEnvBufs qb = h->points.view(h->C, h->R, QD_FRONT_ENV);
     const QdLane& ln = h->lanes[0];
-    if (n_charge) QD_HIP(h->closed_q.reserve((size_t)QD_POINTS_MAX_SLOTS));
+    if (x.n_charge) QD_HIP(h->closed_q.reserve((size_t)QD_POINTS_MAX_SLOTS));
     QdPointSlots T;
     memset(&T, 0, sizeof(T));
     QdClosedQ TQ;
     memset(&TQ, 0, sizeof(TQ));
     QdThermalKT TK;
     memset(&TK, 0, sizeof(TK));
-    T.own_gamma = gamma ? 0 : 1;
+    T.own_gamma = x.gamma ? 0 : 1;
     int n = 0;
     // one launch per `ps` slots: gather -> front end -> per-pixel search of the handed-over records -> ground state -> write
     auto flush = [&]() -> int {
@@ -1403,34 +1411,33 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
         QD_HIP(hipGetLastError());
         // (the redo instantiation, and not through qd_launch_csd: on handles without a tile search that would pick the
         // whole per-pixel search and overwrite the front end)
-        if (n_charge) {
+        if (x.n_charge) {
             // the closed regime: the slots' total charges to the device, then centre and sector search instead of the redo pass
             qd_k_closed_setq<<<dim3(1), dim3(QD_POINTS_MAX_SLOTS), 0, s>>>(TQ, n, h->closed_q.p);
             QD_HIP(hipGetLastError());
             if (int rc = qd_launch_closed(h, qb, ln, (int)CP, h->closed_q.p, n, s)) return rc;
-            if (states_dst) {
-                QD_DISPATCH_N(h->N, qd_k_closed_states<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, h->kept, ln.recs.p, states_dst));
+            if (x.states_dst) {
+                QD_DISPATCH_N(h->N, qd_k_closed_states<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, h->kept, ln.recs.p, x.states_dst));
                 QD_HIP(hipGetLastError());
             }
         } else if (int rc = qd_launch_candidates(h, qb, ln, nullptr, 0, n, s, true)) return rc;
-        if (n_levels > 0) {
+        if (x.n_levels > 0) {
             // the levels of the list as the search left it, before any qd_k_points_sort: one point per single-wave block
             const dim3 lgrid((unsigned)(CP < 4096 ? CP : 4096), n);
-            QD_DISPATCH_N(h->N, qd_k_levels<NN><<<lgrid, dim3(64), 0, s>>>(T, (int)CP, h->kept, n_levels, ln.recs.p, levels_dst, hnorm_dst));
+            QD_DISPATCH_N(h->N, qd_k_levels<NN><<<lgrid, dim3(64), 0, s>>>(T, (int)CP, h->kept, x.n_levels, ln.recs.p, x.levels_dst, x.hnorm_dst));
             QD_HIP(hipGetLastError());
             if (!signal_dst && !occ_dst) { n = 0; return QD_OK; }          // levels only: no ground-state stage
         }
-        if (kT) {
+        if (x.kT) {
             // the thermal state instead of the ground state: c0 and <n> into the slots' zraw and occ, then the unchanged write
             const dim3 tgrid((unsigned)(CP < 4096 ? CP : 4096), n);
-            if (chi_dst || jac_dst || dsignal_dst) {
-                // qd_eval_points_response: the thermal kernel with the response epilogue (qd_response.h); dc0/dv into dsignal_dst
-                QD_DISPATCH_N(h->N, qd_k_thermal_response<NN><<<tgrid, dim3(64), 0, s>>>(T, TK, (int)CP, h->kept, qb.params, ln.recs.p,
-                                                                                        qb.zraw, qb.occ, var_dst, ztail_dst, chi_dst,
-                                                                                        jac_dst, dsignal_dst));
+            if (x.response()) {
+                // qd_eval_points_response: the thermal kernel with the response epilogue (qd_response.h); dc0/dv into x.rd.dsignal
+                QD_DISPATCH_N(h->N, qd_k_thermal_response<NN><<<tgrid, dim3(64), 0, s>>>(
+                    T, TK, (int)CP, h->kept, qb.params, ln.recs.p, qb.zraw, qb.occ, x.var_dst, x.ztail_dst, x.rd.chi, x.rd.jac, x.rd.dsignal));
             } else {
                 QD_DISPATCH_N(h->N, qd_k_thermal<NN><<<tgrid, dim3(64), 0, s>>>(T, TK, (int)CP, h->kept, qb.params, ln.recs.p, qb.zraw,
-                                                                               qb.occ, var_dst, ztail_dst));
+                                                                               qb.occ, x.var_dst, x.ztail_dst));
             }
             QD_HIP(hipGetLastError());
             if (signal_dst || occ_dst) {
@@ -1438,8 +1445,8 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
                                                                                                signal_dst, occ_dst));
                 QD_HIP(hipGetLastError());
             }
-            if (dsignal_dst) {
-                QD_DISPATCH_N(h->N, qd_k_points_dsignal<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, qb.params, qb.zraw, dsignal_dst));
+            if (x.rd.dsignal) {
+                QD_DISPATCH_N(h->N, qd_k_points_dsignal<NN><<<grid, dim3(QD_POINTS_BLOCK), 0, s>>>(T, (int)CP, qb.params, qb.zraw, x.rd.dsignal));
                 QD_HIP(hipGetLastError());
             }
             n = 0;
@@ -1449,7 +1456,7 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
         // The occupations come from the list in the reference order, which is what a validate handle solves and
         // qd_get_occupations returns: with K == KC (search order) the records are sorted and the ground-state stage runs again.
         // (the closed lists are in the reference order as they come)
-        const bool resort = !n_charge && !qd_sorted_records(h) && occ_dst;
+        const bool resort = !x.n_charge && !qd_sorted_records(h) && occ_dst;
         if (signal_dst || !resort) {
             if (int rc = qd_launch_ground(h, qb, ln, nullptr, 0, n, s, QD_ST_GROUND)) return rc;
             if (signal_dst || occ_dst) {
@@ -1474,9 +1481,9 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
         for (long long p0 = group_start[g]; p0 < group_start[g + 1]; p0 += CP) {
             const long long left = group_start[g + 1] - p0;
             T.start[n] = p0; T.env[n] = group_env[g]; T.cnt[n] = (int)(left < CP ? left : CP);
-            T.gamma[n] = gamma ? gamma[g] : 0.0;
-            TQ.q[n] = n_charge ? n_charge[g] : 0;
-            TK.kT[n] = kT ? kT[g] : 0.0;
+            T.gamma[n] = x.gamma ? x.gamma[g] : 0.0;
+            TQ.q[n] = x.n_charge ? x.n_charge[g] : 0;
+            TK.kT[n] = x.kT ? x.kT[g] : 0.0;
             if (++n == ps) if (int rc = flush()) return rc;
         }
     }
@@ -1486,7 +1493,8 @@ static int qd_points_run(qd_handle* h, const char* who, const int32_t* group_env
 extern "C" int qd_eval_points(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
                               const double* vb, const double* gamma, double* signal_dst, double* occ_dst, void* stream) {
     if (!h) return QD_ERR_ARG;
-    return qd_points_run(h, "qd_eval_points", group_env, group_start, ng, vg, vb, gamma, nullptr, signal_dst, occ_dst, nullptr, stream);
+    QdBehindSearch x; x.gamma = gamma;
+    return qd_points_run(h, "qd_eval_points", group_env, group_start, ng, vg, vb, signal_dst, occ_dst, x, stream);
 }
 
 extern "C" int qd_eval_points_closed(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
@@ -1494,62 +1502,52 @@ extern "C" int qd_eval_points_closed(qd_handle* h, const int32_t* group_env, con
                                      double* occ_dst, int32_t* states_dst, void* stream) {
     if (!h) return QD_ERR_ARG;
     if (!n_charge) return qd_fail(h, QD_ERR_ARG, "qd_eval_points_closed: n_charge_host is NULL");
-    return qd_points_run(h, "qd_eval_points_closed", group_env, group_start, ng, vg, vb, gamma, n_charge, signal_dst, occ_dst, states_dst,
-                         stream);
+    QdBehindSearch x; x.gamma = gamma; x.n_charge = n_charge; x.states_dst = states_dst;
+    return qd_points_run(h, "qd_eval_points_closed", group_env, group_start, ng, vg, vb, signal_dst, occ_dst, x, stream);
 }
 
 extern "C" int qd_eval_points_ex(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
                                  const double* vb, double* signal_dst, double* occ_dst, const qd_points_opts* opts, void* stream) {
     static_assert(QD_LEVELS_MAX <= QD_LV_MAX, "a level per state at most");
     if (!h) return QD_ERR_ARG;
-    if (!opts) return qd_points_run(h, "qd_eval_points_ex", group_env, group_start, ng, vg, vb, nullptr, nullptr, signal_dst, occ_dst, nullptr, stream);
-    if (opts->struct_size != (int32_t)sizeof(qd_points_opts))
-        return qd_fail(h, QD_ERR_ARG, "qd_eval_points_ex: opts->struct_size is not sizeof(qd_points_opts)");
+    QdBehindSearch x;
+    if (!opts) return qd_points_run(h, "qd_eval_points_ex", group_env, group_start, ng, vg, vb, signal_dst, occ_dst, x, stream);
+    if (int rc = qd_check_struct_size(h, opts, sizeof(qd_points_opts), "qd_eval_points_ex: opts->struct_size is not sizeof(qd_points_opts)")) return rc;
     if (opts->n_levels < 0 || opts->n_levels > QD_LEVELS_MAX)
         return qd_fail(h, QD_ERR_ARG, "qd_eval_points_ex: opts->n_levels must be in 0..QD_LEVELS_MAX (8)");
     if (opts->n_levels > 0 && !opts->levels_dst)
         return qd_fail(h, QD_ERR_ARG, "qd_eval_points_ex: opts->n_levels > 0 needs opts->levels_dst");
     if (opts->states_dst && !opts->n_charge_host)
         return qd_fail(h, QD_ERR_ARG, "qd_eval_points_ex: opts->states_dst is an output of the closed regime and needs opts->n_charge_host");
-    return qd_points_run(h, "qd_eval_points_ex", group_env, group_start, ng, vg, vb, opts->gamma_host, opts->n_charge_host, signal_dst,
-                         occ_dst, opts->states_dst, stream, opts->n_levels, opts->levels_dst, opts->hnorm_dst);
+    x.gamma = opts->gamma_host; x.n_charge = opts->n_charge_host; x.states_dst = opts->states_dst;
+    x.n_levels = opts->n_levels; x.levels_dst = opts->levels_dst; x.hnorm_dst = opts->hnorm_dst;
+    return qd_points_run(h, "qd_eval_points_ex", group_env, group_start, ng, vg, vb, signal_dst, occ_dst, x, stream);
 }
 
 extern "C" int qd_eval_points_thermal(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
                                       const double* vb, const double* kT, double* signal_dst, double* occ_dst,
                                       const qd_thermal_opts* opts, void* stream) {
     if (!h) return QD_ERR_ARG;
-    if (!kT) return qd_fail(h, QD_ERR_ARG, "qd_eval_points_thermal: kT_host is NULL");
-    for (int g = 0; g < ng; ++g)
-        if (!(kT[g] > 0.0) || !(kT[g] < INFINITY))
-            return qd_fail(h, QD_ERR_ARG, "qd_eval_points_thermal: kT must be finite and > 0");
-    if (opts && opts->struct_size != (int32_t)sizeof(qd_thermal_opts))
-        return qd_fail(h, QD_ERR_ARG, "qd_eval_points_thermal: opts->struct_size is not sizeof(qd_thermal_opts)");
-    return qd_points_run(h, "qd_eval_points_thermal", group_env, group_start, ng, vg, vb, opts ? opts->gamma_host : nullptr,
-                         opts ? opts->n_charge_host : nullptr, signal_dst, occ_dst, nullptr, stream, 0, nullptr, nullptr, kT,
-                         opts ? opts->var_dst : nullptr, opts ? opts->ztail_dst : nullptr);
+    if (int rc = qd_check_kT_host(h, "qd_eval_points_thermal", kT, ng)) return rc;
+    if (int rc = qd_check_struct_size(h, opts, sizeof(qd_thermal_opts), "qd_eval_points_thermal: opts->struct_size is not sizeof(qd_thermal_opts)")) return rc;
+    QdBehindSearch x; x.kT = kT;
+    if (opts) { x.gamma = opts->gamma_host; x.n_charge = opts->n_charge_host; x.var_dst = opts->var_dst; x.ztail_dst = opts->ztail_dst; }
+    return qd_points_run(h, "qd_eval_points_thermal", group_env, group_start, ng, vg, vb, signal_dst, occ_dst, x, stream);
 }
 
 extern "C" int qd_eval_points_response(qd_handle* h, const int32_t* group_env, const int64_t* group_start, int ng, const double* vg,
                                        const double* vb, const double* kT, double* signal_dst, double* occ_dst,
                                        const qd_response_opts* opts, void* stream) {
     if (!h) return QD_ERR_ARG;
-    if (!kT) return qd_fail(h, QD_ERR_ARG, "qd_eval_points_response: kT_host is NULL");
-    for (int g = 0; g < ng; ++g)
-        if (!(kT[g] > 0.0) || !(kT[g] < INFINITY))
-            return qd_fail(h, QD_ERR_ARG, "qd_eval_points_response: kT must be finite and > 0");
-    if (opts && opts->struct_size != (int32_t)sizeof(qd_response_opts))
-        return qd_fail(h, QD_ERR_ARG, "qd_eval_points_response: opts->struct_size is not sizeof(qd_response_opts)");
+    if (int rc = qd_check_kT_host(h, "qd_eval_points_response", kT, ng)) return rc;
+    if (int rc = qd_check_struct_size(h, opts, sizeof(qd_response_opts), "qd_eval_points_response: opts->struct_size is not sizeof(qd_response_opts)")) return rc;
+    QdBehindSearch x; x.kT = kT;
+    if (opts) { x.gamma = opts->gamma_host; x.n_charge = opts->n_charge_host; x.var_dst = opts->var_dst; x.ztail_dst = opts->ztail_dst; }
+    if (opts) { x.rd.chi = opts->chi_dst; x.rd.jac = opts->jac_dst; x.rd.dsignal = opts->dsignal_dst; }
     // (with no response destination the call is qd_eval_points_thermal, which takes such envs)
-    if (group_env && opts && (opts->chi_dst || opts->jac_dst || opts->dsignal_dst))
-        for (int g = 0; g < ng; ++g)
-            if (group_env[g] >= 0 && group_env[g] < h->B && h->vc_on[(size_t)group_env[g]])
-                return qd_fail(h, QD_ERR_STATE, "qd_eval_points_response: the env carries the voltage-dependent capacitance model, whose "
-                                                "per-point scale factors make d F / d v depend on v; that chain rule is not built");
-    return qd_points_run(h, "qd_eval_points_response", group_env, group_start, ng, vg, vb, opts ? opts->gamma_host : nullptr,
-                         opts ? opts->n_charge_host : nullptr, signal_dst, occ_dst, nullptr, stream, 0, nullptr, nullptr, kT,
-                         opts ? opts->var_dst : nullptr, opts ? opts->ztail_dst : nullptr, opts ? opts->chi_dst : nullptr,
-                         opts ? opts->jac_dst : nullptr, opts ? opts->dsignal_dst : nullptr);
+    for (int g = 0; group_env && x.response() && g < ng; ++g)
+        if (group_env[g] >= 0 && group_env[g] < h->B && h->vc_on[(size_t)group_env[g]]) return qd_fail_vc(h, "qd_eval_points_response");
+    return qd_points_run(h, "qd_eval_points_response", group_env, group_start, ng, vg, vb, signal_dst, occ_dst, x, stream);
 }
 
 // numpy 'linear' percentile ranks of n values, as qd_k_percentile takes them

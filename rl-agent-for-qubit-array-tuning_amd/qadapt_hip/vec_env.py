@@ -227,6 +227,62 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _addr(t):
+    """A device tensor's address as a pointer field of an option struct; None stays NULL."""
+    return None if t is None else t.data_ptr()
+
+
+def _opts(cls, **fields):
+    """An option struct of _lib with its struct_size set."""
+    return cls(struct_size=ctypes.sizeof(cls), **fields)
+
+
+NOISE_STAGES = {"sensor": _lib.QD_NOISE_SENSOR, "radial": _lib.QD_NOISE_RADIAL, "latch": _lib.QD_NOISE_LATCH}
+
+
+def check_scan_frame(frame, vgm):
+    """A scan's frame is "virtual" or "physical", and only the virtual one takes a virtual gate matrix."""
+    if frame not in ("virtual", "physical"):
+        raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
+    if vgm is not None and frame == "physical":
+        raise ValueError("vgm has no meaning in the physical frame")
+
+
+def scan_noise_flags(noise, env_flags, family):
+    """The QD_NOISE_* stages of a scan.  noise None / False / (): none.  True: those of `env_flags`, the stages the env was
+    created with, without the radial one.  Or an iterable of {"sensor", "latch"}; "radial" raises, with the family's word
+    ("axis scans", "lines", "grids")."""
+    if noise is True:
+        return env_flags & ~_lib.QD_NOISE_RADIAL
+    names = tuple(noise) if noise else ()
+    if "radial" in names:
+        raise ValueError(f"radial noise is centred on the env's own adjacent-pair observation: not defined for {family}")
+    flags = 0
+    for k in names:
+        flags |= NOISE_STAGES[k]
+    return flags
+
+
+def scan_ranges(x_range, y_range, nq):
+    """(nq, 4) float64 rows (x lo, x hi, y lo, y hi) from one (lo, hi) pair for all queries or (nq, 2) per axis."""
+    return np.concatenate([np.broadcast_to(np.asarray(x_range, np.float64), (nq, 2)),
+                           np.broadcast_to(np.asarray(y_range, np.float64), (nq, 2))], axis=1)
+
+
+def host_vector(x, n):
+    """A scalar or (n,) values, numpy or torch, as a contiguous (n,) float64 array on the host."""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(
+        x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, np.float64), (n,)))
+
+
+def host_kT(kT, n):
+    """kT of a thermal query -- a scalar or (n,) values -- as host_vector gives it; finite and > 0"""
+    kth = host_vector(kT, n)
+    if not (np.isfinite(kth).all() and (kth > 0).all()):
+        raise ValueError(f"kT must be finite and > 0, got {kT!r}")
+    return kth
+
+
 class VecQuantumDeviceEnv:
     def __init__(self, num_envs, num_dots=None, config_path=None, qarray_config_path=None,
                  resolution=None, device=None, seed=None, env_id_offset=0, capacitance_model=None,
@@ -354,7 +410,7 @@ class VecQuantumDeviceEnv:
                     | (_lib.QD_NOISE_LATCH if lt.get("Exists") else 0))
         f = 0
         for k in noise:
-            f |= {"sensor": _lib.QD_NOISE_SENSOR, "radial": _lib.QD_NOISE_RADIAL, "latch": _lib.QD_NOISE_LATCH}[k]
+            f |= NOISE_STAGES[k]
         return f
 
     def _stream(self):
@@ -439,6 +495,18 @@ class VecQuantumDeviceEnv:
                 self._probe_serials += 1
         return int(serial) & 0xFFFFFFFFFFFFFFFF
 
+    def _scan_request(self, opts_type, flags, frame, vgm, gamma, serial, stream_base, nq, occupations):
+        """The options of a scan of nq queries as the family's struct `opts_type` (QdScanOpts, QdScanAffineOpts, QdScan1dOpts,
+        QdScanGridOpts: one layout), with vgm and gamma uploaded.  Returns (opts, keep): keep holds the tensors that opts points
+        to and the caller has not, to be kept until the call has been queued."""
+        vm = None if vgm is None else self._to_dev(vgm, torch.float64, (nq, self.N + 1, self.N + 1))
+        gm = None if gamma is None else self._to_dev(gamma, torch.float64, (nq,))
+        opts = _opts(opts_type, frame=_lib.QD_SCAN_PHYSICAL if frame == "physical" else _lib.QD_SCAN_VIRTUAL, noise_flags=int(flags),
+                     reserved=0, serial=self._query_serial(serial, flags),
+                     stream_base=int(self.env_id_offset if stream_base is None else stream_base),
+                     vgm_dev=_addr(vm), gamma_dev=_addr(gm), occ_dst=_addr(occupations))
+        return opts, (vm, gm)
+
     def probe(self, env_ids, gate_voltages, barrier_voltages, sensor_voltage=None, window=None, normalised=False,
               noise=None, serial=None, stream_base=None, occupations=False):
         """Stateless scans (qd_probe / qd_probe_ex): the reference's `array._get_obs(gate_voltages, barrier_voltages,
@@ -469,10 +537,8 @@ class VecQuantumDeviceEnv:
             _lib.check(self._h, rc, "qd_probe")
             return out
         flags = self.noise_flags if noise is True else self._noise_flags(noise)
-        opts = _lib.QdProbeOpts(struct_size=ctypes.sizeof(_lib.QdProbeOpts), noise_flags=int(flags),
-                                serial=self._query_serial(serial, flags),
-                                stream_base=int(self.env_id_offset if stream_base is None else stream_base),
-                                occ_dst=out["occupations"].data_ptr() if occupations else None)
+        opts = _opts(_lib.QdProbeOpts, noise_flags=int(flags), serial=self._query_serial(serial, flags),
+                     stream_base=int(self.env_id_offset if stream_base is None else stream_base), occ_dst=_addr(out.get("occupations")))
         rc = self._lib.qd_probe_ex(self._h, _ptr(ids), nq, _ptr(gv), _ptr(bv), _ptr(sv), _ptr(wd), _ptr(out["raw"]),
                                    _ptr(out.get("image")), _ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
         _lib.check(self._h, rc, "qd_probe_ex")
@@ -520,33 +586,17 @@ class VecQuantumDeviceEnv:
         Returns device tensors {"raw": (nq, R, R) float64}, plus, with normalised=True, {"image": (nq, R, R) float32
         normalised per query, "plohi": (nq, 2)}, plus, with occupations=True, {"occupations": (nq, R, R, N) float64}."""
         N = self.N
-        if frame not in ("virtual", "physical"):
-            raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
-        if vgm is not None and frame == "physical":
-            raise ValueError("vgm has no meaning in the physical frame")
+        check_scan_frame(frame, vgm)
         nq, ids, gv, bv, sv = self._query_inputs(env_ids, gate_voltages, barrier_voltages, sensor_voltage)
         axes = np.stack([scan_control_indices(x, N, frame, nq), scan_control_indices(y, N, frame, nq)], axis=1)
         if np.any(axes[:, 0] == axes[:, 1]):
             raise ValueError("x and y must be two different controls")
-        rng = np.concatenate([np.broadcast_to(np.asarray(x_range, np.float64), (nq, 2)),
-                              np.broadcast_to(np.asarray(y_range, np.float64), (nq, 2))], axis=1)
-        if noise is True:
-            flags = self.noise_flags & ~_lib.QD_NOISE_RADIAL
-        else:
-            if noise and "radial" in tuple(noise):
-                raise ValueError("radial noise is centred on the env's own adjacent-pair observation: not defined for axis scans")
-            flags = self._noise_flags(noise)
+        rng = scan_ranges(x_range, y_range, nq)
+        flags = scan_noise_flags(noise, self.noise_flags, "axis scans")
         ax = self._to_dev(axes.astype(np.int32), torch.int32, (nq, 2))
         rg = self._to_dev(rng, torch.float64, (nq, 4))
-        vm = None if vgm is None else self._to_dev(vgm, torch.float64, (nq, N + 1, N + 1))
-        gm = None if gamma is None else self._to_dev(gamma, torch.float64, (nq,))
         out = self._query_outputs(nq, (), normalised, occupations)
-        addr = lambda t: None if t is None else t.data_ptr()                    # noqa: E731
-        opts = _lib.QdScanOpts(struct_size=ctypes.sizeof(_lib.QdScanOpts),
-                               frame=_lib.QD_SCAN_PHYSICAL if frame == "physical" else _lib.QD_SCAN_VIRTUAL,
-                               noise_flags=int(flags), reserved=0, serial=self._query_serial(serial, flags),
-                               stream_base=int(self.env_id_offset if stream_base is None else stream_base),
-                               vgm_dev=addr(vm), gamma_dev=addr(gm), occ_dst=addr(out.get("occupations")))
+        opts, _keep = self._scan_request(_lib.QdScanOpts, flags, frame, vgm, gamma, serial, stream_base, nq, out.get("occupations"))
         rc = self._lib.qd_scan2d(self._h, _ptr(ids), nq, _ptr(ax), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv), _ptr(out["raw"]),
                                  _ptr(out.get("image")), _ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
         _lib.check(self._h, rc, "qd_scan2d")
@@ -576,31 +626,15 @@ class VecQuantumDeviceEnv:
         With unit vectors for x and y and 0 at those two controls of the base point this is scan2d (bit for bit, given the
         same gamma).  Returns what scan2d returns."""
         N = self.N
-        if frame not in ("virtual", "physical"):
-            raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
-        if vgm is not None and frame == "physical":
-            raise ValueError("vgm has no meaning in the physical frame")
+        check_scan_frame(frame, vgm)
         nq, ids, gv, bv, sv = self._query_inputs(env_ids, gate_voltages, barrier_voltages, sensor_voltage)
         dirs = np.stack([scan_axis_vectors(x, N, frame, nq), scan_axis_vectors(y, N, frame, nq)], axis=1)
-        rng = np.concatenate([np.broadcast_to(np.asarray(x_range, np.float64), (nq, 2)),
-                              np.broadcast_to(np.asarray(y_range, np.float64), (nq, 2))], axis=1)
-        if noise is True:
-            flags = self.noise_flags & ~_lib.QD_NOISE_RADIAL
-        else:
-            if noise and "radial" in tuple(noise):
-                raise ValueError("radial noise is centred on the env's own adjacent-pair observation: not defined for axis scans")
-            flags = self._noise_flags(noise)
+        rng = scan_ranges(x_range, y_range, nq)
+        flags = scan_noise_flags(noise, self.noise_flags, "axis scans")
         dr = self._to_dev(dirs, torch.float64, (nq, 2, 2 * N))
         rg = self._to_dev(rng, torch.float64, (nq, 4))
-        vm = None if vgm is None else self._to_dev(vgm, torch.float64, (nq, N + 1, N + 1))
-        gm = None if gamma is None else self._to_dev(gamma, torch.float64, (nq,))
         out = self._query_outputs(nq, (), normalised, occupations)
-        addr = lambda t: None if t is None else t.data_ptr()                    # noqa: E731
-        opts = _lib.QdScanAffineOpts(struct_size=ctypes.sizeof(_lib.QdScanAffineOpts),
-                                     frame=_lib.QD_SCAN_PHYSICAL if frame == "physical" else _lib.QD_SCAN_VIRTUAL,
-                                     noise_flags=int(flags), reserved=0, serial=self._query_serial(serial, flags),
-                                     stream_base=int(self.env_id_offset if stream_base is None else stream_base),
-                                     vgm_dev=addr(vm), gamma_dev=addr(gm), occ_dst=addr(out.get("occupations")))
+        opts, _keep = self._scan_request(_lib.QdScanAffineOpts, flags, frame, vgm, gamma, serial, stream_base, nq, out.get("occupations"))
         rc = self._lib.qd_scan_affine(self._h, _ptr(ids), nq, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv), _ptr(out["raw"]),
                                       _ptr(out.get("image")), _ptr(out.get("plohi")), ctypes.byref(opts), self._stream())
         _lib.check(self._h, rc, "qd_scan_affine")
@@ -629,33 +663,18 @@ class VecQuantumDeviceEnv:
         Returns device tensors {"raw": (nq, n) float64, "image": (nq, n) float32 normalised per line with its own 0.5 / 99.5
         percentiles, "plohi": (nq, 2)}, plus, with occupations=True, {"occupations": (nq, n, N) float64}."""
         N = self.N
-        if frame not in ("virtual", "physical"):
-            raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
-        if vgm is not None and frame == "physical":
-            raise ValueError("vgm has no meaning in the physical frame")
+        check_scan_frame(frame, vgm)
         n = int(n_points)
         if not 1 <= n <= self.R * self.R:
             raise ValueError(f"n_points must be in 1..{self.R * self.R} (R*R of this env), got {n_points}")
         nq, ids, gv, bv, sv = self._query_inputs(env_ids, gate_voltages, barrier_voltages, sensor_voltage)
         dirs = scan_axis_vectors(axis, N, frame, nq)
         rng = np.array(np.broadcast_to(np.asarray(s_range, np.float64), (nq, 2)))
-        if noise is True:
-            flags = self.noise_flags & ~_lib.QD_NOISE_RADIAL
-        else:
-            if noise and "radial" in tuple(noise):
-                raise ValueError("radial noise is centred on the env's own adjacent-pair observation: not defined for lines")
-            flags = self._noise_flags(noise)
+        flags = scan_noise_flags(noise, self.noise_flags, "lines")
         dr = self._to_dev(dirs, torch.float64, (nq, 2 * N))
         rg = self._to_dev(rng, torch.float64, (nq, 2))
-        vm = None if vgm is None else self._to_dev(vgm, torch.float64, (nq, N + 1, N + 1))
-        gm = None if gamma is None else self._to_dev(gamma, torch.float64, (nq,))
         out = self._query_outputs(nq, (), True, occupations, shape=(n,))
-        addr = lambda t: None if t is None else t.data_ptr()                    # noqa: E731
-        opts = _lib.QdScan1dOpts(struct_size=ctypes.sizeof(_lib.QdScan1dOpts),
-                                 frame=_lib.QD_SCAN_PHYSICAL if frame == "physical" else _lib.QD_SCAN_VIRTUAL,
-                                 noise_flags=int(flags), reserved=0, serial=self._query_serial(serial, flags),
-                                 stream_base=int(self.env_id_offset if stream_base is None else stream_base),
-                                 vgm_dev=addr(vm), gamma_dev=addr(gm), occ_dst=addr(out.get("occupations")))
+        opts, _keep = self._scan_request(_lib.QdScan1dOpts, flags, frame, vgm, gamma, serial, stream_base, nq, out.get("occupations"))
         rc = self._lib.qd_scan1d(self._h, _ptr(ids), nq, n, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv), _ptr(out["raw"]),
                                  _ptr(out["image"]), _ptr(out["plohi"]), ctypes.byref(opts), self._stream())
         _lib.check(self._h, rc, "qd_scan1d")
@@ -789,32 +808,20 @@ class VecQuantumDeviceEnv:
         """scan_grid (n_charge None) and scan_grid_closed; with kT, scan_grid_thermal in either regime, and with `response`
         scan_grid_response; with levels, scan_grid_levels in either regime"""
         N = self.N
-        if frame not in ("virtual", "physical"):
-            raise ValueError(f"frame must be 'virtual' or 'physical', got {frame!r}")
-        if vgm is not None and frame == "physical":
-            raise ValueError("vgm has no meaning in the physical frame")
+        check_scan_frame(frame, vgm)
         cx, cy = int(nx), int(ny)
         if cx < 1 or cy < 1 or cx * cy > self.R * self.R:
             raise ValueError(f"nx and ny must be >= 1 with nx*ny <= {self.R * self.R} (R*R of this env), got {nx} x {ny}")
         nq, ids, gv, bv, sv = self._query_inputs(env_ids, gate_voltages, barrier_voltages, sensor_voltage)
         dirs = np.stack([scan_axis_vectors(x, N, frame, nq), scan_axis_vectors(y, N, frame, nq)], axis=1)
-        rng = np.concatenate([np.broadcast_to(np.asarray(x_range, np.float64), (nq, 2)),
-                              np.broadcast_to(np.asarray(y_range, np.float64), (nq, 2))], axis=1)
-        if noise is True:
-            flags = self.noise_flags & ~_lib.QD_NOISE_RADIAL
-        else:
-            if noise and "radial" in tuple(noise):
-                raise ValueError("radial noise is centred on the env's own adjacent-pair observation: not defined for grids")
-            flags = self._noise_flags(noise)
+        rng = scan_ranges(x_range, y_range, nq)
+        flags = scan_noise_flags(noise, self.noise_flags, "grids")
         kth = None
         if kT is not None:
             if flags & _lib.QD_NOISE_LATCH:
                 raise ValueError("latching has no thermal form (the latching model holds an integer configuration, a thermal "
                                  "mean has none): a thermal grid's noise may name 'sensor' only")
-            kth = np.ascontiguousarray(np.broadcast_to(np.asarray(
-                kT.detach().cpu().numpy() if isinstance(kT, torch.Tensor) else kT, np.float64), (nq,)))
-            if not (np.isfinite(kth).all() and (kth > 0).all()):
-                raise ValueError(f"kT must be finite and > 0, got {kT!r}")
+            kth = host_kT(kT, nq)
         qd = None
         if n_charge is not None:
             if flags:
@@ -822,67 +829,47 @@ class VecQuantumDeviceEnv:
             qd = self._to_dev(closed_charges(n_charge, nq, "query"), torch.int32, (nq,))
         dr = self._to_dev(dirs, torch.float64, (nq, 2, 2 * N))
         rg = self._to_dev(rng, torch.float64, (nq, 4))
-        vm = None if vgm is None else self._to_dev(vgm, torch.float64, (nq, N + 1, N + 1))
-        gm = None if gamma is None else self._to_dev(gamma, torch.float64, (nq,))
         out = self._query_outputs(nq, (), True, occupations, shape=(cy, cx))
-        addr = lambda t: None if t is None else t.data_ptr()                    # noqa: E731
-        opts = _lib.QdScanGridOpts(struct_size=ctypes.sizeof(_lib.QdScanGridOpts),
-                                   frame=_lib.QD_SCAN_PHYSICAL if frame == "physical" else _lib.QD_SCAN_VIRTUAL,
-                                   noise_flags=int(flags), reserved=0, serial=self._query_serial(serial, flags),
-                                   stream_base=int(self.env_id_offset if stream_base is None else stream_base),
-                                   vgm_dev=addr(vm), gamma_dev=addr(gm), occ_dst=addr(out.get("occupations")))
+        opts, _keep = self._scan_request(_lib.QdScanGridOpts, flags, frame, vgm, gamma, serial, stream_base, nq, out.get("occupations"))
+        # every entry point takes `lead`, then its own inputs, `dst`, its own options and the stream
+        lead = (self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv))
+        dst = (_ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]), ctypes.byref(opts))
+        f64 = {"dtype": torch.float64, "device": self.device}
         if kth is not None:
             kd = self._to_dev(kth, torch.float64, (nq,))
             if variance:
-                out["variance"] = torch.zeros((nq, cy, cx, N), dtype=torch.float64, device=self.device)
+                out["variance"] = torch.zeros((nq, cy, cx, N), **f64)
             if ztail:
-                out["ztail"] = torch.zeros((nq, cy, cx), dtype=torch.float64, device=self.device)
+                out["ztail"] = torch.zeros((nq, cy, cx), **f64)
+            shapes = {"chi": (N, 2 * N - 1), "jacobian": (N, 2 * N), "dsignal": (2 * N,), "docc_axes": (N, 2), "dsignal_axes": (2,)}
+            for r in response:
+                out[r] = torch.zeros((nq, cy, cx) + shapes[r], **f64)
+            thermal = dict(reserved=0, n_charge_dev=_addr(qd), var_dst=_addr(out.get("variance")), ztail_dst=_addr(out.get("ztail")))
             if response:
-                shapes = {"chi": (N, 2 * N - 1), "jacobian": (N, 2 * N), "dsignal": (2 * N,), "docc_axes": (N, 2), "dsignal_axes": (2,)}
-                for r in response:
-                    out[r] = torch.zeros((nq, cy, cx) + shapes[r], dtype=torch.float64, device=self.device)
-                ropts = _lib.QdGridResponseOpts(struct_size=ctypes.sizeof(_lib.QdGridResponseOpts), reserved=0, n_charge_dev=addr(qd),
-                                                var_dst=addr(out.get("variance")), ztail_dst=addr(out.get("ztail")),
-                                                chi_dst=addr(out.get("chi")), jac_dst=addr(out.get("jacobian")),
-                                                dsignal_dst=addr(out.get("dsignal")), docc_axes_dst=addr(out.get("docc_axes")),
-                                                dsignal_axes_dst=addr(out.get("dsignal_axes")))
-                rc = self._lib.qd_scan_grid_response(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
-                                                     _ptr(kd), _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]),
-                                                     ctypes.byref(opts), ctypes.byref(ropts), self._stream())
-                _lib.check(self._h, rc, "qd_scan_grid_response")
-                return out
-            topts = _lib.QdGridThermalOpts(struct_size=ctypes.sizeof(_lib.QdGridThermalOpts), reserved=0, n_charge_dev=addr(qd),
-                                           var_dst=addr(out.get("variance")), ztail_dst=addr(out.get("ztail")))
-            rc = self._lib.qd_scan_grid_thermal(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
-                                                _ptr(kd), _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]),
-                                                ctypes.byref(opts), ctypes.byref(topts), self._stream())
-            _lib.check(self._h, rc, "qd_scan_grid_thermal")
-            return out
-        if levels:
-            out["levels"] = torch.zeros((nq, cy, cx, levels), dtype=torch.float64, device=self.device)
-            out["hnorm"] = torch.zeros((nq, cy, cx), dtype=torch.float64, device=self.device)
-            lopts = _lib.QdGridLevelsOpts(struct_size=ctypes.sizeof(_lib.QdGridLevelsOpts), n_levels=int(levels), n_charge_dev=addr(qd),
-                                          levels_dst=addr(out["levels"]), hnorm_dst=addr(out["hnorm"]))
-            rc = self._lib.qd_scan_grid_levels(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
-                                               _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]), ctypes.byref(opts),
-                                               ctypes.byref(lopts), self._stream())
-            _lib.check(self._h, rc, "qd_scan_grid_levels")
-            if levels >= 2:
-                # (+inf wherever the second level is: a point with one valid state, and one with none, where inf - inf would be nan
-                # and hnorm is 0)
-                l0, l1 = out["levels"][..., 0], out["levels"][..., 1]
-                out["gap"] = torch.where(torch.isinf(l1), l1, l1 - l0)
-                out["rel_gap"] = out["gap"] / out["hnorm"]
-            return out
-        if qd is not None:
-            rc = self._lib.qd_scan_grid_closed(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
-                                               _ptr(qd), _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]), ctypes.byref(opts),
-                                               self._stream())
-            _lib.check(self._h, rc, "qd_scan_grid_closed")
-            return out
-        rc = self._lib.qd_scan_grid(self._h, _ptr(ids), nq, cx, cy, _ptr(dr), _ptr(rg), _ptr(gv), _ptr(bv), _ptr(sv),
-                                    _ptr(out["raw"]), _ptr(out["image"]), _ptr(out["plohi"]), ctypes.byref(opts), self._stream())
-        _lib.check(self._h, rc, "qd_scan_grid")
+                name, own = "qd_scan_grid_response", _opts(
+                    _lib.QdGridResponseOpts, **thermal, chi_dst=_addr(out.get("chi")), jac_dst=_addr(out.get("jacobian")),
+                    dsignal_dst=_addr(out.get("dsignal")), docc_axes_dst=_addr(out.get("docc_axes")),
+                    dsignal_axes_dst=_addr(out.get("dsignal_axes")))
+            else:
+                name, own = "qd_scan_grid_thermal", _opts(_lib.QdGridThermalOpts, **thermal)
+            args = (*lead, _ptr(kd), *dst, ctypes.byref(own))
+        elif levels:
+            out["levels"] = torch.zeros((nq, cy, cx, levels), **f64)
+            out["hnorm"] = torch.zeros((nq, cy, cx), **f64)
+            own = _opts(_lib.QdGridLevelsOpts, n_levels=int(levels), n_charge_dev=_addr(qd), levels_dst=_addr(out["levels"]),
+                        hnorm_dst=_addr(out["hnorm"]))
+            name, args = "qd_scan_grid_levels", (*lead, *dst, ctypes.byref(own))
+        elif qd is not None:
+            name, args = "qd_scan_grid_closed", (*lead, _ptr(qd), *dst)
+        else:
+            name, args = "qd_scan_grid", (*lead, *dst)
+        _lib.check(self._h, getattr(self._lib, name)(*args, self._stream()), name)
+        if levels >= 2:
+            # (+inf wherever the second level is: a point with one valid state, and one with none, where inf - inf would be nan
+            # and hnorm is 0)
+            l0, l1 = out["levels"][..., 0], out["levels"][..., 1]
+            out["gap"] = torch.where(torch.isinf(l1), l1, l1 - l0)
+            out["rel_gap"] = out["gap"] / out["hnorm"]
         return out
 
     # ------------------------------------------------------------------ point evaluation
@@ -953,12 +940,7 @@ class VecQuantumDeviceEnv:
         if states and n_charge is None:
             raise ValueError("states=True needs n_charge: the kept states are an output of the closed regime")
         qh = None if n_charge is None else closed_charges(n_charge, n, "env id")
-        kth = None
-        if kT is not None:
-            kth = np.ascontiguousarray(np.broadcast_to(np.asarray(
-                kT.detach().cpu().numpy() if isinstance(kT, torch.Tensor) else kT, np.float64), (n,)))
-            if not (np.isfinite(kth).all() and (kth > 0).all()):
-                raise ValueError(f"kT must be finite and > 0, got {kT!r}")
+        kth = None if kT is None else host_kT(kT, n)
         if states and self.num_charge_states is None:
             raise _lib.QdError(f"qd_eval_points_closed refused (code {_lib.QD_ERR_STATE}): the full charge-state space has no "
                                "kept list of K states")
@@ -991,106 +973,47 @@ class VecQuantumDeviceEnv:
         start = np.zeros(n + 1, np.int64)
         start[1:] = np.cumsum(counts)
         total = int(start[-1])
-        gam = None
-        if gamma is not None:
-            gam = np.ascontiguousarray(np.broadcast_to(np.asarray(
-                gamma.detach().cpu().numpy() if isinstance(gamma, torch.Tensor) else gamma, np.float64), (n,)))
-        signal = torch.empty((total,), dtype=torch.float64, device=self.device) if "signal" in outputs else None
-        occ = torch.empty((total, N), dtype=torch.float64, device=self.device) if "occupations" in outputs else None
+        gam = None if gamma is None else host_vector(gamma, n)
         K = self.num_charge_states
-        kept = torch.empty((total, K, N), dtype=torch.int32, device=self.device) if states else None
-        lev = torch.empty((total, levels), dtype=torch.float64, device=self.device) if levels else None
-        hn = torch.empty((total,), dtype=torch.float64, device=self.device) if levels else None
-        var = torch.empty((total, N), dtype=torch.float64, device=self.device) if "variance" in outputs else None
-        zt = torch.empty((total,), dtype=torch.float64, device=self.device) if "ztail" in outputs else None
-        chi = jac = dsig = None
-        if response:
-            chi = torch.empty((total, N, 2 * N - 1), dtype=torch.float64, device=self.device)
-            jac = torch.empty((total, N, 2 * N), dtype=torch.float64, device=self.device)
-            dsig = torch.empty((total, 2 * N), dtype=torch.float64, device=self.device)
-        if kth is not None and response:
-            opts = _lib.QdResponseOpts(struct_size=ctypes.sizeof(_lib.QdResponseOpts))
-            if gam is not None:
-                opts.gamma_host = gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-            if qh is not None:
-                opts.n_charge_host = qh.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-            opts.var_dst = None if var is None else var.data_ptr()
-            opts.ztail_dst = None if zt is None else zt.data_ptr()
-            opts.chi_dst, opts.jac_dst, opts.dsignal_dst = chi.data_ptr(), jac.data_ptr(), dsig.data_ptr()
-            rc = 0 if total == 0 else self._lib.qd_eval_points_response(
-                self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
-                ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
-                kth.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                None if signal is None else ctypes.c_void_p(signal.data_ptr()),
-                None if occ is None else ctypes.c_void_p(occ.data_ptr()), ctypes.byref(opts), self._stream())
-            _lib.check(self._h, rc, "qd_eval_points_response")
-        elif kth is not None:
-            opts = _lib.QdThermalOpts(struct_size=ctypes.sizeof(_lib.QdThermalOpts))
-            if gam is not None:
-                opts.gamma_host = gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-            if qh is not None:
-                opts.n_charge_host = qh.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-            opts.var_dst = None if var is None else var.data_ptr()
-            opts.ztail_dst = None if zt is None else zt.data_ptr()
-            rc = 0 if total == 0 else self._lib.qd_eval_points_thermal(
-                self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
-                ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
-                kth.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                None if signal is None else ctypes.c_void_p(signal.data_ptr()),
-                None if occ is None else ctypes.c_void_p(occ.data_ptr()), ctypes.byref(opts), self._stream())
-            _lib.check(self._h, rc, "qd_eval_points_thermal")
+        # every output: name, dtype, shape of one point, whether the call has it -- in the order of the returned dict
+        f64 = torch.float64
+        table = (("states", torch.int32, (K, N), states), ("signal", f64, (), "signal" in outputs),
+                 ("occupations", f64, (N,), "occupations" in outputs), ("levels", f64, (levels,), levels), ("hnorm", f64, (), levels),
+                 ("variance", f64, (N,), "variance" in outputs), ("ztail", f64, (), "ztail" in outputs),
+                 ("chi", f64, (N, 2 * N - 1), response), ("jacobian", f64, (N, 2 * N), response), ("dsignal", f64, (2 * N,), response))
+        t = {name: torch.empty((total, *shape), dtype=dtype, device=self.device) for name, dtype, shape, wanted in table if wanted}
+        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
+        gp, qp = None if gam is None else gam.ctypes.data_as(dp), None if qh is None else qh.ctypes.data_as(ip)
+
+        def opts_of(cls, **own):
+            """the option struct of a branch with the fields they share: peak widths and total charges, variance and tail rows"""
+            thermal = {} if cls is _lib.QdPointsOpts else dict(var_dst=_addr(t.get("variance")), ztail_dst=_addr(t.get("ztail")))
+            return _opts(cls, gamma_host=gp, n_charge_host=qp, **thermal, **own)
+
+        # every entry point takes `head`, then its own inputs, `dst` and its own outputs or options, and the stream
+        head = (self._h, ids.ctypes.data_as(ip), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n, _ptr(g_all), _ptr(b_all))
+        dst = (_ptr(t.get("signal")), _ptr(t.get("occupations")))
+        if kth is not None:
+            if response:
+                name, opts = "qd_eval_points_response", opts_of(_lib.QdResponseOpts, chi_dst=_addr(t["chi"]), jac_dst=_addr(t["jacobian"]),
+                                                                dsignal_dst=_addr(t["dsignal"]))
+            else:
+                name, opts = "qd_eval_points_thermal", opts_of(_lib.QdThermalOpts)
+            args = (*head, kth.ctypes.data_as(dp), *dst, ctypes.byref(opts))
         elif levels:
-            opts = _lib.QdPointsOpts(struct_size=ctypes.sizeof(_lib.QdPointsOpts), n_levels=levels)
-            if gam is not None:
-                opts.gamma_host = gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-            if qh is not None:
-                opts.n_charge_host = qh.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-            opts.states_dst = None if kept is None else kept.data_ptr()
-            opts.levels_dst, opts.hnorm_dst = lev.data_ptr(), hn.data_ptr()
-            rc = 0 if total == 0 else self._lib.qd_eval_points_ex(
-                self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
-                ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
-                None if signal is None else ctypes.c_void_p(signal.data_ptr()),
-                None if occ is None else ctypes.c_void_p(occ.data_ptr()), ctypes.byref(opts), self._stream())
-            _lib.check(self._h, rc, "qd_eval_points_ex")
+            opts = opts_of(_lib.QdPointsOpts, n_levels=levels, states_dst=_addr(t.get("states")), levels_dst=_addr(t["levels"]),
+                           hnorm_dst=_addr(t["hnorm"]))
+            name, args = "qd_eval_points_ex", (*head, *dst, ctypes.byref(opts))
         elif qh is not None:
-            rc = 0 if total == 0 else self._lib.qd_eval_points_closed(
-                self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
-                ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
-                None if gam is None else gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                qh.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                None if signal is None else ctypes.c_void_p(signal.data_ptr()),
-                None if occ is None else ctypes.c_void_p(occ.data_ptr()),
-                None if kept is None else ctypes.c_void_p(kept.data_ptr()), self._stream())
-            _lib.check(self._h, rc, "qd_eval_points_closed")
+            name, args = "qd_eval_points_closed", (*head, gp, qp, *dst, _ptr(t.get("states")))
         else:
-            rc = 0 if total == 0 else self._lib.qd_eval_points(          # (an empty tensor has no address to hand over)
-                self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
-                ctypes.c_void_p(g_all.data_ptr()), ctypes.c_void_p(b_all.data_ptr()),
-                None if gam is None else gam.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                None if signal is None else ctypes.c_void_p(signal.data_ptr()),
-                None if occ is None else ctypes.c_void_p(occ.data_ptr()), self._stream())
-            _lib.check(self._h, rc, "qd_eval_points")
-        out = {}
+            name, args = "qd_eval_points", (*head, gp, *dst)
+        if total:                                                        # (an empty tensor has no address to hand over)
+            _lib.check(self._h, getattr(self._lib, name)(*args, self._stream()), name)
+        if ragged:
+            return {k: [v[start[i]:start[i + 1]] for i in range(n)] for k, v in t.items()}
         m = counts[0] if n else 0
-        if kept is not None:
-            out["states"] = [kept[start[i]:start[i + 1]] for i in range(n)] if ragged else kept.reshape(n, m, K, N)
-        if signal is not None:
-            out["signal"] = [signal[start[i]:start[i + 1]] for i in range(n)] if ragged else signal.reshape(n, m)
-        if occ is not None:
-            out["occupations"] = [occ[start[i]:start[i + 1]] for i in range(n)] if ragged else occ.reshape(n, m, N)
-        if levels:
-            out["levels"] = [lev[start[i]:start[i + 1]] for i in range(n)] if ragged else lev.reshape(n, m, levels)
-            out["hnorm"] = [hn[start[i]:start[i + 1]] for i in range(n)] if ragged else hn.reshape(n, m)
-        if var is not None:
-            out["variance"] = [var[start[i]:start[i + 1]] for i in range(n)] if ragged else var.reshape(n, m, N)
-        if zt is not None:
-            out["ztail"] = [zt[start[i]:start[i + 1]] for i in range(n)] if ragged else zt.reshape(n, m)
-        if response:
-            out["chi"] = [chi[start[i]:start[i + 1]] for i in range(n)] if ragged else chi.reshape(n, m, N, 2 * N - 1)
-            out["jacobian"] = [jac[start[i]:start[i + 1]] for i in range(n)] if ragged else jac.reshape(n, m, N, 2 * N)
-            out["dsignal"] = [dsig[start[i]:start[i + 1]] for i in range(n)] if ragged else dsig.reshape(n, m, 2 * N)
-        return out
+        return {k: v.reshape(n, m, *v.shape[1:]) for k, v in t.items()}
 
     # ------------------------------------------------------------------ reset
     def load_new_devices(self, env_ids=None, seed=None):
